@@ -32,7 +32,8 @@ on this host on a bounded sample: 1 thread and all host threads, the headline's 
 of sampled streams the legs check their bytes against; rank 0 / N=1 only), "kernels_ms_per_step", "inflate_gib_s" /
 "deflate_gib_s", and the untimed legs, each with its parity sample and its share of the roofline: "e2e_gib_s"
 (PCIe-inclusive host forms), "text_gib_s", "best_gib_s", "corpus_gib_s", "one_stream_ms", "long_members" (a call of 64
-members of 1 MiB), "c4_leg".
+members of 1 MiB), "c4_leg"; with --dump-outputs DIR, "dump_outputs" (what the last timed step computed, written to DIR as
+.npy files: the files, their bytes, the streams they cover).
 """
 import argparse
 import json
@@ -70,6 +71,10 @@ def parse_args(argv=None):
                     help="a second profiled pass with ONE slice: every kernel launched over the whole batch with nothing beside it "
                          "(roofline.*.alone).  Off by default so that a rocprofv3 summary of the default command holds only the "
                          "launches the timed region makes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed for rank 0's streams to DIR/<name>.npy: every "
+                         "stream's status, length, CRC-32 and byte sum (float64) and the bytes of a fixed, seeded sample of the "
+                         "streams (float32), at most 64 MB in all -- for comparing two builds output for output")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)  # the cpu_baseline leg's own process
     return ap.parse_args(argv)
 
@@ -646,6 +651,15 @@ def run_c2(args, rank, local_rank, world, dev, cpu=None):
         torch.cuda.synchronize()
 
     elapsed, ranks = timed_steps(step, barrier, args.steps, args.warmup, world, dev)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (before the profiled steps below write the same buffers again)
+        last, ilast = batch.results_from_device(d_res), batch.results_from_device(d_ires)
+        dumped = dump_outputs(args.dump_outputs, n, {
+            "deflate_status": last["status"], "deflate_out_len": last["out_len"], "deflate_crc32": last["checksum"],
+            "deflate_byte_sum": stream_byte_sums(comp, descs["dst_off"], last["out_len"]),
+            "inflate_status": ilast["status"], "inflate_out_len": ilast["out_len"], "inflate_crc32": ilast["checksum"],
+            "inflate_byte_sum": stream_byte_sums(out, idescs["dst_off"], ilast["out_len"]),
+        }, {"deflate_bytes": (comp, descs["dst_off"], last["out_len"], cap), "inflate_bytes": (out, idescs["dst_off"], ilast["out_len"], L)})
 
     psteps = max(1, min(args.steps, 3))
     t = {"def": 0.0, "inf": 0.0}
@@ -692,6 +706,8 @@ def run_c2(args, rank, local_rank, world, dev, cpu=None):
         "roofline": roof,
         "kernels_ms_per_step": per_step,
     }
+    if dumped:
+        line["dump_outputs"] = dumped
     if world == 1 and not args.no_extra_legs:
         line.update(extra_legs(ctx, dev, n, L, cpu))
     return line
@@ -837,6 +853,66 @@ def sampled_equal(comp, descs, res, expect):
     return ok
 
 
+# ---- --dump-outputs ----------------------------------------------------------------------------------
+
+DUMP_BYTES = 64 * 10 ** 6  # one dump, all its files together
+DUMP_SEED = 0x5EED         # which streams are sampled: a fixed choice, the same in every run of the same shape
+
+
+def stream_byte_sums(buf, offs, lens):
+    """the sum of every stream's bytes, reduced on buf's device (buf: uint8 tensor, stream j at offs[j] = j x stride,
+    lens[j] bytes long), as a float64 host array"""
+    import numpy as np
+    import torch
+
+    n = len(offs)
+    stride = int(offs[1]) - int(offs[0]) if n > 1 else max(int(lens[0]), 1)
+    assert np.array_equal(np.asarray(offs, np.int64), np.arange(n, dtype=np.int64) * stride), "not a uniform layout"
+    lens_d = torch.from_numpy(np.asarray(lens, np.int64)).to(buf.device)
+    cols = torch.arange(stride, device=buf.device)
+    sums = torch.empty(n, dtype=torch.int64, device=buf.device)
+    step = max(1, (256 << 20) // stride)  # streams per slab
+    for a in range(0, n, step):
+        b = min(n, a + step)
+        v = buf[a * stride:b * stride]
+        v = torch.nn.functional.pad(v, (0, (b - a) * stride - v.numel())).view(b - a, stride)
+        sums[a:b] = torch.where(cols < lens_d[a:b, None], v, 0).sum(dim=1, dtype=torch.int64)
+    return sums.cpu().numpy().astype(np.float64)
+
+
+def dump_outputs(path, n, per_stream, rows):
+    """Write what the last timed step computed to path/<name>.npy.  per_stream: name -> one number per stream (float64);
+    rows: name -> (uint8 tensor, offsets, lengths, width): a sampled stream's bytes as a float32 row of `width`, zero past its
+    length.  The per-stream numbers of every stream (of a seeded sample of them where n is too large for a quarter of
+    DUMP_BYTES: streams.npy says which), the rows of a seeded sample of at most 64 streams (sample_streams.npy) in the rest.
+    Returns what was written, for the JSON line."""
+    import numpy as np
+
+    order = np.random.default_rng(DUMP_SEED).permutation(n)
+    m = min(n, DUMP_BYTES // 4 // (8 * (len(per_stream) + 1)))
+    streams = np.arange(n) if m == n else np.sort(order[:m])
+    out = {"streams": streams.astype(np.float64)}
+    out.update({k: np.asarray(v, np.float64)[streams] for k, v in per_stream.items()})
+    room = DUMP_BYTES - sum(a.nbytes for a in out.values()) - 256 * (len(out) + len(rows) + 1)  # (npy headers)
+    width = sum(r[3] for r in rows.values())
+    k = max(1, min(64, n, room // (4 * width)))
+    shrink = min(1.0, room / (4.0 * width * k))  # streams too long for the room even alone: their first bytes
+    sample = np.sort(order[:k])
+    out["sample_streams"] = sample.astype(np.float64)
+    for name, (buf, offs, lens, w) in rows.items():
+        w = int(w * shrink)
+        a = np.zeros((k, w), np.float32)
+        for i, j in enumerate(sample):
+            ln = min(int(lens[j]), w)
+            a[i, :ln] = buf[int(offs[j]):int(offs[j]) + ln].cpu().numpy()
+        out[name] = a
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "files": sorted(out), "bytes": sum(a.nbytes for a in out.values()), "streams": len(streams),
+            "sampled_streams": k}
+
+
 def device_round_trip(ctx, dev, src, n, L, level, reps=2, expect=None):
     """One leg: n streams of L bytes held in `src`, device-resident, deflate (CRC-32) then inflate, checked by the
     round trip and -- a few sampled streams -- byte for byte against the oracle's output (expect).  Returns GiB/s and
@@ -933,6 +1009,12 @@ def run_c4(args, rank, local_rank, world, dev, cpu=None):
     assert (res["status"] == 0).all(), "deflate failed"
     assert len(records) == members
     C_all = int(records["compressed_size"].astype(np.uint64).sum())
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (before the archive check, which deflates into the same arena again)
+        dumped = dump_outputs(args.dump_outputs, n, {
+            "deflate_status": res["status"], "deflate_out_len": res["out_len"], "deflate_crc32": res["checksum"],
+            "deflate_byte_sum": stream_byte_sums(comp, descs["dst_off"], res["out_len"]),
+        }, {"deflate_bytes": (comp, descs["dst_off"], res["out_len"], cap)})
     check = None if args.no_archive_check else c4_check(ctx, dev, rank, world, parts, paths, records, comp, descs, L, bits, args.level)
 
     t4 = {"def": 0.0, "inf": 0.0}
@@ -973,6 +1055,8 @@ def run_c4(args, rank, local_rank, world, dev, cpu=None):
         "kernels_ms_per_step": per_step,
         "archive_check": check,
     }
+    if dumped:
+        line["dump_outputs"] = dumped
     return line
 
 

@@ -81,3 +81,37 @@ def test_cpu_baseline_leg_hands_over_the_oracles_samples():
     assert sorted(s) == ["one_c1_zeros_1mib", "text_default"] and sorted(s["text_default"]) == ["0", "1", "2", "3"]
     st, comp, crc = oracle.deflate(bench.text_pieces(65536)[2], level=2, crc_op=oracle.CRC_CRC32)
     assert s["text_default"]["2"] == [hashlib.sha256(comp).hexdigest()[:24], crc, len(comp)]
+
+
+def test_dump_outputs_is_a_bounded_seeded_sample(tmp_path):
+    """--dump-outputs on host tensors: every stream's numbers as float64, the bytes of the same seeded sample of streams in
+    every run as float32 rows (zero past a stream's length), and all files together within the 64 MB bound -- also when
+    one stream alone is longer than that"""
+    import numpy as np
+    import torch
+
+    import bench
+
+    n, slot = 300, 4352
+    buf = torch.randint(0, 256, (n * slot + 256,), dtype=torch.uint8, generator=torch.Generator().manual_seed(5))
+    offs = np.arange(n, dtype=np.uint64) * np.uint64(slot)
+    lens = np.random.default_rng(1).integers(0, slot, n).astype(np.uint64)
+    sums = bench.stream_byte_sums(buf, offs, lens)
+    host = buf.numpy()
+    assert sums.tolist() == [int(host[int(o):int(o) + int(k)].astype(np.int64).sum()) for o, k in zip(offs, lens)]
+    for d in ("a", "b"):
+        r = bench.dump_outputs(str(tmp_path / d), n, {"out_len": lens, "byte_sum": sums}, {"bytes": (buf, offs, lens, slot)})
+        assert r["streams"] == n and r["sampled_streams"] == 64
+    for f in sorted(os.listdir(tmp_path / "a")):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    rows, sample = np.load(tmp_path / "a" / "bytes.npy"), np.load(tmp_path / "a" / "sample_streams.npy").astype(int)
+    assert np.array_equal(np.load(tmp_path / "a" / "byte_sum.npy"), sums)
+    for i, j in enumerate(sample):
+        k = int(lens[j])
+        assert np.array_equal(rows[i, :k], host[int(offs[j]):int(offs[j]) + k]) and not rows[i, k:].any()
+    big = 48 << 20
+    buf = torch.zeros(2 * big, dtype=torch.uint8)
+    offs, lens = np.arange(2, dtype=np.uint64) * np.uint64(big), np.full(2, big, np.uint64)
+    bench.dump_outputs(str(tmp_path / "c"), 2, {"out_len": lens}, {"x": (buf, offs, lens, big), "y": (buf, offs, lens, big)})
+    assert sum(os.path.getsize(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c")) <= 64 * 10 ** 6
