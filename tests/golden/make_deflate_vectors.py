@@ -41,26 +41,36 @@ PLAN = [(n, ("none",) + LEVELS3) for n in ("trip0", "trip1", "trip2", "trip3", "
     ("record_table", LEVELS3), ("rand70k", ("none", "default")),
     ("ff4200", ("none", "default")), ("rand200k", ("none", "default")),
 ]
-# ... and every named case of the parity tests (tests/util.py deflate_cases), at the three levels
+# ... and every named case of the parity tests (tests/util.py deflate_cases), at the three levels -- among them the
+# inputs that sit on the block chooser's ties and next to Q3's padding (util.TIE_CASES), so the kernels are held to them
 PLAN += [(n, LEVELS3) for n in sorted(util.deflate_cases()) if n not in dict(PLAN)]
 
 
 def one(job):
     name, level = job
-    data = util.vector_input(name)
     t = time.time()
+    rec = record(Z, util.vector_input(name), level)
+    rec["seconds"] = round(time.time() - t, 1)
+    return name, level, rec
+
+
+def record(Z, data, level, adler_by_encoder=False):
+    """what the reading `Z` (this module's zd_second_reading, or a mutant of it: tests/golden/mutants.py) makes of
+    `data` at `level`: one entry of the file's "levels"."""
     crc, comp, stats = Z.crc_and_deflate(data, level, Z.CRC_32)
-    # the Adler-32 of the fused form: one update per block over the block's source bytes (zd.ml:1081-1086).  The block
-    # cuts are the parse's, so it is replayed over them instead of running the parse twice.
-    adler = 1
-    pos = 0
-    for ln in stats["block_src_lens"]:
-        adler = Z.adler_32_string_update(adler, data, pos, ln)
-        pos += ln
-    assert pos == len(data)
-    return name, level, {
-        "clen": len(comp), "sha256": hashlib.sha256(comp).hexdigest(), "crc32": crc, "adler32_fused": adler & 0xFFFFFFFF,
-        "blocks": compact(stats["blocks"]), "huffman_retries": stats.get("huffman_retries", 0), "seconds": round(time.time() - t, 1)}
+    if adler_by_encoder:
+        adler = Z.crc_and_deflate(data, level, Z.ADLER_32)[0]
+    else:
+        # the Adler-32 of the fused form: one update per block over the block's source bytes (zd.ml:1081-1086).  The
+        # block cuts are the parse's, so it is replayed over them instead of running the parse twice.
+        adler = 1
+        pos = 0
+        for ln in stats["block_src_lens"]:
+            adler = Z.adler_32_string_update(adler, data, pos, ln)
+            pos += ln
+        assert pos == len(data)
+    return {"clen": len(comp), "sha256": hashlib.sha256(comp).hexdigest(), "crc32": crc, "adler32_fused": adler & 0xFFFFFFFF,
+            "blocks": compact(stats["blocks"]), "huffman_retries": stats.get("huffman_retries", 0)}
 
 
 def compact(kinds):

@@ -1,6 +1,7 @@
 """Parity of the HIP path against the CPU oracle, through the C ABI
 (include/zipc_hip.h), on a real MI355X.  Bar: bit-exact bytes, identical
 accept/reject status, identical checksums (integer/byte work: no tolerance)."""
+import os
 import random
 import zlib
 
@@ -841,6 +842,43 @@ def _vectors():
     return json.load(open(os.path.join(util.GOLDEN, "deflate_vectors.json")))
 
 
+# Each form the library can take is held to the vectors: ZIPC_TEST_VECTOR_FORM names the override this process runs
+# under (test_the_second_readings_vectors_under_overrides below starts one process per form, since the library reads
+# its switches once per process), and the kernels a form must launch are checked so an override cannot miss its path.
+VECTOR_FORMS = {
+    # few long streams: parse by segments, blocks coded by a wave each (deflate_plan .. _scan .. _seal): the tie inputs'
+    # two blocks are chosen by deflate_scan_kernel's copy of the chooser
+    "parse-segments": ({"ZIPC_HIP_PARSE_SEGMENTS": "1", "ZIPC_HIP_PARSE_SEG": "4096"},
+                       {"lz_parse_spec", "lz_parse_stitch", "deflate_plan", "deflate_scan", "deflate_seal"}, set()),
+    # a wave per stream for parse and blocks: deflate_emit_kernel's wave_choose
+    "one-wave-forms": ({"ZIPC_HIP_PARSE_SEGMENTS": "0"}, {"lz_parse", "deflate_emit"}, {"lz_parse_spec", "deflate_scan"}),
+    "chain-peel": ({"ZIPC_HIP_CHAIN": "peel"}, {"lz_chain", "lz_match"}, set()),
+    "match-form-1": ({"ZIPC_HIP_MATCH_FORM": "1"}, {"lz_match"}, set()),
+    "match-form-2": ({"ZIPC_HIP_MATCH_FORM": "2"}, {"lz_match"}, set()),
+}
+
+
+def _check_form(ctx, what, launched):
+    """the kernels `launched` (names, zipc_hip_kernel_times) are the ones the form under test must launch"""
+    form = os.environ.get("ZIPC_TEST_VECTOR_FORM")
+    if not form:
+        return
+    env, need, never = VECTOR_FORMS[form]
+    assert all(os.environ.get(k) == v for k, v in env.items()), (form, what)
+    assert need <= launched and not (never & launched), (form, what, sorted(launched))
+
+
+def _profiled(ctx):
+    ctx.set_profiling(True)
+    ctx.reset_kernel_times()
+
+
+def _launched(ctx):
+    names = {k for k, (n, ms) in ctx.kernel_times().items() if n}
+    ctx.set_profiling(False)
+    return names
+
+
 def test_deflate_host_forms_equal_the_second_readings_vectors(gpu_ctx):
     import hashlib
 
@@ -848,15 +886,20 @@ def test_deflate_host_forms_equal_the_second_readings_vectors(gpu_ctx):
 
     doc = _vectors()
     checked = 0
-    for name, v in doc["vectors"].items():
-        data = util.vector_input(name)
-        for level, want in v["levels"].items():
-            crc, cs = Z.crc_32_and_deflate(data, level=level).get_ok()
-            assert (len(cs), hashlib.sha256(cs).hexdigest(), crc) == (want["clen"], want["sha256"], want["crc32"]), (name, level)
-            adler, cs2 = Z.adler_32_and_deflate(data, level=level).get_ok()
-            assert cs2 == cs and adler == want["adler32_fused"], (name, level)  # per-block chaining, signed remainder (Q6/Q7)
-            checked += 1
-    assert checked >= 130
+    _profiled(gpu_ctx)
+    try:
+        for name, v in doc["vectors"].items():
+            data = util.vector_input(name)
+            for level, want in v["levels"].items():
+                crc, cs = Z.crc_32_and_deflate(data, level=level).get_ok()
+                assert (len(cs), hashlib.sha256(cs).hexdigest(), crc) == (want["clen"], want["sha256"], want["crc32"]), (name, level)
+                adler, cs2 = Z.adler_32_and_deflate(data, level=level).get_ok()
+                assert cs2 == cs and adler == want["adler32_fused"], (name, level)  # per-block chaining, signed remainder (Q6/Q7)
+                checked += 1
+    finally:
+        launched = _launched(gpu_ctx)
+    assert checked >= 170
+    _check_form(gpu_ctx, "host forms", launched)
     for name, want in doc["adler32_whole"].items():
         assert Z.Adler_32.string(util.vector_input(name)) == want, name
 
@@ -870,26 +913,87 @@ def test_deflate_batch_form_equals_the_second_readings_vectors(gpu_ctx):
 
     dev = torch.device("cuda", 0)
     doc = _vectors()
-    for level, lv in (("fast", 1), ("default", 2), ("best", 3)):
-        names = [n for n, v in doc["vectors"].items() if level in v["levels"]]
-        streams = [util.vector_input(n) for n in names]
-        src_off = np.cumsum([0] + [len(s) for s in streams[:-1]]).astype(np.uint64)
-        caps = [batch.deflate_bound(len(s)) for s in streams]
-        slots = [(c + 255) // 256 * 256 for c in caps]
-        dst_off = np.cumsum([0] + slots[:-1]).astype(np.uint64)
-        descs = batch.make_descs(src_off, [len(s) for s in streams], dst_off, caps)
-        src = torch.from_numpy(np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()).to(dev)
-        d_descs = batch.to_device(descs, dev)
-        total = int(sum(len(s) for s in streams))
-        for crc_op, key in ((1, "crc32"), (2, "adler32_fused")):
-            dst = torch.zeros(int(sum(slots)) + 256, dtype=torch.uint8, device=dev)
-            d_res = torch.zeros(len(streams) * 16, dtype=torch.uint8, device=dev)
-            batch.deflate_batch(gpu_ctx, src, dst, d_descs, d_res, len(streams), max(len(s) for s in streams), total, lv, crc_op)
-            res = batch.results_from_device(d_res)
-            out = dst.cpu().numpy()
-            for i, n in enumerate(names):
-                want = doc["vectors"][n]["levels"][level]
-                assert res["status"][i] == 0 and int(res["out_len"][i]) == want["clen"], (n, level)
-                o = int(dst_off[i])
-                assert hashlib.sha256(out[o:o + want["clen"]].tobytes()).hexdigest() == want["sha256"], (n, level)
-                assert int(res["checksum"][i]) == want[key], (n, level, key)
+    _profiled(gpu_ctx)
+    try:
+        for level, lv in (("fast", 1), ("default", 2), ("best", 3)):
+            names = [n for n, v in doc["vectors"].items() if level in v["levels"]]
+            streams = [util.vector_input(n) for n in names]
+            src_off = np.cumsum([0] + [len(s) for s in streams[:-1]]).astype(np.uint64)
+            caps = [batch.deflate_bound(len(s)) for s in streams]
+            slots = [(c + 255) // 256 * 256 for c in caps]
+            dst_off = np.cumsum([0] + slots[:-1]).astype(np.uint64)
+            descs = batch.make_descs(src_off, [len(s) for s in streams], dst_off, caps)
+            src = torch.from_numpy(np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()).to(dev)
+            d_descs = batch.to_device(descs, dev)
+            total = int(sum(len(s) for s in streams))
+            for crc_op, key in ((1, "crc32"), (2, "adler32_fused")):
+                dst = torch.zeros(int(sum(slots)) + 256, dtype=torch.uint8, device=dev)
+                d_res = torch.zeros(len(streams) * 16, dtype=torch.uint8, device=dev)
+                batch.deflate_batch(gpu_ctx, src, dst, d_descs, d_res, len(streams), max(len(s) for s in streams), total, lv, crc_op)
+                res = batch.results_from_device(d_res)
+                out = dst.cpu().numpy()
+                for i, n in enumerate(names):
+                    want = doc["vectors"][n]["levels"][level]
+                    assert res["status"][i] == 0 and int(res["out_len"][i]) == want["clen"], (n, level)
+                    o = int(dst_off[i])
+                    assert hashlib.sha256(out[o:o + want["clen"]].tobytes()).hexdigest() == want["sha256"], (n, level)
+                    assert int(res["checksum"][i]) == want[key], (n, level, key)
+    finally:
+        launched = _launched(gpu_ctx)
+    _check_form(gpu_ctx, "batch form", launched)
+
+
+def test_deflate_many_form_equals_the_second_readings_vectors(gpu_ctx):
+    """zipc_hip_deflate_many, the host-pointer form of many streams: one call holds every vector of a level"""
+    import ctypes as C
+    import hashlib
+
+    from zipc_amd import _lib
+
+    lib = _lib.lib()
+    doc = _vectors()
+    _profiled(gpu_ctx)
+    try:
+        for level, lv in LEVELS.items():
+            names = [n for n, v in doc["vectors"].items() if level in v["levels"]]
+            datas = [util.vector_input(n) for n in names]
+            n = len(datas)
+            keep = [np.frombuffer(d, np.uint8) if d else np.zeros(1, np.uint8) for d in datas]
+            caps = [int(lib.zipc_hip_deflate_bound(len(d))) for d in datas]
+            for crc_op, key in ((1, "crc32"), (2, "adler32_fused")):
+                outs = [np.full(c + 16, 0xA5, np.uint8) for c in caps]
+                res = (_lib.StreamResult * n)()
+                assert lib.zipc_hip_deflate_many(gpu_ctx.handle, n, (C.c_void_p * n)(*[a.ctypes.data for a in keep]),
+                                                 (C.c_size_t * n)(*[len(d) for d in datas]), lv, crc_op,
+                                                 (C.c_void_p * n)(*[a.ctypes.data for a in outs]), (C.c_size_t * n)(*caps),
+                                                 res) == 0, level
+                for i, name in enumerate(names):
+                    want = doc["vectors"][name]["levels"][level]
+                    assert int(res[i].status) == 0 and int(res[i].out_len) == want["clen"], (name, level)
+                    assert hashlib.sha256(outs[i][:want["clen"]].tobytes()).hexdigest() == want["sha256"], (name, level)
+                    assert int(res[i].checksum) == want[key], (name, level, key)
+                    assert (outs[i][caps[i]:] == 0xA5).all(), (name, level)
+    finally:
+        launched = _launched(gpu_ctx)
+    # (every form takes the tie inputs: streams of two blocks, and of 16 segments of 4096 positions)
+    assert sum(1 for n in util.TIE_CASES if doc["vectors"][n]["len"] > 65534) >= 10
+    _check_form(gpu_ctx, "many form", launched)
+
+
+@pytest.mark.parametrize("form", list(VECTOR_FORMS))
+def test_the_second_readings_vectors_under_overrides(form):
+    """the three tests above in a process of their own under each override that picks another exact form"""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(util.HERE)
+    e = dict(os.environ)
+    e.update(VECTOR_FORMS[form][0])
+    e["ZIPC_TEST_VECTOR_FORM"] = form
+    tests = ["tests/test_gpu_parity.py::" + t for t in ("test_deflate_host_forms_equal_the_second_readings_vectors",
+                                                        "test_deflate_batch_form_equals_the_second_readings_vectors",
+                                                        "test_deflate_many_form_equals_the_second_readings_vectors")]
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"] + tests, cwd=root,
+                       env=e, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+    out = r.stdout.decode()
+    assert r.returncode == 0 and "3 passed" in out, (form, out[-3000:])

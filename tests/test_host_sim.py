@@ -432,3 +432,41 @@ def test_inflate_token_form_resolves_to_the_plain_decode(sim, oracle):
                 ol = C.c_uint64()
                 st = sim.sim_inflate_token(raw, len(raw), dst, len(data), follow, desc, cut, C.byref(ol))
                 assert st == 0 and ol.value == len(data) and dst.raw[:len(data)] == data, (name, enc, follow, desc, cut)
+
+
+def test_coder_choose_mutants_are_killed(oracle, tmp_path):
+    """tools/kernel_mutants.py's mutants of coder_choose (the block chooser's two `<=` and Q3's 8 bits of padding, the
+    host models' copy of wave_choose and deflate_scan_kernel's): each built into a host model of its own, each must
+    change the bytes of an input that sits on its line (util.TIE_CASES).  The GPU copies: tools/kernel_mutants.py."""
+    import os
+    import shutil
+    import subprocess
+
+    from host_sim import HERE as SIM_DIR, SRCS, _bind
+    from tools import kernel_mutants as KM
+
+    ties = util.tie_cases()
+    rows = []
+    for m in KM.LANE_MUTANTS:
+        d = tmp_path / m[0]
+        csrc = KM.mutated_tree(m, str(d))
+        sim_dir = d / "tests" / "host_sim"
+        os.makedirs(sim_dir)
+        for f in os.listdir(SIM_DIR):
+            if f.endswith((".cpp", ".h")):
+                shutil.copy(os.path.join(SIM_DIR, f), sim_dir / f)
+        assert os.path.exists(os.path.join(csrc, "deflate_lane.h"))
+        so = str(sim_dir / "libhost_sim.so")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-I", str(sim_dir), "-o", so]
+                       + [str(sim_dir / s) for s in SRCS], check=True)
+        msim = _bind(C.CDLL(so))
+        changed = []
+        for name, (level, _, _) in util.TIE_CASES.items():
+            lv = oracle.LEVELS[level]
+            st0, c0, a0 = oracle.deflate(ties[name], level=lv, crc_op=oracle.CRC_ADLER32)
+            st, c, a, _ = sim_deflate(msim, oracle, ties[name], lv)
+            if (st, c) != (st0, c0):
+                changed.append(name)
+        rows.append((m[0], changed))
+    print("\n".join("%-28s %s" % (n, ("killed by " + " ".join(c)) if c else "SURVIVED") for n, c in rows))
+    assert all(c for _, c in rows), rows

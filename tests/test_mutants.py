@@ -1,0 +1,135 @@
+"""The mutation table (tests/golden/mutants.py): every one-line mutant of either reading of the reference's encoder
+must change a committed vector of tests/golden/deflate_vectors.json.  No GPU."""
+import concurrent.futures
+import hashlib
+import json
+import os
+import sys
+
+import pytest
+
+import util
+
+sys.path.insert(0, util.GOLDEN)
+import mutants  # noqa: E402
+
+KINDS = {0: "none", 1: "fixed", 2: "dynamic"}
+
+
+def _vectors():
+    return json.load(open(os.path.join(util.GOLDEN, "deflate_vectors.json")))
+
+
+def _compact(kinds):
+    out = []
+    for k in kinds:
+        if out and out[-1][0] == k:
+            out[-1][1] += 1
+        else:
+            out.append([k, 1])
+    return " ".join(k if n == 1 else "%s*%d" % (k, n) for k, n in out)
+
+
+def _oracle_changes(O, doc):
+    """the committed vectors the loaded oracle does not reproduce: [(name, level or "adler32_whole", field)]"""
+    changed = []
+    for name, v in doc["vectors"].items():
+        data = util.vector_input(name)
+        for level, want in v["levels"].items():
+            lv = O.LEVELS[level]
+            O.huffman_retries(reset=True)
+            st, c, crc, blocks = O.deflate_trace(data, level=lv, crc_op=O.CRC_CRC32)
+            retries = sum(O.huffman_retries())
+            st2, c2, adler = O.deflate(data, level=lv, crc_op=O.CRC_ADLER32)
+            got = {"clen": len(c), "sha256": hashlib.sha256(c).hexdigest(), "crc32": crc, "adler32_fused": adler,
+                   "blocks": _compact([KINDS[b.kind] for b in blocks]), "huffman_retries": retries}
+            diff = [k for k in want if got[k] != want[k]]
+            if st != 0 or st2 != 0 or diff:
+                changed.append((name, level, diff[0] if diff else "status"))
+    for name, want in doc["adler32_whole"].items():
+        if O.adler32(util.vector_input(name)) != want:
+            changed.append((name, "adler32_whole", "adler32"))
+    return changed
+
+
+@pytest.fixture(scope="module")
+def oracle_mutants(tmp_path_factory):
+    """every oracle mutant built with gcc (as oracle/Makefile builds the oracle): name -> .so"""
+    d = str(tmp_path_factory.mktemp("oracle_mutants"))
+    with concurrent.futures.ThreadPoolExecutor(max_workers=os.cpu_count() or 1) as ex:
+        sos = list(ex.map(lambda m: mutants.build_oracle(m, d), mutants.MUTANTS))
+    return {m.name: so for m, so in zip(mutants.MUTANTS, sos)}
+
+
+def test_the_table_is_whole():
+    names = [m.name for m in mutants.MUTANTS]
+    assert len(names) == len(set(names)) >= 14
+    doc = _vectors()
+    for m in mutants.MUTANTS:
+        name, level = m.killer
+        assert level in doc["vectors"][name]["levels"], m.name
+        assert m.c[0] != m.c[1] and m.py[0] != m.py[1], m.name
+
+
+def test_every_oracle_mutant_changes_a_committed_vector(oracle, oracle_mutants, capsys):
+    O = oracle
+    doc = _vectors()
+    assert _oracle_changes(O, doc) == []  # the real oracle reproduces every vector (so a change below is the mutant's)
+    rows, survivors = [], []
+    saved_lib, saved_env = O._lib, os.environ.get("ZD_ORACLE_LIB")
+    try:
+        for m in mutants.MUTANTS:
+            os.environ["ZD_ORACLE_LIB"] = oracle_mutants[m.name]
+            O._lib = None
+            O.lib()
+            changed = _oracle_changes(O, doc)
+            killed_by_named = any((n, lv) == m.killer for n, lv, _ in changed)
+            rows.append((m, changed, killed_by_named))
+            if not changed or not killed_by_named:
+                survivors.append(m.name)
+    finally:
+        O._lib = saved_lib
+        if saved_env is None:
+            os.environ.pop("ZD_ORACLE_LIB", None)
+        else:
+            os.environ["ZD_ORACLE_LIB"] = saved_env
+    with capsys.disabled():
+        print("\noracle/zd_oracle.c mutants against %d committed vectors" % sum(len(v["levels"]) for v in doc["vectors"].values()))
+        print("  %-26s %-24s %8s  %-30s %s" % ("mutant", "reference", "vectors", "named killer", "first change"))
+        for m, changed, named in rows:
+            first = "%s %s (%s)" % changed[0] if changed else "-"
+            print("  %-26s %-24s %8d  %-30s %s" % (m.name, m.ref, len(changed), "%s %s %s" % (m.killer + ("ok" if named else "MISSED",)), first))
+        print("  %d of %d killed, %d surviving" % (len(rows) - len(survivors), len(rows), len(survivors)))
+    assert survivors == []
+
+
+def test_every_second_reading_mutant_changes_its_named_vector(capsys):
+    """the same mutants in the second reading, each run on the one vector the table names (it is slow Python)"""
+    doc = _vectors()
+    plain = mutants.second_reading()
+    rows, survivors = [], []
+    for m in mutants.MUTANTS:
+        name, level = m.killer
+        data = util.vector_input(name)
+        want = doc["vectors"][name]["levels"][level]
+        # the unmutated copy reproduces the vector, so what changes below is the mutant's doing
+        assert mutants.second_reading_record(plain, data, level) == want, (m.name, name, level)
+        got = mutants.second_reading_record(mutants.second_reading(m), data, level)
+        diff = [k for k in want if got[k] != want[k]]
+        rows.append((m, diff))
+        if not diff:
+            survivors.append(m.name)
+    with capsys.disabled():
+        print("\nzd_second_reading.py mutants against their named vectors")
+        for m, diff in rows:
+            print("  %-26s %-30s %s" % (m.name, "%s %s" % m.killer, ("killed: " + ", ".join(diff)) if diff else "SURVIVED"))
+        print("  %d of %d killed, %d surviving" % (len(rows) - len(survivors), len(rows), len(survivors)))
+    assert survivors == []
+
+
+def test_a_mutant_must_match_once():
+    with pytest.raises(AssertionError, match="occurs 0 times"):
+        mutants.patched("abc", "x", "y", "t")
+    with pytest.raises(AssertionError, match="occurs 2 times"):
+        mutants.patched("xx", "x", "y", "t")
+    assert mutants.patched("abc", "b", "B", "t") == "aBc"

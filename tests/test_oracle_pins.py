@@ -262,3 +262,30 @@ def test_the_second_reading_is_live_and_reproduces_its_vectors():
     assert [doc["vectors"]["trip%d" % i]["levels"]["default"]["blocks"] for i in range(5)] == ["fixed", "fixed", "fixed", "dynamic", "none"]
     assert Z2.adler_32_string(b"\xff" * 4200) == doc["adler32_whole"]["ff4200"]
     assert Z2.zlib_compress(b"hello world", "default")[1][:2].hex() == "789c"
+
+
+def test_the_tie_inputs_sit_on_their_ties(oracle):
+    """util.TIE_CASES are in deflate_vectors.json to pin the chooser's two `<=` (zd.ml:1102-1103) and Q3's 8 bits of
+    padding (zd.ml:1045-1047): each must still land exactly where it says, or the vectors pin nothing there."""
+    kinds = {0: "none", 1: "fixed", 2: "dynamic"}
+    doc = _vectors()
+    seen = set()
+    for name, (level, bi, what) in util.TIE_CASES.items():
+        assert level in doc["vectors"][name]["levels"], name
+        st, c, crc, blocks = oracle.deflate_trace(util.vector_input(name), level=oracle.LEVELS[level])
+        assert st == 0 and len(blocks) > bi, name
+        b = blocks[bi]
+        loss = b.nlen - 3 - (4 + b.src_len) * 8  # the stored estimate's padding: 8 - (pending + 3) % 8
+        got = (kinds[b.kind], b.nlen, b.flen, b.dlen, loss)
+        if what == "nf":
+            assert b.kind == 0 and b.nlen == b.flen <= b.dlen, (name, got)
+        elif what == "fd":
+            assert b.kind == 1 and b.flen == b.dlen < b.nlen, (name, got)
+        else:  # q3: the type bits end a byte, and a stored estimate without those 8 bits would win
+            assert b.kind == 1 and loss == 8 and b.flen < b.nlen <= b.flen + 8 and b.flen <= b.dlen, (name, got)
+        seen.add((what, bi == 0, loss if what == "nf" and bi else None))
+    # stored/fixed in block 1 and in a later block at every padding 1..8 (8: the type bits end a byte), fixed/dynamic in
+    # block 1 and in a later block (the code-length counts carried over, Q1), Q3 in block 2
+    want = {("nf", True, None), ("fd", True, None), ("fd", False, None), ("q3", False, None)}
+    want |= {("nf", False, k) for k in range(1, 9)}
+    assert seen >= want, want - seen

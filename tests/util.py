@@ -106,6 +106,62 @@ def record_table(n_records, seed=31):
     return bytes(out)
 
 
+def nibbles_then(seed, n_prefix, tail):
+    """`n_prefix` random nibbles (random.Random(seed)) then `tail`: at `Fast the nibbles fill block 1 (65534 source
+    bytes, dynamic) and leave the bit position block 2 starts at up to the seed; the tail's bytes (>= 16) never match
+    a nibble, so block 2 is the tail alone"""
+    r = random.Random(seed)
+    return bytes(r.randrange(16) for _ in range(n_prefix)) + tail
+
+
+def small_alphabet(seed):
+    """n = 8..63 symbols from range(k), k = 2..5 (random.Random(seed)): a one-block input, fixed against dynamic"""
+    r = random.Random(seed)
+    n, k = r.randrange(8, 64), r.randrange(2, 6)
+    return bytes(r.randrange(k) for _ in range(n))
+
+
+def skewed_tail(seed, n):
+    """n bytes from base .. base + k (base >= 16, mostly the lowest): a tail that codes well by a dynamic code"""
+    r = random.Random(seed)
+    k, base = r.randrange(2, 9), 16 + r.randrange(0, 200)
+    return bytes(base + min(int(r.expovariate(0.7)), k) for _ in range(n))
+
+
+# Inputs that sit exactly on a line of the block chooser (zd.ml:1094-1104) or next to the stored block's estimate
+# (Q3, zd.ml:1045-1047): name -> (level, block index, what the block's costs are).  "nf": nlen == flen and the block
+# is stored (the first `<=`); "fd": flen == dlen < nlen and the block is fixed (the second `<=`); "q3": fixed with
+# nlen - flen <= 8 and the block's type bits end a byte (alignment loss 8), so a stored estimate with 0 padding would
+# choose stored.  A block of n distinct 9-bit literals after a nibble prefix costs flen = 9n + 10 and
+# nlen = 8n + 35 + loss, loss = 8 - (pending + 3) % 8: n = 25 + loss ties them; the seeds pick the pending bit count.
+# tests/test_oracle_pins.py checks that every one still lands where it says.
+TIE_CASES = {
+    "tie_nf_b1": ("default", 0, "nf"),
+    "tie_fd_b1_s74": ("default", 0, "fd"),
+    "tie_fd_b1_s1062": ("default", 0, "fd"),
+    "q3_b2_s6": ("fast", 1, "q3"),
+    "tie_fd_b2": ("fast", 1, "fd"),
+}
+# loss -> prefix seed whose block 1 leaves that many bits of padding before block 2's stored body
+_NF_B2_SEEDS = {1: 5, 2: 3, 3: 9, 4: 19, 5: 0, 6: 1, 7: 31, 8: 6}
+for _loss in _NF_B2_SEEDS:
+    TIE_CASES["tie_nf_b2_loss%d" % _loss] = ("fast", 1, "nf")
+
+
+def tie_cases():
+    """name -> plaintext of TIE_CASES"""
+    c = {
+        "tie_nf_b1": bytes(range(144, 174)),                       # 30 distinct 9-bit literals: nlen = flen = 280
+        "tie_fd_b1_s74": small_alphabet(74),                       # (544, 244, 244)
+        "tie_fd_b1_s1062": small_alphabet(1062),                   # (160, 130, 130)
+        "q3_b2_s6": nibbles_then(6, 65534 - 6 % 7, bytes(range(150, 150 + 27 + 6 % 7))),  # block 2: (259, 253), loss 8
+        "tie_fd_b2": nibbles_then(0, 65534, skewed_tail(22, 93)),  # block 2: (784, 592, 592)
+    }
+    for loss, seed in _NF_B2_SEEDS.items():
+        c["tie_nf_b2_loss%d" % loss] = nibbles_then(seed, 65534, bytes(range(144, 144 + 25 + loss)))
+    return c
+
+
 _VECTOR_INPUTS = {}
 
 
@@ -183,6 +239,7 @@ def deflate_cases(small=False):
         })
         for m, raw in zip_docs_members():
             c[m["path"]] = zlib.decompress(raw, -15)
+        c.update(tie_cases())
     return c
 
 
