@@ -120,8 +120,8 @@ unsigned zipc_hip_last_inflate_blocks(zipc_hip_ctx *ctx);
 int zipc_hip_lds_exchange_ordered(zipc_hip_ctx *ctx);
 /* What the guards of that property have seen so far (round 6): positions whose links BOTH chain kernels made and were
  * compared -- the create-time probe runs lz_chain_xchg_kernel itself, whole and by segments, on a stream made of runs,
- * short periods and few-symbol alphabets; the context's first deflate batch has its first streams (ZIPC_HIP_CHAIN_CHECK,
- * default 32, at most 16 MiB) chained by both kernels under that batch's load -- and how many differed.  A difference in
+ * short periods and few-symbol alphabets; the context's first deflate batch has its first 32 streams (at most
+ * 16 MiB) chained by both kernels under that batch's load -- and how many differed.  A difference in
  * the first batch fails that batch's streams with ZIPC_HIP_ERR_HIP and moves the context to the ordering kernel.
  * Synchronises the context's stream. */
 int zipc_hip_chain_check(zipc_hip_ctx *ctx, unsigned long long *compared, unsigned long long *differences);
@@ -289,8 +289,7 @@ int zipc_hip_deflate_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_d
                            int crc_op);
 
 /* CRC-32 and Adler-32 of one device buffer (Crc_32.string + Adler_32.string).  Both asked for: ONE pass over the bytes
- * leaves the CRC-32 partials and the Adler-32 chunk sums (len bytes of traffic; ZIPC_HIP_CHECKSUM_FUSED=0 keeps the two
- * passes of rounds 1-2), then the two short finishes.  d_out receives {crc32, adler32}.  Either selector may be 0 to
+ * leaves the CRC-32 partials and the Adler-32 chunk sums (len bytes of traffic), then the two short finishes.  d_out receives {crc32, adler32}.  Either selector may be 0 to
  * skip that checksum. */
 int zipc_hip_checksum_device(zipc_hip_ctx *ctx, const void *d_buf, size_t len,
                              int want_crc32, int want_adler32, uint32_t *d_out);

@@ -1,6 +1,6 @@
 #!/bin/bash
-# A variant of libzipc_hip.so whose DEVICE code went through a rewrite of its assembly (an experiment's tool, like
-# build_variant.sh; the product is never built this way):
+# A variant of libzipc_hip.so whose DEVICE code went through a rewrite of its assembly (an experiment's tool; the
+# product is never built this way):
 #   tools/build_asm_variant.sh NAME 'sed-script' [source ...]     -> zipc_amd/lib/libzipc_hip_NAME.so
 # e.g. the selects that read VCC in the VOP2 encoding as VOP3 (profiles/r06_vcc_select.txt):
 #   tools/build_asm_variant.sh e64 's/v_cndmask_b32_e32 \(.*\), vcc$/v_cndmask_b32_e64 \1, vcc/'

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""C3 (both checksums of one buffer): wall ms per call and the kernels' own times, for the build and
-environment the process was started with (ZIPC_HIP_CHECKSUM_FUSED=0: the two passes).  N bytes (default 4 GiB)."""
+"""C3 (both checksums of one buffer): wall ms per call and the kernels' own times, for the build the process was
+started with.  N bytes (default 4 GiB)."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, zipc_amd
@@ -25,5 +25,5 @@ k = {name: round(v[1] / v[0], 3) for name, v in ctx.kernel_times().items()}
 ctx.set_profiling(False)
 again = batch.checksum_device(ctx, buf)
 ms = sorted(ts)[len(ts) // 2]
-print(json.dumps({"n": n, "fused": os.environ.get("ZIPC_HIP_CHECKSUM_FUSED", "1"), "crc": hex(first[0]), "adler": hex(first[1]),
+print(json.dumps({"n": n, "crc": hex(first[0]), "adler": hex(first[1]),
                   "same": first == again, "ms": round(ms, 3), "best_ms": round(min(ts), 3), "gib_s": round(n / 2**30 / ms * 1e3, 1), "kernels_ms": k}))

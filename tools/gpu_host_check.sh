@@ -17,7 +17,7 @@ for n in ${NS:-4096 16384}; do
     echo "n=$n new $(N_STREAMS=$n REPS=$R python3 tools/bench_host_forms.py 2>/dev/null | row)" | tee -a $O
     echo "n=$n new, ZIPC_HIP_HOST_PACK=0 $(ZIPC_HIP_HOST_PACK=0 N_STREAMS=$n REPS=$R python3 tools/bench_host_forms.py 2>/dev/null | row)" | tee -a $O
   done
-  for sw in ${SWITCHES:-ZIPC_HIP_HOST_PACK_WGS=4 ZIPC_HIP_HOST_PACK_WGS=8 ZIPC_HIP_HOST_PACK_WGS=64 ZIPC_HIP_HOST_CHUNKS=3 ZIPC_HIP_HOST_CHUNKS=4 ZIPC_HIP_HOST_CHUNKS=5 ZIPC_HIP_HOST_CHUNKS=6 ZIPC_HIP_HOST_THREADS=4 ZIPC_HIP_HOST_THREADS=16 ZIPC_HIP_HOST_H2D_MIB=0 ZIPC_HIP_HOST_H2D_MIB=4 ZIPC_HIP_HOST_H2D_MIB=64}; do
+  for sw in ${SWITCHES:-ZIPC_HIP_HOST_CHUNKS=3 ZIPC_HIP_HOST_CHUNKS=4 ZIPC_HIP_HOST_CHUNKS=5 ZIPC_HIP_HOST_CHUNKS=6 ZIPC_HIP_HOST_THREADS=4 ZIPC_HIP_HOST_THREADS=16}; do
     echo "n=$n $sw $(env $sw N_STREAMS=$n REPS=$R python3 tools/bench_host_forms.py 2>/dev/null | row)" | tee -a $O
   done
   ZIPC_HIP_HOST_TIMING=1 N_STREAMS=$n REPS=1 python3 tools/bench_host_forms.py 2>&1 >/dev/null | grep -A6 "zipc_hip" | tail -14 | tee -a $O

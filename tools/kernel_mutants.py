@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "zipc_amd", "csrc")
 OUT = os.path.join(ROOT, "zipc_amd", "lib", "mutants")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-# zipc_amd/csrc/Makefile's flags (tools/build_variant.sh builds a variant the same way)
+# zipc_amd/csrc/Makefile's flags
 HIPFLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function"]
 
 # (name, file under zipc_amd/csrc, text, replacement)

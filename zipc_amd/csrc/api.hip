@@ -209,7 +209,6 @@ const Tuning &tuning() {
     auto is = [](const char *name, const char *v) { const char *e = getenv(name); return e && !strcmp(e, v); };
     Tuning x;
     x.chain_peel = is("ZIPC_HIP_CHAIN", "peel");
-    x.chain_check = num("ZIPC_HIP_CHAIN_CHECK", 32);
     x.parse_segments = num("ZIPC_HIP_PARSE_SEGMENTS", -1);
     x.parse_seg = num("ZIPC_HIP_PARSE_SEG", 0);
     x.match_tiles_per_group = num("ZIPC_HIP_MATCH_TILES_PER_GROUP", 0);
@@ -225,15 +224,11 @@ const Tuning &tuning() {
     if (x.explore_stride < 1024) x.explore_stride = 1024;  // (a divisor: never 0 or negative, whatever the environment says)
     x.resolve_hops0 = (int)num("ZIPC_HIP_RESOLVE_HOPS0", 256);
     x.resolve_hops1 = (int)num("ZIPC_HIP_RESOLVE_HOPS1", 256);
-    x.checksum_fused = num("ZIPC_HIP_CHECKSUM_FUSED", 1) != 0;
     x.host_threads = num("ZIPC_HIP_HOST_THREADS", 0);
     x.host_chunks = num("ZIPC_HIP_HOST_CHUNKS", 0);
     x.host_chunk_min = num("ZIPC_HIP_HOST_CHUNK_MIN", 1024);
     if (x.host_chunk_min < 1) x.host_chunk_min = 1;
     x.host_pack = num("ZIPC_HIP_HOST_PACK", 1) != 0;
-    x.host_pack_wgs = num("ZIPC_HIP_HOST_PACK_WGS", 6);
-    if (x.host_pack_wgs < 1) x.host_pack_wgs = 1;
-    x.host_h2d_mib = num("ZIPC_HIP_HOST_H2D_MIB", 16);
     x.host_timing = num("ZIPC_HIP_HOST_TIMING", 0) != 0;
     return x;
   }();
@@ -1038,27 +1033,19 @@ int zipc_hip_checksum_device(zipc_hip_ctx *ctx, const void *d_buf, size_t len, i
   if (!ctx || !d_out || (!d_buf && len)) return ZIPC_HIP_ERR_INVALID_ARG;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // Both checksums: ONE pass over the bytes (crc32_adler_segments_kernel leaves the CRC partials and the
-  // Adler chunk sums), then the two finishes -- on two queues for a large buffer.  ZIPC_HIP_CHECKSUM_FUSED=0
-  // keeps the two passes of rounds 1-3 (CRC on a side queue from 64 MiB on) for comparison and for the tests.
-  const bool fused_ok = zd::tuning().checksum_fused;
-  const bool c3_two_queues = true;
-  const bool fused = want_crc32 && want_adler32 && len > 0 && fused_ok;
-  const bool side = want_crc32 && want_adler32 && len >= (64u << 20) && c3_two_queues;
-  if (side || fused)  // (before any fork: growing a buffer synchronises)
+  // Adler chunk sums), then the two finishes -- on two queues for a large buffer
+  const bool fused = want_crc32 && want_adler32 && len > 0;
+  const bool side = fused && len >= (64u << 20);
+  if (fused)  // (before any fork: growing a buffer synchronises)
     HIP_TRY(ctx, ctx->ensure(ctx->crc_partials, crc32_segs(len) * sizeof(uint32_t)));
-  if (side && !fused) {
-    HIP_TRY(ctx, ctx->fork(1));
-    ctx->cur = ctx->side[0];
-  }
   if (want_crc32 && !fused) {
-    int st = crc32_pass(ctx, (const uint8_t *)d_buf, RANGE_SINGLE, nullptr, nullptr, 1, 0, len, len, d_out);
-    if (side) ctx->cur = ctx->stream;
-    if (st != ZIPC_HIP_OK) { if (side) (void)ctx->join(1); return st; }
+    const int st = crc32_pass(ctx, (const uint8_t *)d_buf, RANGE_SINGLE, nullptr, nullptr, 1, 0, len, len, d_out);
+    if (st != ZIPC_HIP_OK) return st;
   }
   struct Joiner {  // the side queue is joined on every way out of the Adler half
     zipc_hip_ctx *c; bool on;
     ~Joiner() { if (on) { c->cur = c->stream; (void)c->join(1); } }
-  } joiner{ctx, side && !fused};
+  } joiner{ctx, false};
   if (want_adler32) {
     const uint64_t n_chunks = len ? len / ADLER_CHUNK + 1 : 0;
     // chunk sums, then the ambiguous-chunk list and the per-run arrays of the chain kernels
@@ -1247,6 +1234,7 @@ __global__ __launch_bounds__(1024) void pack_offsets_kernel(const StreamDesc *de
 // Workgroup w of G moves the w-th part of the packed bytes (parts of whole 4 KiB): the stream its part begins in is
 // found by bisection of off[], the next ones follow; every thread moves 16 bytes at a time, four loads in flight (slots
 // begin on 256-byte boundaries).
+constexpr unsigned PACK_COPY_WGS = 6;
 __global__ __launch_bounds__(256) void pack_copy_kernel(const uint8_t *dst_arena, uint8_t *pack_arena, const StreamDesc *descs,
                                                         const uint64_t *off, uint32_t n, uint64_t base) {
   const uint64_t total_end = off[n];
@@ -1443,7 +1431,7 @@ static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void
       }
       PIPE_TRY(hipStreamWaitEvent(ctx->copy_out, ev_k.ev[g], 0));
       if (packed) {  // its stores ARE the copy back, of as many bytes as the device knows it made, beside the next sub-batch's kernels
-        hipLaunchKernelGGL(pack_copy_kernel, dim3((unsigned)zd::tuning().host_pack_wgs), dim3(256), 0, ctx->copy_out,
+        hipLaunchKernelGGL(pack_copy_kernel, dim3(PACK_COPY_WGS), dim3(256), 0, ctx->copy_out,
                            (const uint8_t *)ctx->io_dst.p, (uint8_t *)ctx->pin_dst.p, (const StreamDesc *)dd,
                            (const uint64_t *)off, (uint32_t)(hi - lo), c);
         PIPE_TRY(hipGetLastError());
@@ -1467,7 +1455,7 @@ static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void
   job.descs = descs.data(); job.src_arena_end = so; job.dst_arena_end = dof;
   job.cut = cut; job.n_max = n_max; job.packed = packed; job.want_bytes = want_bytes;
   job.ahead = is_inflate && max_cap >= BLOCKS_BATCH_MIN_DST;
-  job.h2d_bytes = zd::tuning().host_h2d_mib > 0 ? (uint64_t)zd::tuning().host_h2d_mib << 20 : 0;
+  job.h2d_bytes = (uint64_t)16 << 20;  // (sources sent in runs of about 16 MiB as they are gathered)
   job.pin_src = (uint8_t *)ctx->pin_src.p; job.pin_dst = want_bytes ? (const uint8_t *)ctx->pin_dst.p : nullptr;
   job.pin_res = (const zipc_hip_stream_result *)ctx->pin_res.p;
   job.threads = host_threads();

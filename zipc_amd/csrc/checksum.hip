@@ -163,9 +163,6 @@ __device__ __forceinline__ void crc32_segment(
       s2 += 16u * s1 + u2;
       s1 += u1;
     }
-#ifdef ZD_CRC_FAKE  // timing only (wrong checksums): what the pass costs without the table walk
-    c ^= w.x ^ w.y ^ w.z ^ w.w;
-#else
     uint32_t u = c ^ w.x;
     c = T[3][u & 0xFF] ^ T[2][(u >> 8) & 0xFF] ^ T[1][(u >> 16) & 0xFF] ^ T[0][u >> 24];
     u = c ^ w.y;
@@ -174,7 +171,6 @@ __device__ __forceinline__ void crc32_segment(
     c = T[3][u & 0xFF] ^ T[2][(u >> 8) & 0xFF] ^ T[1][(u >> 16) & 0xFF] ^ T[0][u >> 24];
     u = c ^ w.w;
     c = T[3][u & 0xFF] ^ T[2][(u >> 8) & 0xFF] ^ T[1][(u >> 16) & 0xFF] ^ T[0][u >> 24];
-#endif
   }
   // merge the 256 equal-length pieces: tree over lanes, then over waves.  The
   // multipliers are constants: nibble-table products (the bit-serial gf2_mul here was

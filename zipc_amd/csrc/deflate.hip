@@ -377,17 +377,8 @@ static_assert(MAX_STREAM_LEN <= XCHG_NONE, "no position looks like the table's e
 // turns of 8 / 32 rounds 1.83 / 1.41; polling without s_sleep 1.63; the hand-over NOT waiting for the exchanges' answers
 // 1.42 -- neither the hand-over nor a wave's own work is what a stream waits for: 1024 exchanges of 64 random addresses
 // take the LDS ~45 clocks each (text, where lanes of one exchange share addresses: 1.59).  One wave alone: 3.4.
-#ifndef ZD_XCHG_WAVES
-#define ZD_XCHG_WAVES 4
-#endif
-#ifndef ZD_XCHG_U
-#define ZD_XCHG_U 16
-#endif
-#ifndef ZD_XCHG_SLEEP
-#define ZD_XCHG_SLEEP 1
-#endif
-constexpr uint32_t XCHG_WAVES = ZD_XCHG_WAVES;
-constexpr int XCHG_U = ZD_XCHG_U;             // rounds of 64 positions per turn
+constexpr uint32_t XCHG_WAVES = 4;
+constexpr int XCHG_U = 16;             // rounds of 64 positions per turn
 constexpr uint32_t XCHG_TURN = 64u * XCHG_U;  // positions per turn
 static_assert(MAX_MATCH_DIST % XCHG_TURN == 0 && SWEEP_PERIOD % XCHG_TURN == 0, "segments start on turn boundaries");
 
@@ -432,11 +423,7 @@ __device__ __forceinline__ void lz_chain_xchg_workgroup(const uint8_t *__restric
     uint32_t old[XCHG_U], hb[XCHG_U];
 #pragma unroll
     for (int u = 0; u < XCHG_U; u++) hb[u] = hash4(wd[u]);
-    while (__hip_atomic_load(&turn_now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != t) {
-#if ZD_XCHG_SLEEP
-      __builtin_amdgcn_s_sleep(ZD_XCHG_SLEEP);
-#endif
-    }
+    while (__hip_atomic_load(&turn_now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != t) __builtin_amdgcn_s_sleep(1);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #pragma unroll
     for (int u = 0; u < XCHG_U; u++) {
@@ -691,30 +678,19 @@ constexpr uint32_t MATCHW_TILE = 16384;
 constexpr int MATCHW_NP = 2;  // run slots per lane.  3 and 4 measured on C2 with the shared cursor: +3 % and +7.5 % (and
                                // +3 % / +8 % on 1 MiB streams of 3-bit symbols); 3 again under the tile-wide pool: +9 % on C2,
                                // +6 % on real text: the loop is nearer its vector bound than latency-bound
-#ifndef ZD_SCAN_NP
-#define ZD_SCAN_NP 2
-#endif
-constexpr int MATCHW_SCAN_NP = ZD_SCAN_NP;  // run slots per lane of the second form of the walk
+constexpr int MATCHW_SCAN_NP = 2;  // run slots per lane of the second form of the walk
 constexpr uint32_t MATCHW_LINKS = MAX_MATCH_DIST + MATCHW_TILE;           // u16 each
 constexpr uint32_t MATCHW_SRC_BYTES = MAX_MATCH_DIST + MATCHW_TILE + 272;  // + MAX_MATCH_LEN + an 8-byte read, 16-aligned
-#ifndef ZD_SCAN_STEPS
-#define ZD_SCAN_STEPS 4
-#endif
 // run-slot steps per position (iterations x lanes x slots / positions) from which the second form of the walk
 // pays: 4-bit symbols take 2.7 of the first form's (1.56 chain steps at 0.58 lane use), 3-bit symbols ~12, text ~48
-constexpr uint32_t MATCHW_SCAN_STEPS = ZD_SCAN_STEPS;
-#ifndef ZD_PROBE_DEEP
-#define ZD_PROBE_DEEP 192
-#endif
+constexpr uint32_t MATCHW_SCAN_STEPS = 4;
 // of the 1024 chains a workgroup probes in its first tile, those that hold three candidates: above this many the tile takes the
 // second form.  Round 5's second form costs a third less than round 4's, and the rule moved with it (it was 512, and 6 steps
 // a position): the benchmark's symbols probe 143 +- 11 deep and keep the first form (1.57 ms per 4096 streams against 1.75 in the
 // second); the corpus' binaries -- a few long chains among many empty ones -- now take the second: 9.1 -> 3.6 ms per 64 MiB of
-// such chunks, the corpus' lz_match 17.1 -> 12.6 ms per 256 MiB (tools/sweep_form_rule.sh)
-constexpr uint32_t MATCHW_PROBE_DEEP = ZD_PROBE_DEEP;
-#ifndef ZD_MATCH_GROUPS_PER_WG
-#define ZD_MATCH_GROUPS_PER_WG 8
-#endif
+// such chunks, the corpus' lz_match 17.1 -> 12.6 ms per 256 MiB
+constexpr uint32_t MATCHW_PROBE_DEEP = 192;
+constexpr size_t MATCHW_GROUPS_PER_WG = 8;  // groups a workgroup takes one behind the other, at most (launch_deflate_group)
 constexpr size_t MATCHW_SMALL = 8192;  // streams up to this long keep the global-memory kernel
 static_assert(MATCHW_TILE % MATCHW_THREADS == 0 && MATCHW_SRC_BYTES % 16 == 0, "tile shape");
 static_assert(MATCHW_SRC_BYTES + 2 * MATCHW_LINKS <= 160 * 1024, "LDS of one CU");
@@ -1028,11 +1004,10 @@ __device__ __forceinline__ void parse_tile_macro(int lane, uint32_t p, unsigned 
                                                uint32_t len, uint64_t m_cur, uint64_t m_nxt,
                                                const uint32_t *__restrict__ match, const uint32_t *__restrict__ snap, int good_match, uint32_t &br,
                                                uint32_t &adv, uint32_t &lits) {
-#ifndef ZD_PARSE_CHAIN_INTS
   // The lanes whose lazy chain goes on are a LANE MASK (round 6).  Rounds 3-5 kept the flag as an integer in a vector
   // register -- a select to make it, a compare to read it back, twice a turn -- because the kernel was thought to wait for
   // scalar issue; it waits for vector issue, and a mask's and / or are scalar instructions.
-  // A turn: 29 -> 20 vector instructions (-DZD_PARSE_CHAIN_INTS keeps the old form for A/B runs).
+  // A turn: 29 -> 20 vector instructions (the integer form: `git show 4d5ffca:zipc_amd/csrc/deflate.hip`).
   // Round 6, second pass over the loop's assembly (22 -> 13 vector instructions a turn):
   //  * a chaining lane's j is p + the turn: every lane of chain_m has taken every turn so far (a lane that does not take one
   //    leaves the mask for good), so j is not a register -- and "j <= max_pos" follows from "pl < maxlen" (a pending length is
@@ -1099,66 +1074,6 @@ __device__ __forceinline__ void parse_tile_macro(int lane, uint32_t p, unsigned 
   lits = n_lits;
   const uint32_t step = n_lits + (pend & 0x1FF);
   adv = mine(valid_m) ? (step ? step : 1u) : 0u;
-#else
-  // (flags as integers and selects instead of branches: a loop-carried bool lives in a scalar mask that
-  // costs three scalar instructions per update, and the CU's ONE scalar issue per clock is what this
-  // kernel's 32 waves per CU queue for)
-  const bool valid = __builtin_amdgcn_inverse_ballot_w64(valid_m);
-  uint32_t pend = (valid && has_match && p <= max_pos) ? (uint32_t)m_cur : 0u;
-  uint32_t chaining = (pend & 0x1FF) != 0 ? 1u : 0u;
-  uint32_t n_lits = 0, j = p + 1;
-  const uint32_t cur_lo = (uint32_t)m_cur, cur_hi = (uint32_t)(m_cur >> 32);
-  const uint32_t nxt_lo = (uint32_t)m_nxt, nxt_hi = (uint32_t)(m_nxt >> 32);
-  // one step of a lane's lazy chain with the entry mj of position j
-  auto chain_step = [&](uint32_t mj_lo, uint32_t mj_hi, uint32_t use_hi) {
-    const uint32_t pl = pend & 0x1FF;
-    const uint32_t rem = len - j;  // (j > max_pos: the value is not used)
-    const uint32_t maxlen = rem < (uint32_t)MAX_MATCH_LEN ? rem : (uint32_t)MAX_MATCH_LEN;
-    const uint32_t c = use_hi ? mj_hi : mj_lo;
-    const uint32_t take = (chaining != 0 && j <= max_pos && pl < maxlen && (c & 0x1FF) > pl) ? 1u : 0u;
-    n_lits += take;
-    pend = take ? c : pend;
-    j += take;
-    chaining = take;
-  };
-  // chains within the staged tiles (all but pathological ones).  Every chaining lane looks at the same distance ahead,
-  // lane + ahead (< 128), so the two tiles' best-of-K words are SHIFTED down a lane per turn (v_mov_b32_dpp wave_shl:1:
-  // lane i takes lane i + 1's, lane 63 the next tile's lane 0 -- tools/probes/dpp_wave_shl.hip) where round 3 fetched
-  // them by two ds_bpermute a turn: no LDS operation and no address -- and no measurable difference (C2 lz_parse 2.90-2.93
-  // against 2.86-2.97 ms beside the other slice's kernels): the shuffles' round trips are not what a tile waits for.
-  uint32_t sh_cur = cur_lo, sh_nxt = nxt_lo;  // after k turns: the words of positions p + k (this tile's lanes), p + 64 + k
-  ZD_PCOUNT(0, 1); ZD_PCOUNT(2, __builtin_amdgcn_ballot_w64(chaining != 0) ? 1 : 0);
-  for (uint32_t ahead = 1; ahead < 128u - 63u && __builtin_amdgcn_ballot_w64(chaining != 0); ahead++) {
-    ZD_PCOUNT(1, 1); ZD_PCOUNT(3, __builtin_popcountll(__builtin_amdgcn_ballot_w64(chaining != 0)));
-    const uint32_t off = (uint32_t)lane + ahead;
-    const uint32_t addr = (off & 63u) * 4u;
-    const bool in_cur = off < 64u;
-    // best-of-K of position j; best-of-K/4 only if a pending match is that long
-    {
-      const uint32_t n0 = (uint32_t)__builtin_amdgcn_readlane((int)sh_nxt, 0);
-      sh_cur = (uint32_t)__builtin_amdgcn_update_dpp((int)n0, (int)sh_cur, 0x130, 0xf, 0xf, false);
-      sh_nxt = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sh_nxt, 0x130, 0xf, 0xf, false);
-    }
-    const uint32_t mj_lo = sh_cur;
-    uint32_t mj_hi = 0;
-    const uint32_t want_hi = (chaining != 0 && (pend & 0x1FF) >= (uint32_t)good_match) ? 1u : 0u;
-    if (__builtin_amdgcn_ballot_w64(want_hi != 0)) {
-      const uint32_t a_hi = lane_value(addr, cur_hi), b_hi = lane_value(addr, nxt_hi);
-      mj_hi = in_cur ? a_hi : b_hi;
-    }
-    chain_step(mj_lo, mj_hi, want_hi);
-  }
-  // a chain of 64 strictly growing matches and more: straight from the table
-  // (kept out of the loop above: its load would make that loop wait for memory)
-  if (__builtin_amdgcn_ballot_w64(chaining != 0)) {
-    while (chaining) {
-      const uint64_t mj = j <= max_pos ? match_pair(match, snap, j) : 0ull;
-      chain_step((uint32_t)mj, (uint32_t)(mj >> 32), (pend & 0x1FF) >= (uint32_t)good_match ? 1u : 0u);
-    }
-  }
-  br = 0; lits = 0; adv = valid ? 1u : 0u;
-  if ((pend & 0x1FF) != 0) { br = pend; lits = n_lits; adv = n_lits + (pend & 0x1FF); }
-#endif
 }
 
 // Streams parsed by several waves (lz_parse_spec_kernel / lz_parse_stitch_kernel / lz_parse_gather_kernel below):
@@ -2889,6 +2804,28 @@ size_t debug_chain_positions(size_t n, size_t total_src_len) {
   return (size_t)P;
 }
 
+// The parse-segment scratch (ctx->parse_scratch): the block plans, then the ParseSegs arrays, each on a 256-byte boundary.
+// Carves them from base and returns the end: from 0, that is the size to allocate -- ONE layout for the size and the pointers.
+static uintptr_t carve_parse_scratch(uintptr_t base, size_t n_plans, size_t n_slots, size_t tiles, size_t seg_syms,
+                                     EmitPlan *&plans, ParseSegs &g) {
+  uintptr_t q = base;
+  auto take = [&q](auto *&p, size_t bytes) {
+    p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(q);
+    q += align_up(bytes, 256);
+  };
+  take(plans, n_plans * sizeof(EmitPlan));
+  take(g.spec_syms, n_slots * seg_syms * 4);
+  take(g.vis, tiles * 8);
+  take(g.tile_sym0, tiles * 4);
+  for (uint32_t **a : {&g.seg_exit, &g.seg_total, &g.seg_dst, &g.seg_from, &g.seg_n, &g.meet_f, &g.meet_from, &g.meet_exit,
+                       &g.meet_end, &g.fix_dst, &g.fix_n})
+    take(*a, n_slots * 4);
+  take(g.vis2, tiles * 8);
+  take(g.sym02, tiles * 4);
+  take(g.meet_syms, n_slots * MEET_CAP * 4);
+  return q;
+}
+
 // ---------------------------------------------------------------------------------
 static hipError_t launch_deflate_group(zipc_hip_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst,
                                        const StreamDesc *d_descs, StreamResult *d_results, size_t n,
@@ -2973,45 +2910,22 @@ static hipError_t launch_deflate_group(zipc_hip_ctx *ctx, const uint8_t *d_src, 
   EmitPlan *plans = nullptr;
   if (segmented) {
     const size_t n_slots = (size_t)(S.cap_positions / segp) + n + 1, tiles = (size_t)(S.cap_positions / 64) + 4;  // (ParseSegs::slot)
-    const size_t plan_bytes = align_up((size_t)S.cap_blocks * sizeof(EmitPlan), 256);
     const size_t seg_syms = segp + PARSE_SEG_SLACK;
-    const size_t bytes = plan_bytes + align_up(n_slots * seg_syms * 4, 256) + 2 * align_up(tiles * 8, 256) +
-                         2 * align_up(tiles * 4, 256) + 11 * align_up(n_slots * 4, 256) + align_up(n_slots * MEET_CAP * 4, 256);
-    if (ctx->ensure(ctx->parse_scratch, bytes) != hipSuccess) {
+    if (ctx->ensure(ctx->parse_scratch, carve_parse_scratch(0, S.cap_blocks, n_slots, tiles, seg_syms, plans, segs)) != hipSuccess) {
       // (8192 members of 1 MiB ask for 39 GB of segment symbols here: where the device cannot give them, the forms by a wave per
       // stream -- which need none -- take the call, as they did for this shape until round 6; only a call that ASKED for segments fails)
       (void)hipGetLastError();
       if (segs_env == 1) return hipErrorOutOfMemory;
       segmented = false;
+      plans = nullptr;
+      segs = ParseSegs{};
+    } else {
+      carve_parse_scratch((uintptr_t)ctx->parse_scratch.p, S.cap_blocks, n_slots, tiles, seg_syms, plans, segs);
+      segs.segs_per_stream = (uint32_t)sps;
+      segs.seg_positions = (uint32_t)segp; segs.seg_syms = (uint32_t)seg_syms;
+      const hipError_t me = hipMemsetAsync(segs.vis, 0, tiles * 8, ctx->cur);
+      if (me != hipSuccess) return me;
     }
-  }
-  if (segmented) {
-    const size_t n_slots = (size_t)(S.cap_positions / segp) + n + 1, tiles = (size_t)(S.cap_positions / 64) + 4;
-    const size_t plan_bytes = align_up((size_t)S.cap_blocks * sizeof(EmitPlan), 256);
-    const size_t seg_syms = segp + PARSE_SEG_SLACK;
-    uint8_t *q = (uint8_t *)ctx->parse_scratch.p;
-    plans = (EmitPlan *)q; q += plan_bytes;
-    segs.spec_syms = (uint32_t *)q; q += align_up(n_slots * seg_syms * 4, 256);
-    segs.vis = (unsigned long long *)q; q += align_up(tiles * 8, 256);
-    segs.tile_sym0 = (uint32_t *)q; q += align_up(tiles * 4, 256);
-    segs.seg_exit = (uint32_t *)q; q += align_up(n_slots * 4, 256);
-    segs.seg_total = (uint32_t *)q; q += align_up(n_slots * 4, 256);
-    segs.seg_dst = (uint32_t *)q; q += align_up(n_slots * 4, 256);
-    segs.seg_from = (uint32_t *)q; q += align_up(n_slots * 4, 256);
-    segs.seg_n = (uint32_t *)q; q += align_up(n_slots * 4, 256);
-    segs.meet_f = (uint32_t *)q; q += align_up(n_slots * 4, 256);
-    segs.meet_from = (uint32_t *)q; q += align_up(n_slots * 4, 256);
-    segs.meet_exit = (uint32_t *)q; q += align_up(n_slots * 4, 256);
-    segs.meet_end = (uint32_t *)q; q += align_up(n_slots * 4, 256);
-    segs.fix_dst = (uint32_t *)q; q += align_up(n_slots * 4, 256);
-    segs.fix_n = (uint32_t *)q; q += align_up(n_slots * 4, 256);
-    segs.vis2 = (unsigned long long *)q; q += align_up(tiles * 8, 256);
-    segs.sym02 = (uint32_t *)q; q += align_up(tiles * 4, 256);
-    segs.meet_syms = (uint32_t *)q;
-    segs.segs_per_stream = (uint32_t)sps;
-    segs.seg_positions = (uint32_t)segp; segs.seg_syms = (uint32_t)seg_syms;
-    const hipError_t me = hipMemsetAsync(segs.vis, 0, tiles * 8, ctx->cur);
-    if (me != hipSuccess) return me;
   }
   // lz_chain: by ordered exchange where the context's probe passed (ZIPC_HIP_CHAIN=peel keeps the peel kernel: tests, A/B).
   // A wave per stream leaves most of the chip idle while there are fewer streams than CUs: a long stream is then cut into
@@ -3024,11 +2938,11 @@ static hipError_t launch_deflate_group(zipc_hip_ctx *ctx, const uint8_t *d_src, 
                       "that batch's streams reported ZIPC_HIP_ERR_HIP, the context now orders equal hashes itself";
   }
   const bool xchg_chain = ctx->xchg_ordered && !tuning().chain_peel;
-  // ZIPC_HIP_CHAIN_CHECK=N (default 32; 0: never): the first N streams of the context's FIRST batch -- as many of them as hold
-  // 16 MiB of source -- are chained by both kernels and compared (chain_check_enqueue)
+  // The first 32 streams of the context's FIRST batch -- as many of them as hold 16 MiB of source -- are chained by both
+  // kernels and compared (chain_check_enqueue)
   size_t check_k = 0;
-  if (xchg_chain && !ctx->chain_checked && tuning().chain_check > 0 && ctx->chain_check_host) {
-    check_k = (size_t)tuning().chain_check < n ? (size_t)tuning().chain_check : n;
+  if (xchg_chain && !ctx->chain_checked && ctx->chain_check_host) {
+    check_k = n < 32 ? n : 32;
     const size_t fit = max_src_len ? ((size_t)16 << 20) / max_src_len : check_k;
     check_k = check_k > fit ? (fit ? fit : 1) : check_k;
     ctx->chain_checked = true;
@@ -3067,7 +2981,7 @@ static hipError_t launch_deflate_group(zipc_hip_ctx *ctx, const uint8_t *d_src, 
       // groups a workgroup takes one behind the other: as many as leave 2048 workgroups and more, 8 at most (measured 1 / 2 / 4 / 8:
       // the benchmark's streams 4.70 / 4.60 / 4.50 / 4.50 ms, text 48.6 / 47.0 / 45.7 / 46.2, 1 MiB members of 3-bit symbols 31.9 / 32.2 / 32.7 / 30.6)
       size_t gpw = m * gps / 2048;
-      gpw = gpw < 1 ? 1 : gpw > (size_t)ZD_MATCH_GROUPS_PER_WG ? (size_t)ZD_MATCH_GROUPS_PER_WG : gpw;
+      gpw = gpw < 1 ? 1 : gpw > MATCHW_GROUPS_PER_WG ? MATCHW_GROUPS_PER_WG : gpw;
       // (... of groups that are short: a launch ends when its last workgroup does, and at `Best a group of text takes milliseconds --
       // 2048 streams: 8 workgroups of two groups a CU 76.8 ms, 16 of one 66.5.  Taking the groups from a counter instead of by
       // position in the grid evened that out -- 66.0 -- and cost 1 MiB members 13 % and the benchmark's streams 2-10 %; three

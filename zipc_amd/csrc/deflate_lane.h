@@ -61,10 +61,7 @@ ZD_HD uint32_t common_prefix_t(S s, uint32_t q, uint32_t p, uint32_t maxlen, uin
   uint32_t i = from;
   // (the first 16 bytes as they come: on text most compares end there, and three aligned reads and two funnel shifts
   // per 8 bytes cost it more than the odd stall -- lz_match 95.5 -> 101.3 ms with words from the first byte on)
-#ifndef ZD_PREFIX_PLAIN
-#define ZD_PREFIX_PLAIN 2
-#endif
-  for (int k = 0; k < ZD_PREFIX_PLAIN && i + 8 <= maxlen; k++) {
+  for (int k = 0; k < 2 && i + 8 <= maxlen; k++) {
     const uint64_t x = load_u64_le(s + q + i) ^ load_u64_le(s + p + i);
     if (x) return i + (uint32_t)(__builtin_ctzll(x) >> 3);
     i += 8;
@@ -466,26 +463,12 @@ ZD_HD uint64_t scan_run_result(const ScanRun &r, uint32_t Kq) {
   const uint32_t snap = Kq == 0 ? 0u : (r.snap != SNAP_NONE ? r.snap : r.best);
   return (uint64_t)r.best | ((uint64_t)snap << 32);
 }
-#ifndef ZD_SCAN_ROUNDS
-#define ZD_SCAN_ROUNDS 8
-#endif
-#ifndef ZD_SCAN_ROUNDS_DENSE
-#define ZD_SCAN_ROUNDS_DENSE 4
-#endif
-#ifndef ZD_SCAN_DENSE_HITS
-#define ZD_SCAN_DENSE_HITS 32
-#endif
-#ifndef ZD_SCAN_MIN_WALKERS
-#define ZD_SCAN_MIN_WALKERS 16
-#endif
-#ifndef ZD_SCAN_HANDOUT
-#define ZD_SCAN_HANDOUT 24
-#endif
-constexpr int SCAN_ROUNDS = ZD_SCAN_ROUNDS;  // cheap steps between two compares, at most ...
-constexpr uint32_t SCAN_DENSE_HITS = ZD_SCAN_DENSE_HITS;  // ... ZD_SCAN_ROUNDS_DENSE when the compare before had this many runs in it (of 128): measured,
-                                                          // text (20 a compare) is 6 % faster with 8 rounds than with 4, 3-bit symbols (56) 5 % slower
-constexpr int SCAN_MIN_WALKERS = ZD_SCAN_MIN_WALKERS;  // ... and only while this many lanes of the wave still walk
-constexpr uint32_t SCAN_HANDOUT = ZD_SCAN_HANDOUT;  // finished positions wait for this many lanes with one
+constexpr int SCAN_ROUNDS = 8;  // cheap steps between two compares, at most ...
+constexpr int SCAN_ROUNDS_DENSE = 4;  // ... this many when the compare before had
+constexpr uint32_t SCAN_DENSE_HITS = 32;  // this many runs in it (of 128): measured,
+                                          // text (20 a compare) is 6 % faster with 8 rounds than with 4, 3-bit symbols (56) 5 % slower
+constexpr int SCAN_MIN_WALKERS = 16;  // ... and only while this many lanes of the wave still walk
+constexpr uint32_t SCAN_HANDOUT = 24;  // finished positions wait for this many lanes with one
 
 // The same walk for one lane's positions first, first + step, ... < pend, serially (the host
 // model's form; the device runs lz_match_scan_pool below on the same pieces).
@@ -523,13 +506,8 @@ ZD_HD void lz_match_scan_serial(const uint8_t *s, uint32_t len, uint32_t first, 
 // everywhere: -6.5 % on the benchmark's symbols, -2 % on 3-bit symbols, -36 % on text.  Results
 // are stored per position, so who walks which position does not matter.  Returns the wave's
 // iteration count.
-#ifndef ZD_POOL_TAPER
-#define ZD_POOL_TAPER 4096
-#endif
-constexpr uint32_t POOL_TAPER = ZD_POOL_TAPER;
-#ifndef ZD_POOL_TAPER_Q
-#define ZD_POOL_TAPER_Q 2
-#endif
+constexpr uint32_t POOL_TAPER = 4096;
+constexpr uint32_t POOL_TAPER_Q = 2;  // chunks of a quarter for the last POOL_TAPER / POOL_TAPER_Q positions (TilePool below)
 constexpr uint32_t POOL_CHUNK = 256;  // >= 64 * NP: a fresh chunk serves any one handout.  Measured, same box, 128 / 256 / 512:
                                       // C2 5.58 / 5.44-5.48 / 5.83 ms, real text 145.5 / 150.1 / 167.5 ms
 // first form of the walk (match_run_step: every candidate's 8 bytes are read): the faster one
@@ -573,7 +551,7 @@ struct TilePool {
       if (taper) {
         const uint32_t seen = __hip_atomic_load(pool_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         const uint32_t left = seen > pend - pbeg ? 0u : pend - pbeg - seen;  // (what another wave takes in between: a chunk more or less)
-        const uint32_t small = left <= taper / ZD_POOL_TAPER_Q ? 2u : left <= taper ? 1u : 0u;
+        const uint32_t small = left <= taper / POOL_TAPER_Q ? 2u : left <= taper ? 1u : 0u;
         c = atomicAdd(pool_next, POOL_CHUNK >> small) | (small << 30);
       } else {
         c = atomicAdd(pool_next, POOL_CHUNK);
@@ -596,7 +574,7 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
 // integer again: `ballot(fin)` went through v_cndmask 0 / 1 + v_cmp_ne, `steps + (walk ? 1 : 0)` through a select and an add.
 // Here the finished runs come back as a mask and the steps are counted by an add-with-carry of the walk mask: three vector
 // instructions fewer per run slot and iteration, no scalar instruction more (the mask form that moved MORE to the scalar
-// unit lost: tools/experiments/lz_match_walk_masks).  Returns the lanes whose position is finished.
+// unit lost: `git show 4d5ffca:tools/experiments/lz_match_walk_masks`).  Returns the lanes whose position is finished.
 template <typename Sink, typename S, typename P>
 __device__ __forceinline__ unsigned long long match_run_step_masks(MatchRun &r, S s, P prev, uint32_t K, uint32_t Kq, Sink sink) {
   auto ballot = [](bool b) { return (unsigned long long)__builtin_amdgcn_ballot_w64(b); };
@@ -675,13 +653,8 @@ __device__ __forceinline__ uint32_t lz_match_runs_pool(S s, uint32_t len, Pool &
 #pragma unroll
     for (int i = 0; i < NP; i++) {
       ZD_COUNT(8, __builtin_popcountll(__builtin_amdgcn_ballot_w64(r[i].alive != 0)));
-#ifdef ZD_MATCH_FIRST_SHARED
-      const bool fin = match_run_step_to<true>(r[i], s, prev, (uint32_t)K, (uint32_t)Kq, sink);
-      const unsigned long long fm = __builtin_amdgcn_ballot_w64(fin);
-#else
       const unsigned long long fm = match_run_step_masks(r[i], s, prev, (uint32_t)K, (uint32_t)Kq, sink);
       const bool fin = __builtin_amdgcn_inverse_ballot_w64(fm);
-#endif
       if (fm) {  // wave-uniform
         ZD_COUNT(6, 1); ZD_COUNT(7, __builtin_popcountll(fm));
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
@@ -698,9 +671,6 @@ __device__ __forceinline__ uint32_t lz_match_runs_pool(S s, uint32_t len, Pool &
         } else {
           next = rem > taken ? next + taken : cend;
         }
-#ifdef ZD_MATCH_FIRST_SHARED
-        if (fin) match_run_start<true>(r[i], s, len, np < lim ? np : lim, lim, prev);
-#else
         if (fin) {  // match_run_start with the position's test made once (the shared form clamps np to lim and then compares again)
           MatchRun &n = r[i];
           const uint32_t park = lim ? lim - 1u : 0u;  // a finished run parks on a valid position
@@ -713,7 +683,6 @@ __device__ __forceinline__ uint32_t lz_match_runs_pool(S s, uint32_t len, Pool &
           n.pw = load_u64_words(s, n.p);
           n.dn = prev[n.p];
         }
-#endif
       }
       alive |= r[i].alive;
     }
@@ -777,7 +746,7 @@ struct ScanSlotMasks { unsigned long long W, H, F, L; };  // walking, hit, fin, 
 #define ZD_SCAN_EXIT_ASM(L, N) L ":\n\ts_mov_b32 %[n], " N "\n\ts_branch 99f\n"
 #define ZD_STR_(x) #x
 #define ZD_STR(x) ZD_STR_(x)
-// (SCAN_ROUNDS rounds at most, ZD_SCAN_ROUNDS_DENSE -- the exit behind the fourth -- when dense is set)
+// (SCAN_ROUNDS rounds at most, SCAN_ROUNDS_DENSE -- the exit behind the fourth -- when dense is set)
 #define ZD_SCAN_BODY(ROUND, SAVE, HITS)                                                                                 \
   "s_mov_b64 %[sv], exec\n\t" SAVE                                                                                      \
   ROUND("11f") ROUND("12f") ROUND("13f") ROUND("14f")                                                                   \
@@ -797,7 +766,7 @@ struct ScanSlotMasks { unsigned long long W, H, F, L; };  // walking, hit, fin, 
 #define ZD_SCAN_SHARED_IN [cs] "s"(cs), [minw] "s"((uint32_t)SCAN_MIN_WALKERS), [dense] "s"(dense)
 template <int NP>
 __device__ __forceinline__ uint32_t scan_rounds_lds(ScanRun (&r)[NP], ScanSlotMasks (&m)[NP], uint32_t (&h)[NP], uint32_t cs, uint32_t dense) {
-  static_assert(SCAN_ROUNDS == 8 && ZD_SCAN_ROUNDS_DENSE == 4, "the loop below is unrolled by hand");
+  static_assert(SCAN_ROUNDS == 8 && SCAN_ROUNDS_DENSE == 4, "the loop below is unrolled by hand");
   static_assert(NP >= 2 && NP <= 4, "written out for two to four run slots");
   unsigned long long sv, any, ws[NP];
   uint32_t a, la, g[NP], n;

@@ -542,12 +542,8 @@ __device__ __forceinline__ bool wide_turns(InflateLane &d, const LaneLds &L, uin
 // it found a literal of n bits, what it finds is the k-th symbol from here.  The literals in front of the first lane that
 // found something else are stored side by side and the position moves behind them; that lane's symbol is the next turn's.
 // (n <= LIT_TBITS: the table's entry is the whole code.  ready: words of input staged from the position's word on.)
-#ifndef ZD_STRIDE_MIN
-#define ZD_STRIDE_MIN 4
-#endif
-#ifndef ZD_STRIDE_WAIT
-#define ZD_STRIDE_WAIT 8
-#endif
+constexpr uint32_t STRIDE_MIN = 4;  // a strided turn that got fewer symbols than this ...
+constexpr int STRIDE_WAIT = 8;      // ... is followed by this many rounds of wide turns before the next is tried
 template <int MODE>
 __device__ __forceinline__ uint32_t strided_turn(InflateLane &d, const LaneLds &L, uint8_t *__restrict__ dst, int lane, uint32_t n, uint32_t ready) {
   const uint32_t p = d.boff + n * (uint32_t)lane;
@@ -784,9 +780,6 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
         ZD_PH_START();
         if (MULTI) fixed_tables = d.phase == PH_TABLES && d.hdr_fixed != 0;  // (a dynamic header's codes go where the fixed ones stood)
         wave_tables(d, L, lane);
-#ifdef ZD_HDR_SPLIT  // (experiment: the tables booked as "wide turns", the wide tables as "services+rest")
-        ZD_PH(ph_wide);
-#endif
         if (d.phase == PH_SYMBOLS) {
           const uint32_t shortest = build_wide_tables(d, L, lane);
           d.levels = levels_for(wave_min(shortest));
@@ -813,9 +806,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
             break;  // (the input ring starts over)
           }
         }
-#ifndef ZD_HDR_SPLIT
         ZD_PH(ph_hdr);
-#endif
       } else if (MULTI && d.phase == PH_SYMBOLS && d.fixed_lazy && fixed_tables) {
         // (an explorer walks fixed block after fixed block: the tables of the one before are this one's -- nothing
         // but a dynamic header's wave_tables writes where they stand -- instead of 48 symbols decoded one by one and
@@ -880,7 +871,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
           stopped = false;
         } else {
           // (a strided turn that got little: wide turns for a while -- the stretch is not of one length)
-          if (try_stride) stride_wait = stride_got < (uint32_t)ZD_STRIDE_MIN ? ZD_STRIDE_WAIT : 0;  // (a strided turn costs a quarter of a wide one: four symbols pay for it)
+          if (try_stride) stride_wait = stride_got < STRIDE_MIN ? STRIDE_WAIT : 0;  // (a strided turn costs a quarter of a wide one: four symbols pay for it)
           else if (stride_wait > 0) stride_wait--;
           const uint32_t before = d.out_pos;
           if (d.levels == 4) stopped = wide_turns<4, MODE>(d, L, dst, tok, lane, turn);

@@ -261,11 +261,6 @@ ZD_WV void span_advance(SpanReader &R, const SpanEnv &E, uint32_t p) {  // the p
   }
 }
 
-#ifdef SPAN_TRACE
-static uint64_t span_trace_steps[8];
-static uint64_t span_trace_seq;  // holes filled one after the other by the whole wave
-static uint32_t span_lane_steps[64];
-#endif
 // ---- phase A: a lane's walk over a region, recording the index
 struct SpanWalk {
   uint32_t p;         // bit position of the next symbol (from the span's first word)
@@ -311,18 +306,9 @@ template <bool STITCH>
 ZD_WV void span_walk_loop(SpanWalk &W, SpanReader &R, const SpanEnv &E, const LaneLds &L, uint16_t *idx,
                           int lit_max_sym, int dist_max_sym) {
   for (;;) {
-#ifdef SPAN_TRACE
-    if (E.lane == 0) span_trace_steps[STITCH ? 1 : 0] += 4;
-#endif
     uint32_t pq[4], oq[4];  // position and the granule's bytes after each step
 #pragma unroll
     for (int u = 0; u < 4; u++) {
-#ifdef SPAN_TRACE
-      if (W.run && !span_can_step(R)) span_trace_steps[4]++;
-      if (W.run) span_trace_steps[5]++;
-      if (W.run && E.lane == 5) span_trace_steps[6]++;
-      if (W.run && !STITCH) span_lane_steps[E.lane]++;
-#endif
       const bool ok = W.run && span_can_step(R);
       uint32_t xlo, xhi, tot, outlen;
       bool slow;
@@ -539,9 +525,6 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
   if (TG > 64u * K) TG = 64u * K;
   uint32_t n_lanes = TG / SPAN_K_MIN;
   if (n_lanes > 64u) n_lanes = 64u;
-#ifdef SPAN_TRACE
-  if (lane == 0) fprintf(stderr, "span geometry: usable %u K %u TG %u lanes %u\n", usable, K, TG, n_lanes);
-#endif
   if (n_lanes < SPAN_MIN_LANES) return SPAN_NONE;
 
   SpanEnv E;
@@ -610,11 +593,6 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
       kr = len;
     }
   }
-#ifdef SPAN_TRACE
-  if (lane == 0) fprintf(stderr, "regions: ");
-  for (int i = 0; i < 64; i++) { const uint32_t v = wv::readlane(kr, (uint32_t)i); if (lane == 0) fprintf(stderr, "%u ", v); }
-  if (lane == 0) fprintf(stderr, "\n");
-#endif
 
   ZD_SPAN_PH(2);
   // ---- phase A: every lane its own region
@@ -636,9 +614,7 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
       const uint32_t n = wv::readlane(c, l);
       if (n > best_n) { best_n = n; best_len = l; }
     }
-#ifndef ZD_SPAN_NO_HINT
     if (best_len != 0u && in_span) hint_adj = (best_len - (g0 * SPAN_G) % best_len) % best_len;
-#endif
   }
   W.p = base + (in_span ? g0 : 0u) * SPAN_G;
   W.nb = W.p + SPAN_G;
@@ -706,9 +682,6 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
       else { n_valid = wv::readlane(g0, f) + kk; end_stop = true; }  // WK_STOP
     }
   }
-#ifdef SPAN_TRACE
-  if (lane == 0) fprintf(stderr, "span: usable %u K %u TG %u lanes %u n_valid %u p_end-base %u stop %d\n", usable, K, TG, n_lanes, n_valid, p_end - base, (int)end_stop);
-#endif
 
   // the index leaves LDS (phase B needs the tile's place): its verified part, to the stream's scratch
   wv::sync();
@@ -790,9 +763,6 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
       for (int u = 0; u < SPAN_FLY; u++) {
         if (MODE == IM_REAL) span_land(tile, f_meta[u], f_a[u], f_b[u]);
         const bool act = p < stop_p;
-#ifdef SPAN_TRACE
-        if (lane == 0) span_trace_steps[2]++;
-#endif
         uint32_t xlo, xhi;
         span_peek(R, p, xlo, xhi);
         const SpanSym s = span_symbol<true>(act, xlo, xhi, L, lit_max, dist_max);
@@ -1015,9 +985,6 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
         }
         wv::sync();
         for (uint32_t c0 = 0; c0 < n_near; c0 += 64u) {
-#ifdef SPAN_TRACE
-          if (lane == 0) span_trace_steps[3]++;
-#endif
           const bool have = c0 + ulane < n_near;
           const uint32_t dp = have ? (uint32_t)list[c0 + ulane] : 0u;
           uint32_t dist = 1, len = 0;
@@ -1033,9 +1000,6 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
           const int b = sp + (int)len < (int)dp ? sp + (int)len : (int)dp;
           bool open = have;
           for (;;) {
-#ifdef SPAN_TRACE
-            if (lane == 0) span_trace_steps[7]++;
-#endif
             const bool ready = open && (b <= a || !span_bits_any(mbits, (uint32_t)a, (uint32_t)b));
             const bool go = ready && len <= SPAN_LONG;
             // a period of 1, 2 or 3 bytes: twelve bytes of it in registers
@@ -1111,9 +1075,6 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
                 const uint32_t last = l + run - 1u > 63u ? 63u : l + run - 1u;
                 const uint32_t ldp = wv::readlane(dp, l), ldist = wv::readlane(dist, l);
                 const uint32_t total = wv::readlane(lincl, last) - wv::readlane(lincl, l) + wv::readlane(len, l);
-#ifdef SPAN_TRACE
-                if (lane == 0) span_trace_seq++;
-#endif
                 span_fill_by_wave(tile, gbase, ldp, ldist, total, ulane);
                 if (ulane == 0u) span_bits_mark<false>(mbits, ldp, total);
                 wv::sync();
@@ -1162,11 +1123,6 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
   }
 
   // ---- the stream goes on behind the committed symbols
-#ifdef SPAN_TRACE
-  if (lane == 0) { for (int i = 0; i < 64; i++) fprintf(stderr, "%u ", span_lane_steps[i]); fprintf(stderr, "\n"); }
-  if (lane == 0) fprintf(stderr, "hole groups %llu rounds %llu one-by-one %llu so far; ", (unsigned long long)span_trace_steps[3], (unsigned long long)span_trace_steps[7], (unsigned long long)span_trace_seq);
-  if (lane == 0) fprintf(stderr, "steps: A %llu stitch %llu B %llu; lane-steps starved %llu running %llu lane5 %llu\n", (unsigned long long)span_trace_steps[0], (unsigned long long)span_trace_steps[1], (unsigned long long)span_trace_steps[2], (unsigned long long)span_trace_steps[4], (unsigned long long)span_trace_steps[5], (unsigned long long)span_trace_steps[6]);
-#endif
   const bool progress = p_end != base || out_pos != out_pos0;
   d.out_pos = out_pos;
   d.in_word = in_word + (p_end >> 5);
