@@ -123,16 +123,7 @@ def patched(text, old, new, where):
 
 def build_oracle(m, out_dir, cc="gcc"):
     """oracle/zd_oracle.c with mutant `m` applied, built the way oracle/Makefile builds the oracle -> path of the .so"""
-    src = patched(open(ORACLE_C).read(), m.c[0], m.c[1], "oracle/zd_oracle.c " + m.name)
-    d = os.path.join(out_dir, m.name)
-    os.makedirs(d, exist_ok=True)
-    with open(os.path.join(d, "zd_oracle.c"), "w") as f:
-        f.write(src)
-    with open(os.path.join(d, "zd_oracle.h"), "w") as f:
-        f.write(open(ORACLE_H).read())
-    so = os.path.join(d, "libzd_oracle.so")
-    subprocess.run([cc] + CFLAGS + ["-o", so, os.path.join(d, "zd_oracle.c")], check=True, capture_output=True)
-    return so
+    return build_oracle_patched(m.name, [m.c], out_dir, cc)
 
 
 def second_reading(m=None):
@@ -153,3 +144,117 @@ def second_reading_record(Z, data, level):
     import make_deflate_vectors
 
     return make_deflate_vectors.record(Z, data, level, adler_by_encoder=True)
+
+
+# ---- inflate ------------------------------------------------------------------------------------------------------
+# One-line mutants of the oracle's decoder, each a rule of zd.ml:355-391, 564-709 in its "obvious" other reading, and
+# the case of tests/golden/inflate_rules.py that is expected to kill it ("name/wrapper").  `patches` are (old, new)
+# text pairs of oracle/zd_oracle.c, each matching once.  A relaxed mutant (one that accepts more) clamps where the
+# real decoder would have refused before indexing a table, so that it stays well-defined.
+#
+# `killer` None: an equivalent mutant, which no input can tell from the oracle -- the test requires it to change
+# nothing, so that the claim is checked too.  empty_codelen_code_ok: with no code-length code every code-length
+# symbol is undecodable, so read_symbol refuses the block at its first code-length symbol (hlit + hdist >= 258 of them
+# follow), with the same status the missing check gives.
+InflateMutant = collections.namedtuple("InflateMutant", "name ref what patches killer")
+
+_RAISE = "ZD_RAISE(d->x, ZD_ERR_CORRUPTED);"
+INFLATE_MUTANTS = [
+    # -- what the deflate-side inputs and the header fuzz left standing
+    InflateMutant("hlit_287_ok", "zd.ml:641", "HLIT 287 accepted",
+                  [("if (hlit > MAX_LITLEN_SYM_COUNT ||", "if (hlit > MAX_LITLEN_SYM_COUNT + 1 ||")], "hlit_287/a"),
+    InflateMutant("hdist_31_ok", "zd.ml:641", "HDIST 31 accepted",
+                  [("|| hdist > MAX_DIST_SYM_COUNT)", "|| hdist > MAX_DIST_SYM_COUNT + 1)")], "hdist_31/a"),
+    InflateMutant("cl16_first_ok", "zd.ml:653", "code-length symbol 16 accepted as the first item (it copies a 0)",
+                  [("      if (num == 0) " + _RAISE + "\n      repeat = (int)read_int(d, 3, 2);\n      sym = lengths[num - 1];",
+                    "      repeat = (int)read_int(d, 3, 2);\n      sym = num ? lengths[num - 1] : 0;")], "cl16_first/a"),
+    InflateMutant("eob_length_zero_ok", "zd.ml:662", "lengths[256] == 0 accepted",
+                  [("  if (lengths[256] == 0) " + _RAISE + "\n", "")], "lengths256_zero_over_limit/a"),
+    InflateMutant("dist_out_plus_1_ok", "zd.ml:614", "a distance of out_len + 1 accepted (it copies zeros)",
+                  [("    if (dist > (int64_t)d->dst.len) " + _RAISE + "\n",
+                    "    if (dist > (int64_t)d->dst.len + 1) " + _RAISE + "\n"
+                    "    if (dist > (int64_t)d->dst.len) { for (int64_t k = 0; k < length; k++) buf_add_uint8(&d->dst, 0); continue; }\n")],
+                  "match_first/a"),
+    InflateMutant("no_phantom", "zd.ml:389-390", "a single code's second code decodes the same symbol (no phantom)",
+                  [("t->symbols[1] = t->max_sym + 1; }", "t->symbols[1] = t->max_sym; }")], "litlen_eob_only_phantom/a"),
+    InflateMutant("phantom_is_0", "zd.ml:389-390", "the phantom symbol is 0",
+                  [("t->symbols[1] = t->max_sym + 1; }", "t->symbols[1] = 0; }")], "litlen_eob_only_phantom/a"),
+    InflateMutant("codelen_phantom_unchecked", "zd.ml:646", "the code-length symbol's sym > max_sym check removed",
+                  [("    if (sym > huff->max_sym) " + _RAISE, "    if (sym > CODELEN_SYM_MAX) " + _RAISE)],
+                  "codelen_single_phantom/a"),
+    InflateMutant("empty_codelen_code_ok", "zd.ml:635", "an empty code-length code accepted",
+                  [("  if (huff->max_sym == -1) " + _RAISE + "\n", "")], None),
+    InflateMutant("fixed_litlen_286_ok", "zd.ml:603", "fixed litlen symbols 286/287 accepted (as 285)",
+                  [("t->max_sym = LITLEN_SYM_MAX; /* 286 and 287 are unused */", "t->max_sym = LITLEN_SYM_FIXED_MAX;"),
+                   ("if (sym > hlitlen->max_sym || sym > LITLEN_SYM_MAX ||", "if (sym > hlitlen->max_sym ||"),
+                   ("length_value_of_sym_table[sym - LITLEN_FIRST_LEN_SYM]",
+                    "length_value_of_sym_table[(sym > LITLEN_SYM_MAX ? LITLEN_SYM_MAX : sym) - LITLEN_FIRST_LEN_SYM]")],
+                  "fixed_litlen_286/a"),
+    InflateMutant("fixed_dist_30_ok", "zd.ml:608", "fixed distance symbols 30/31 accepted (as 0)",
+                  [("t->max_sym = DIST_SYM_MAX; /* 30 and 31 are unused */", "t->max_sym = DIST_SYM_FIXED_MAX;"),
+                   ("if (dsym > hdist->max_sym || dsym > DIST_SYM_MAX)", "if (dsym > hdist->max_sym)"),
+                   ("dist_value_of_sym[dsym];", "dist_value_of_sym[dsym > DIST_SYM_MAX ? 0 : dsym];")],
+                  "fixed_dist_30/a"),
+    InflateMutant("btype3_as_fixed", "zd.ml:701", "BTYPE 3 decoded as a fixed block",
+                  [("    case 1: read_fixed_block(d); break;", "    case 1: case 3: read_fixed_block(d); break;")],
+                  "btype3_first/a"),
+    InflateMutant("size_before_distance", "zd.ml:612-616", "the size limit tested before the distance check",
+                  [("    if (dist > (int64_t)d->dst.len) ",
+                    "    if (d->dst.fixed && d->dst.len + (size_t)length > d->dst.cap) ZD_RAISE(d->x, ZD_ERR_SIZE_EXCEEDED);\n"
+                    "    if (dist > (int64_t)d->dst.len) ")], "far_match_over_limit/a"),
+    InflateMutant("size_before_stored_input", "zd.ml:677", "the size limit tested before a stored block's input check",
+                  [("  if (d->src_max - d->src_pos + 1 < length) ",
+                    "  if (d->dst.fixed && d->dst.len + (size_t)length > d->dst.cap) ZD_RAISE(d->x, ZD_ERR_SIZE_EXCEEDED);\n"
+                    "  if (d->src_max - d->src_pos + 1 < length) ")], "stored_short_of_input_and_limit/a"),
+    # -- what the earlier inputs already killed
+    InflateMutant("hlit_286_refused", "zd.ml:641", "HLIT 286 refused",
+                  [("if (hlit > MAX_LITLEN_SYM_COUNT ||", "if (hlit >= MAX_LITLEN_SYM_COUNT ||")], "hlit_286/a"),
+    InflateMutant("hdist_30_refused", "zd.ml:641", "HDIST 30 refused",
+                  [("|| hdist > MAX_DIST_SYM_COUNT)", "|| hdist >= MAX_DIST_SYM_COUNT)")], "hdist_30/a"),
+    InflateMutant("repeat_to_end_refused", "zd.ml:659", "a repeat that ends at hlit + hdist refused",
+                  [("if (repeat > hlit + hdist - num)", "if (repeat >= hlit + hdist - num)")], "cl18_ends_at_hlit_hdist/a"),
+    InflateMutant("repeat_one_past_ok", "zd.ml:659", "a repeat one past hlit + hdist accepted",
+                  [("if (repeat > hlit + hdist - num)", "if (repeat > hlit + hdist - num + 1)")], "cl18_one_past/a"),
+    InflateMutant("dist_eq_out_refused", "zd.ml:614", "a distance equal to the output so far refused",
+                  [("if (dist > (int64_t)d->dst.len)", "if (dist >= (int64_t)d->dst.len)")], "dist_eq_out/a"),
+    InflateMutant("stored_len_eq_input_refused", "zd.ml:677", "a stored LEN equal to the input left refused",
+                  [("if (d->src_max - d->src_pos + 1 < length)", "if (d->src_max - d->src_pos + 1 <= length)")],
+                  "stored_len_eq_input_left/a"),
+    InflateMutant("stored_header_5", "zd.ml:672", "a stored header wants 5 bytes left, not 4",
+                  [("if (d->src_max - d->src_pos + 1 < 4)", "if (d->src_max - d->src_pos + 1 < 5)")],
+                  "stored_len_zero_final/a"),
+    InflateMutant("single_code_refused", "zd.ml:377-378", "a single code refused",
+                  [("(num_codes == 1 && counts[1] != 1)", "(num_codes == 1)")], "litlen_eob_only/a"),
+    InflateMutant("single_code_any_length", "zd.ml:377-378", "a single code of any length accepted",
+                  [("if ((num_codes > 1 && available > 0) || (num_codes == 1 && counts[1] != 1))",
+                    "if (num_codes > 1 && available > 0)")], "litlen_single_len2/a"),
+    InflateMutant("oversubscribed_ok", "zd.ml:370", "an over-subscribed code accepted",
+                  [("    if (used > available) ZD_RAISE(x, ZD_ERR_CORRUPTED); /* over-subscribed */\n", "")],
+                  "litlen_oversubscribed/a"),
+    InflateMutant("incomplete_ok", "zd.ml:377", "an incomplete code of two or more codes accepted",
+                  [("if ((num_codes > 1 && available > 0) || (num_codes == 1 && counts[1] != 1))",
+                    "if (num_codes == 1 && counts[1] != 1)")], "litlen_incomplete/a"),
+    InflateMutant("nlen_unchecked", "zd.ml:675", "a stored block's NLEN not checked",
+                  [("if (length != ((~inv_length) & 0xFFFF))", "if (0 && length != ((~inv_length) & 0xFFFF))")],
+                  "stored_nlen_byte2_bit0/a"),
+    InflateMutant("litlen_285_refused", "zd.ml:603", "litlen symbol 285 refused",
+                  [("|| sym > LITLEN_SYM_MAX ||", "|| sym >= LITLEN_SYM_MAX ||")], "fixed_litlen_285/a"),
+    InflateMutant("dist_29_refused", "zd.ml:608", "distance symbol 29 refused",
+                  [("|| dsym > DIST_SYM_MAX)", "|| dsym >= DIST_SYM_MAX)")], "fixed_dist_29/a"),
+]
+
+
+def build_oracle_patched(name, patches, out_dir, cc="gcc"):
+    """oracle/zd_oracle.c with every (old, new) of `patches` applied, built as oracle/Makefile builds it -> the .so"""
+    src = open(ORACLE_C).read()
+    for old, new in patches:
+        src = patched(src, old, new, "oracle/zd_oracle.c " + name)
+    d = os.path.join(out_dir, name)
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, "zd_oracle.c"), "w") as f:
+        f.write(src)
+    with open(os.path.join(d, "zd_oracle.h"), "w") as f:
+        f.write(open(ORACLE_H).read())
+    so = os.path.join(d, "libzd_oracle.so")
+    subprocess.run([cc] + CFLAGS + ["-o", so, os.path.join(d, "zd_oracle.c")], check=True, capture_output=True)
+    return so

@@ -470,3 +470,126 @@ def test_coder_choose_mutants_are_killed(oracle, tmp_path):
         rows.append((m[0], changed))
     print("\n".join("%-28s %s" % (n, ("killed by " + " ".join(c)) if c else "SURVIVED") for n, c in rows))
     assert all(c for _, c in rows), rows
+
+
+def test_inflate_lane_equals_the_oracle_on_the_rule_cases(sim, oracle, monkeypatch):
+    """inflate_lane.h (plain step, fixed path, serial header and stored code) and its wide turn on every case of
+    tests/golden/inflate_rules.py in every wrapper, at budgets 512 and 7: status, bytes and Adler-32 as the oracle."""
+    import sys
+
+    sys.path.insert(0, util.GOLDEN)
+    import inflate_rules
+
+    cases = inflate_rules.wrapped_cases()
+    for wide in (False, True):
+        if wide:
+            monkeypatch.setenv("SIM_INFLATE_WIDE", "1")
+        for name, c in cases.items():
+            cap = c.limit if c.limit is not None else 1 << 20
+            st0, d0, a0 = oracle.inflate(c.stream, decompressed_size=cap, crc_op=oracle.CRC_ADLER32)
+            for budget in (512, 7):
+                st, d, a = sim_inflate(sim, c.stream, cap, limit=cap, crc_op=2, budget=budget)
+                assert st == st0 and (st != 0 or (d, a) == (d0, a0)), (name, wide, budget, st, st0)
+
+
+_LANE_CHILD = r"""
+import ctypes as C, json, os, sys
+sys.path.insert(0, os.path.join(sys.argv[2], "tests")); sys.path.insert(0, os.path.join(sys.argv[2], "tests", "golden"))
+sys.path.insert(0, sys.argv[2])
+import oracle, inflate_rules
+from host_sim import _bind
+sim = _bind(C.CDLL(sys.argv[1]))
+changed = []
+for name, c in inflate_rules.wrapped_cases().items():
+    cap = c.limit if c.limit is not None else 1 << 20
+    st0, d0, a0 = oracle.inflate(c.stream, decompressed_size=cap, crc_op=oracle.CRC_ADLER32)
+    dst = C.create_string_buffer(cap + 64)
+    ol, ck = C.c_uint64(), C.c_uint32()
+    st = sim.sim_inflate(c.stream, len(c.stream), dst, cap, 1, cap, 2, C.byref(ol), C.byref(ck), 512)
+    if st != st0 or (st == 0 and (dst.raw[:ol.value], ck.value) != (d0, a0)):
+        changed.append(name)
+print(json.dumps(changed))
+"""
+
+
+def test_inflate_lane_mutants_are_killed(oracle, tmp_path, capsys):
+    """tools/kernel_mutants.py's mutants of inflate_lane.h -- the stricter ones the GPU runs too, and relaxed ones --
+    each built into a host model of its own and run over every rule case (tests/golden/inflate_rules.py) in a child
+    process, plain and wide: each must change a result.  A relaxed mutant that read out of bounds would end its child,
+    not this run (and would count as a kill only through the results it printed: none)."""
+    import concurrent.futures
+    import json
+    import os
+    import shutil
+    import subprocess
+    import sys
+
+    from host_sim import HERE as SIM_DIR, SRCS
+    from tools import kernel_mutants as KM
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    muts = [(m, "stricter") for m in KM.LANE_INFLATE_MUTANTS] + [(m, "relaxed") for m in KM.LANE_INFLATE_RELAXED]
+
+    def build(m):
+        d = tmp_path / m[0]
+        KM.mutated_tree(m, str(d))
+        sim_dir = d / "tests" / "host_sim"
+        os.makedirs(sim_dir)
+        for f in os.listdir(SIM_DIR):
+            if f.endswith((".cpp", ".h")):
+                shutil.copy(os.path.join(SIM_DIR, f), sim_dir / f)
+        so = str(sim_dir / "libhost_sim.so")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-I", str(sim_dir), "-o", so]
+                       + [str(sim_dir / s) for s in SRCS], check=True)
+        return so
+
+    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+        sos = list(ex.map(build, [m for m, _ in muts]))
+    rows = []
+    for (m, kind), so in zip(muts, sos):
+        changed, notes = set(), []
+        for wide in ("0", "1"):
+            env = dict(os.environ)
+            env.pop("SIM_INFLATE_WIDE", None)
+            if wide == "1":
+                env["SIM_INFLATE_WIDE"] = "1"
+            r = subprocess.run([sys.executable, "-c", _LANE_CHILD, so, root], env=env, stdout=subprocess.PIPE,
+                               stderr=subprocess.STDOUT, timeout=600)
+            if r.returncode != 0:
+                notes.append("child rc %d" % r.returncode)
+                continue
+            changed |= set(json.loads(r.stdout.decode().strip().splitlines()[-1]))
+        rows.append((m[0], kind, sorted(changed), notes))
+    with capsys.disabled():
+        print("\ninflate_lane.h mutants in the host models against the rule cases")
+        for n, kind, changed, notes in rows:
+            print("  %-34s %-9s %4d changed  %s %s" % (n, kind, len(changed), changed[0] if changed else "SURVIVED", " ".join(notes)))
+        print("  %d of %d killed" % (sum(bool(c) for _, _, c, _ in rows), len(rows)))
+    assert all(c and not notes for _, _, c, notes in rows), rows
+
+
+def test_block_header_search_finds_the_dynamic_headers_around_the_rule_cases(sim, oracle):
+    """inflate_find.h on the accepted rule cases inside long streams (tests/golden/inflate_rules.py, wrapper e): every
+    dynamic block the inflate model decodes is among the candidates the search lists."""
+    import sys
+
+    sys.path.insert(0, util.GOLDEN)
+    import inflate_rules
+
+    sim.sim_find_candidates.restype = C.c_uint64
+    sim.sim_inflate_block_starts.restype = C.c_uint64
+    n = 0
+    for name, c in inflate_rules.wrapped_cases("e").items():
+        if not name.endswith("/e") or c.status != 0:
+            continue
+        st, d, _ = sim_inflate(sim, c.stream, len(c.plain), limit=len(c.plain))
+        assert st == 0 and d == c.plain, name
+        bits, types = (C.c_uint64 * 4096)(), (C.c_int * 4096)()
+        nb = sim.sim_inflate_block_starts(bits, types, 4096)
+        starts = {int(bits[i]) for i in range(nb) if types[i] == 2}
+        cand, nf = (C.c_uint64 * 65536)(), C.c_uint64()
+        nc = sim.sim_find_candidates(c.stream, len(c.stream), cand, 65536, C.byref(nf))
+        found = {int(cand[i]) for i in range(nc)}
+        assert len(starts) >= 4 and starts <= found, (name, sorted(starts - found))
+        n += 1
+    assert n >= 25

@@ -133,3 +133,59 @@ def test_a_mutant_must_match_once():
     with pytest.raises(AssertionError, match="occurs 2 times"):
         mutants.patched("xx", "x", "y", "t")
     assert mutants.patched("abc", "b", "B", "t") == "aBc"
+
+
+# ---- inflate: tests/golden/inflate_rules.py against mutants.INFLATE_MUTANTS ------------------------------------------
+
+def _inflate_changes(O, cases):
+    """the rule cases the loaded oracle does not decode as built: [name]"""
+    import zlib
+
+    changed = []
+    for name, c in cases.items():
+        st, d, k = O.inflate(c.stream, decompressed_size=c.limit, crc_op=O.CRC_CRC32)
+        if st != c.status or (st == 0 and (d != c.plain or k != zlib.crc32(c.plain))):
+            changed.append(name)
+    return changed
+
+
+def test_every_inflate_oracle_mutant_is_killed_by_its_named_rule_case(oracle, tmp_path, capsys):
+    """Every one-line mutant of the oracle's decoder (mutants.INFLATE_MUTANTS) changes the result of the rule case the
+    table names; an equivalent one (killer None) changes none."""
+    import inflate_rules
+
+    O = oracle
+    cases = inflate_rules.wrapped_cases()
+    assert _inflate_changes(O, cases) == []
+    names = [m.name for m in mutants.INFLATE_MUTANTS]
+    assert len(names) == len(set(names)) >= 27
+    assert all(m.killer is None or m.killer in cases for m in mutants.INFLATE_MUTANTS)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
+        sos = list(ex.map(lambda m: mutants.build_oracle_patched(m.name, m.patches, str(tmp_path)), mutants.INFLATE_MUTANTS))
+    rows, bad = [], []
+    saved_lib, saved_env = O._lib, os.environ.get("ZD_ORACLE_LIB")
+    try:
+        for m, so in zip(mutants.INFLATE_MUTANTS, sos):
+            os.environ["ZD_ORACLE_LIB"] = so
+            O._lib = None
+            O.lib()
+            changed = _inflate_changes(O, cases)
+            rows.append((m, changed))
+            if (m.killer is None) != (not changed) or (m.killer is not None and m.killer not in changed):
+                bad.append(m.name)
+    finally:
+        O._lib = saved_lib
+        if saved_env is None:
+            os.environ.pop("ZD_ORACLE_LIB", None)
+        else:
+            os.environ["ZD_ORACLE_LIB"] = saved_env
+    with capsys.disabled():
+        print("\noracle/zd_oracle.c decoder mutants against %d rule cases (tests/golden/inflate_rules.py)" % len(cases))
+        print("  %-28s %-14s %6s  %-40s %s" % ("mutant", "reference", "cases", "named killer", "first change"))
+        for m, changed in rows:
+            verdict = "equivalent" if m.killer is None else ("ok" if m.killer in changed else "MISSED")
+            print("  %-28s %-14s %6d  %-40s %s" % (m.name, m.ref, len(changed), "%s %s" % (m.killer, verdict),
+                                                     changed[0] if changed else "-"))
+        n_eq = sum(m.killer is None for m in mutants.INFLATE_MUTANTS)
+        print("  %d of %d killed by their named case, %d equivalent, %d wrong" % (len(rows) - n_eq - len(bad), len(rows) - n_eq, n_eq, len(bad)))
+    assert bad == []

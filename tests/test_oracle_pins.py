@@ -289,3 +289,83 @@ def test_the_tie_inputs_sit_on_their_ties(oracle):
     want = {("nf", True, None), ("fd", True, None), ("fd", False, None), ("q3", False, None)}
     want |= {("nf", False, k) for k in range(1, 9)}
     assert seen >= want, want - seen
+
+
+# ---- inflate's accept / reject rules (tests/golden/inflate_rules.py) -----------------------------------------------
+
+def _rules():
+    sys.path.insert(0, util.GOLDEN)
+    import inflate_rules
+
+    return inflate_rules
+
+
+def _adler_by_blocks(oracle, c):
+    """the reference's Adler-32 of an accepted case: one update per block (zd.ml:682-690; Q6 may fire in a long one)"""
+    a, prev = 1, 0
+    for cut in c.cuts:
+        a = oracle.adler32_update(a, c.plain[prev:cut])
+        prev = cut
+    return a
+
+
+def test_oracle_inflate_equals_the_rule_cases_by_construction(oracle):
+    """The oracle's status, bytes, CRC-32 and Adler-32 on every rule case in every wrapper equal what the case was
+    built to be: the cases are the second reading of the decoder, as zd_second_reading.py is of the encoder."""
+    R = _rules()
+    cases = R.wrapped_cases()
+    assert len(R.INFLATE_RULE_CASES) >= 100 and len(cases) >= 450
+    wrong = []
+    for name, c in cases.items():
+        for op, want in ((oracle.CRC_CRC32, lambda: zlib.crc32(c.plain)), (oracle.CRC_ADLER32, lambda: _adler_by_blocks(oracle, c))):
+            st, d, k = oracle.inflate(c.stream, decompressed_size=c.limit, crc_op=op)
+            if st != c.status or (st == 0 and (d != c.plain or k != want())):
+                wrong.append((name, st, c.status))
+    assert wrong == []
+    statuses = {c.status for c in cases.values()}
+    assert statuses == {R.OK, R.CORRUPTED, R.SIZE_EXCEEDED}
+
+
+def test_zlib_agrees_with_the_rule_cases_but_where_named(oracle):
+    """zlib (an independent decoder) gives an accepted case's bytes and refuses a refused one, except on the cases
+    inflate_rules.ZLIB_DIFFERS names: zlib has no size limit."""
+    R = _rules()
+    differ = set()
+    for name, c in R.wrapped_cases().items():
+        z = zlib.decompressobj(-15)
+        try:
+            got = z.decompress(c.stream)
+            ok = z.eof
+        except zlib.error:
+            got, ok = None, False
+        if c.status == R.OK:
+            assert ok and got == c.plain, name
+        elif ok:
+            differ.add(name.split("/")[0])
+    assert differ == set(R.ZLIB_DIFFERS)
+    assert all(R.SPECS[n].status == R.SIZE_EXCEEDED for n in differ)
+
+
+def test_the_rule_cases_have_both_sides(oracle):
+    """every rule has a case on each side; a truncated case's input ends before the last bit of the field it names,
+    and less than a byte before that field's first bit (inside it, or -- a field within one byte -- just before it)"""
+    R = _rules()
+    S = R.SPECS
+    for ok, bad in (("hlit_286", "hlit_287"), ("hdist_30", "hdist_31"), ("cl16_second", "cl16_first"),
+                    ("cl18_ends_at_hlit_hdist", "cl18_one_past"), ("cl17_ends_at_hlit_hdist", "cl17_one_past"),
+                    ("cl16_ends_at_hlit_hdist", "cl16_one_past"), ("litlen_eob_only", "litlen_eob_only_phantom"),
+                    ("dist_empty_literals", "dist_empty_match"), ("dist_single_29_bit0", "dist_single_29_phantom"),
+                    ("dist_eq_out", "dist_out_plus1"), ("dist_32768_at_32768", "dist_32768_at_32767"),
+                    ("stored_len_eq_input_left", "stored_len_input_left_plus1"), ("fixed_litlen_285", "fixed_litlen_286"),
+                    ("fixed_dist_29", "fixed_dist_30"), ("limit_exact", "limit_one_short")):
+        assert S[ok].status == R.OK and S[bad].status != R.OK, (ok, bad)
+    assert {"stored_phase%d" % p for p in range(8)} <= set(S)
+    for name, s in S.items():
+        if s.cut_at is not None:
+            raw, _, marks, _ = R.assemble(s.blocks, s.final_last)
+            start, n = marks[s.cut_at]
+            got = len(R.INFLATE_RULE_CASES[name].stream) * 8
+            assert start - 8 < got < start + n, name
+    assert len(R.INFLATE_RULE_CASES["eob_on_last_bit"].stream) * 8 == R.assemble(S["eob_on_last_bit"].blocks)[2]["eob"][0] + 7
+    big = [c for n, c in R.wrapped_cases("e").items() if n.endswith("/e")]
+    assert len(big) >= 40 and all(len(c.plain or b"") >= 600000 for c in big if c.status == R.OK)

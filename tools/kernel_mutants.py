@@ -12,6 +12,16 @@ within deflate_bound, so no mutant can write out of bounds.
                                           (build again after any change of zipc_amd/csrc)
   tools/kernel_mutants.py                 (on the MI355X) the vector tests of tests/test_gpu_parity.py against each
                                           mutant library (ZIPC_HIP_LIB), once; every mutant must make them fail
+  tools/kernel_mutants.py --inflate ...   the same for the inflate mutants below, against tests/test_gpu_inflate_rules.py
+
+Inflate: the accept / reject rules (zd.ml:355-391, 564-709) are written out again in inflate_lane.h (the plain step,
+the fixed path, the serial header and stored code, which the host models compile too), in inflate.hip's wave forms
+(wave_init_decoder, wave_tables, wave_dynamic_lengths) and in the refusals of inflate_span.h.  On the GPU a mutant only
+makes a check STRICTER -- it refuses more or stops earlier -- so it touches no memory the real kernel does not.  Each
+one of the decoding copies must make the rule tests fail.  The span's refusals hand a symbol to the plain step, so a
+stricter refusal must change NO result: those are listed as expected to survive, and the rule tests (under every
+override) passing under them is what shows the hand-off right.  The relaxed mutants (LANE_INFLATE_RELAXED) run only in
+the host models, in child processes: tests/test_host_sim.py::test_inflate_lane_mutants_are_killed.
 
 The coder_choose mutants are killed on the CPU: tests/test_host_sim.py::test_coder_choose_mutants_are_killed.
 Each text must occur exactly once in its file, so a change of the kernels cannot quietly make a mutant a no-op.
@@ -49,14 +59,63 @@ LANE_MUTANTS = [
     ("coder_choose_q3_mod_8", "deflate_lane.h",
      "(uint64_t)(8 - ((pending_bits + 3) % 8))", "(uint64_t)((8 - ((pending_bits + 3) % 8)) % 8)"),
 ]
+# (name, file, text, replacement, expected): stricter only, so safe on the GPU.  Expected: "killed"; "survives" (a span
+# refusal: the plain step decodes the symbol); "host-only" (the serial header code -- setup_dynamic_lengths and the
+# lane init_decoder -- which the kernels replace by wave_dynamic_lengths / wave_tables: killed in the host models);
+# "unreached" (the plain step's check of a dynamic block's distance symbol 29: no rule case brings a distance 29 to the
+# plain step on the GPU, where the wide table decodes it -- a gap, killed in the host models only)
+INFLATE_GPU_MUTANTS = [
+    ("lane_dist_eq_out_refused", "inflate_lane.h", "if (dist > d.out_pos) { d.fail", "if (dist >= d.out_pos) { d.fail", "killed"),
+    ("lane_litlen_285_refused", "inflate_lane.h", "if (sym > d.lit_max_sym || sym > LITLEN_SYM_MAX) { d.fail",
+     "if (sym > d.lit_max_sym || sym >= LITLEN_SYM_MAX) { d.fail", "killed"),
+    ("lane_dist_29_refused", "inflate_lane.h", "dsym > d.dist_max_sym || dsym > DIST_SYM_MAX) { d.fail",
+     "dsym > d.dist_max_sym || dsym >= DIST_SYM_MAX) { d.fail", "unreached"),
+    ("lane_fixed_litlen_285_refused", "inflate_lane.h", "if (sym > LITLEN_SYM_MAX) { d.fail(ST_CORRUPTED); return SYM_STOP; }",
+     "if (sym >= LITLEN_SYM_MAX) { d.fail(ST_CORRUPTED); return SYM_STOP; }", "killed"),
+    ("lane_fixed_dist_29_refused", "inflate_lane.h", "if (dsym > DIST_SYM_MAX) { d.fail", "if (dsym >= DIST_SYM_MAX) { d.fail", "killed"),
+    ("lane_hlit_286_refused", "inflate_lane.h", "if (hlit > 286 || hdist > 30)", "if (hlit > 285 || hdist > 30)", "killed"),
+    ("lane_hdist_30_refused", "inflate_lane.h", "if (hlit > 286 || hdist > 30)", "if (hlit > 286 || hdist > 29)", "killed"),
+    ("lane_cl16_second_refused", "inflate_lane.h", "if (num == 0) return -1;  // zd.ml:653", "if (num <= 1) return -1;", "host-only"),
+    ("lane_repeat_to_end_refused", "inflate_lane.h", "if (repeat > (uint32_t)(total - num)) return -1;",
+     "if (repeat >= (uint32_t)(total - num)) return -1;", "host-only"),
+    ("lane_eob_length_1_refused", "inflate_lane.h", "if (L.u16(LDS_LENGTHS, 256) == 0) return -1;",
+     "if (L.u16(LDS_LENGTHS, 256) <= 1) return -1;", "host-only"),
+    ("lane_single_code_refused", "inflate_lane.h", "(num_codes == 1 && L.u16(counts_off, 1) != 1))\n    return false;",
+     "(num_codes == 1))\n    return false;", "host-only"),
+    ("lane_stored_len_eq_input_refused", "inflate_lane.h", "if (d.src_len - pos < length)", "if (d.src_len - pos <= length)", "killed"),
+    ("lane_stored_header_5", "inflate_lane.h", "d.src_len - pos < 4)", "d.src_len - pos < 5)", "killed"),
+    ("wave_single_code_refused", "inflate.hip", "(num_codes == 1 && L.u16(counts_off, 1) != 1)) return false;",
+     "(num_codes == 1)) return false;", "killed"),
+    ("wave_tables_empty_code_refused", "inflate.hip", "(job == 0 && max_sym == -1)) {", "(max_sym == -1)) {", "killed"),
+    ("wave_cl16_second_refused", "inflate.hip", "(sym == 16u && start == 0u)", "(sym == 16u && start <= 1u)", "killed"),
+    ("wave_repeat_to_end_refused", "inflate.hip", "repeat > total - start);", "repeat >= total - start);", "killed"),
+    ("wave_eob_length_1_refused", "inflate.hip", "if (L.u16(LDS_LENGTHS, 256) == 0) return -1;",
+     "if (L.u16(LDS_LENGTHS, 256) <= 1) return -1;", "killed"),
+    ("span_refuses_the_top_litlen_symbol", "inflate_span.h", "sym > lit_max_sym || sym > LITLEN_SYM_MAX) {",
+     "sym >= lit_max_sym || sym > LITLEN_SYM_MAX) {", "survives"),
+    ("span_refuses_the_top_dist_symbol", "inflate_span.h", "dsym > dist_max_sym || dsym > DIST_SYM_MAX) {",
+     "dsym >= dist_max_sym || dsym > DIST_SYM_MAX) {", "survives"),
+]
+# the host models' copies: the inflate_lane.h mutants above, and relaxed ones (accept more) that stay in bounds
+LANE_INFLATE_MUTANTS = [m[:4] for m in INFLATE_GPU_MUTANTS if m[1] == "inflate_lane.h"]
+LANE_INFLATE_RELAXED = [
+    ("lane_nlen_unchecked", "inflate_lane.h", "if (length != ((~inv) & 0xFFFFu))", "if (0 && length != ((~inv) & 0xFFFFu))"),
+    ("lane_single_code_any_length", "inflate_lane.h",
+     "if ((num_codes > 1 && available > 0) || (num_codes == 1 && L.u16(counts_off, 1) != 1))",
+     "if (num_codes > 1 && available > 0)"),
+    ("lane_incomplete_ok", "inflate_lane.h",
+     "if ((num_codes > 1 && available > 0) || (num_codes == 1 && L.u16(counts_off, 1) != 1))",
+     "if (num_codes == 1 && L.u16(counts_off, 1) != 1)"),
+]
 # what runs against each GPU mutant: the vectors under the default form, then under every override (one process each)
 TESTS = "tests/test_gpu_parity.py"
 SELECT = "second_readings_vectors"
+INFLATE_TESTS = "tests/test_gpu_inflate_rules.py"
 
 
 def mutated_tree(mutant, into):
     """copies of zipc_amd/csrc and include/ under `into` (the relative includes resolve), one mutant applied"""
-    name, fname, old, new = mutant
+    name, fname, old, new = mutant[:4]
     csrc = os.path.join(into, "zipc_amd", "csrc")
     shutil.copytree(CSRC, csrc, ignore=shutil.ignore_patterns("build"))
     shutil.copytree(os.path.join(ROOT, "include"), os.path.join(into, "include"))
@@ -71,25 +130,31 @@ def mutated_tree(mutant, into):
 
 
 def build(mutant):
-    """libzipc_hip.so with the mutated deflate.hip and the product's other objects -> its path"""
+    """libzipc_hip.so with the mutated unit (deflate.hip, or inflate.hip for the inflate files) and the product's other
+    objects -> its path"""
     name = mutant[0]
+    unit = "inflate" if mutant[1].startswith("inflate") else "deflate"
     so = os.path.join(OUT, "libzipc_hip_%s.so" % name)
     with tempfile.TemporaryDirectory() as tmp:
         csrc = mutated_tree(mutant, tmp)
-        obj = os.path.join(tmp, "deflate.o")
-        subprocess.run([HIPCC] + HIPFLAGS + ["-c", os.path.join(csrc, "deflate.hip"), "-o", obj], check=True)
-        others = [os.path.join(CSRC, "build", o + ".o") for o in ("api", "inflate", "checksum")]
+        obj = os.path.join(tmp, unit + ".o")
+        subprocess.run([HIPCC] + HIPFLAGS + ["-c", os.path.join(csrc, unit + ".hip"), "-o", obj], check=True)
+        others = [os.path.join(CSRC, "build", o + ".o") for o in ("api", "inflate", "checksum", "deflate") if o != unit]
         os.makedirs(OUT, exist_ok=True)
         subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, obj] + others, check=True)
     return so
 
 
-def run(name, so):
+def run(name, so, tests=TESTS, select=SELECT):
     """the vector tests against one mutant library: -> (killed, the failing test)"""
     env = dict(os.environ, ZIPC_HIP_LIB=so)
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-rf", "-m", "gpu", "-p", "no:cacheprovider", TESTS,
-                        "-k", SELECT], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=3000)
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-rf", "-m", "gpu", "-p", "no:cacheprovider", tests]
+                       + (["-k", select] if select else []), cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, timeout=1200)
     out = r.stdout.decode()
+    if r.returncode < 0 or r.returncode in (134, 139):  # an abort or a fault is not a kill: start nothing more
+        sys.stderr.write(out[-3000:])
+        raise SystemExit("%s: the test process ended with status %d; stopping" % (name, r.returncode))
     failed = re.findall(r"^FAILED (\S+)(.*)$", out, re.M)
     if r.returncode == 0:
         return False, "-"
@@ -103,27 +168,40 @@ def run(name, so):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--build", action="store_true", help="build the mutant libraries only")
+    ap.add_argument("--inflate", action="store_true", help="the inflate mutants (INFLATE_GPU_MUTANTS)")
     ap.add_argument("only", nargs="*", help="mutant names (default: all)")
     a = ap.parse_args()
     subprocess.run(["make", "-s", "-C", CSRC, "-j4", "all"], check=True)
-    mutants = [m for m in GPU_MUTANTS if not a.only or m[0] in a.only]
+    table = INFLATE_GPU_MUTANTS if a.inflate else [m + ("killed",) for m in GPU_MUTANTS]
+    mutants = [m for m in table if not a.only or m[0] in a.only]
     sos = {}
-    for m in mutants:  # (built once, before the GPU run: a run uses what --build left)
+
+    def one(m):  # (built once, before the GPU run: a run uses what --build left)
         so = os.path.join(OUT, "libzipc_hip_%s.so" % m[0])
-        sos[m[0]] = build(m) if a.build or not os.path.exists(so) else so
+        return build(m) if a.build or not os.path.exists(so) else so
+
+    import concurrent.futures
+    with concurrent.futures.ThreadPoolExecutor(max_workers=8) as ex:
+        for m, so in zip(mutants, ex.map(one, mutants)):
+            sos[m[0]] = so
     if a.build:
         print("\n".join(sos.values()))
         return 0
     rows = []
     for m in mutants:
-        killed, by = run(m[0], sos[m[0]])
-        rows.append((m[0], killed, by))
-        print("%-28s %-9s %s" % (m[0], "killed" if killed else "SURVIVED", by), flush=True)
-    survivors = [n for n, k, _ in rows if not k]
-    print("\nkernel chooser mutants: %d of %d killed, %d surviving" % (len(rows) - len(survivors), len(rows), len(survivors)))
-    for n, k, by in rows:
-        print("  %-28s %-9s %s" % (n, "killed" if k else "SURVIVED", by))
-    return 1 if survivors else 0
+        if a.inflate:  # killers: the rule tests in this process; the expected survivors also under every override
+            killed, by = run(m[0], sos[m[0]], INFLATE_TESTS, "not overrides" if m[4] == "killed" else None)
+        else:
+            killed, by = run(m[0], sos[m[0]])
+        rows.append((m[0], m[4], killed, by))
+        print("%-36s %-9s %s" % (m[0], "killed" if killed else "SURVIVED", by), flush=True)
+    wrong = [n for n, want, k, _ in rows if k != (want == "killed")]
+    print("\nkernel %s mutants: %d of %d as expected, %d not" % ("inflate" if a.inflate else "chooser", len(rows) - len(wrong),
+                                                              len(rows), len(wrong)))
+    print("  %-36s %-9s %-9s %s" % ("mutant", "expected", "got", "first failing test"))
+    for n, want, k, by in rows:
+        print("  %-36s %-9s %-9s %s" % (n, want, "killed" if k else "survived", by))
+    return 1 if wrong else 0
 
 
 if __name__ == "__main__":
