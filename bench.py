@@ -21,7 +21,14 @@ RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set), relay
 line and exits non-zero if any worker failed.  Under torch.distributed.run the environment's
 WORLD_SIZE must equal --gpus.
 
-Extra objects in the JSON line: "roofline" (dominant kernel: the algorithmic bytes of the streams ONE launch covers --
+A plain run does only what the headline needs: it sets up (inputs, buffers, one untimed pass that fixes the inflate
+descriptors and checks the round trip), warms up, times the steps, writes --dump-outputs and prints the line: "metric",
+"value", "unit", "ms_per_step", the shape in "config", the ranks' own times and, with --dump-outputs, "dump_outputs".
+Everything else the benchmark measures or checks runs with --full only: the cpu_baseline process and the oracle's parity
+samples, the profiled steps behind "roofline", "kernels_ms_per_step" and the two directions' GiB/s, the untimed legs (C2)
+and the archive check (C4); --no-cpu-baseline, --no-extra-legs, --no-archive-check and --alone-pass act on those.
+
+Extra objects in the JSON line with --full: "roofline" (dominant kernel: the algorithmic bytes of the streams ONE launch covers --
 a step is two slices on two queues, a launch half the batch -- over its HIP-event duration, against the 8 TB/s HBM peak;
 its "others" lists the step's other kernels the same way, "deflate_pipeline" / "inflate" the directions over their wall
 time; --alone-pass adds every kernel launched alone over the whole batch; SCALARS inside it -- and again inside "config" --
@@ -63,20 +70,27 @@ def parse_args(argv=None):
     ap.add_argument("--stream-len", type=int, default=None, help="c2: 65536; c4: 1048576")
     ap.add_argument("--bits", type=int, default=None, help="entropy bits per byte (c2: 4, c4: 3)")
     ap.add_argument("--level", type=int, default=2, help="0 none, 1 fast, 2 default, 3 best")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the untimed legs (host forms, real text)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: the cpu_baseline process and the oracle's parity samples, the "
+                         "profiled steps (roofline, kernels_ms_per_step, deflate_gib_s / inflate_gib_s), the untimed legs (c2) "
+                         "and the archive check (c4)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline process")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the untimed legs (host forms, real text)")
     ap.add_argument("--no-archive-check", action="store_true",
-                    help="c4: skip the untimed check of the whole archive (unzip -tq, zipfile, N-rank == 1-rank): counter passes only")
+                    help="with --full, c4: skip the untimed check of the whole archive (unzip -tq, zipfile, N-rank == 1-rank): counter passes only")
     ap.add_argument("--alone-pass", action="store_true",
-                    help="a second profiled pass with ONE slice: every kernel launched over the whole batch with nothing beside it "
-                         "(roofline.*.alone).  Off by default so that a rocprofv3 summary of the default command holds only the "
-                         "launches the timed region makes")
+                    help="with --full: a second profiled pass with ONE slice: every kernel launched over the whole batch with nothing "
+                         "beside it (roofline.*.alone).  Off by default so that a rocprofv3 summary of the --full command holds only "
+                         "the launches the timed and profiled steps make")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed for rank 0's streams to DIR/<name>.npy: every "
                          "stream's status, length, CRC-32 and byte sum (float64) and the bytes of a fixed, seeded sample of the "
                          "streams (float32), at most 64 MB in all -- for comparing two builds output for output")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)  # the cpu_baseline leg's own process
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.alone_pass and not args.full:
+        ap.error("--alone-pass is a pass of the profiled steps, which run with --full only")
+    return args
 
 
 # ---- the launcher (no torch, no GPU in this process) ------------------------------------------------
@@ -661,29 +675,33 @@ def run_c2(args, rank, local_rank, world, dev, cpu=None):
             "inflate_byte_sum": stream_byte_sums(out, idescs["dst_off"], ilast["out_len"]),
         }, {"deflate_bytes": (comp, descs["dst_off"], last["out_len"], cap), "inflate_bytes": (out, idescs["dst_off"], ilast["out_len"], L)})
 
-    psteps = max(1, min(args.steps, 3))
-    t = {"def": 0.0, "inf": 0.0}
+    if args.full:
+        psteps = max(1, min(args.steps, 3))
+        t = {"def": 0.0, "inf": 0.0}
 
-    def profiled():
-        a = time.perf_counter()
-        batch.deflate_batch(ctx, src, comp, d_descs, d_res, n, L, N, args.level, 1)
-        b = time.perf_counter()
-        batch.inflate_batch(ctx, comp, out, d_idescs, d_ires, n, L, 1)
-        t["def"] += b - a
-        t["inf"] += time.perf_counter() - b
+        def profiled():
+            a = time.perf_counter()
+            batch.deflate_batch(ctx, src, comp, d_descs, d_res, n, L, N, args.level, 1)
+            b = time.perf_counter()
+            batch.inflate_batch(ctx, comp, out, d_idescs, d_ires, n, L, 1)
+            t["def"] += b - a
+            t["inf"] += time.perf_counter() - b
 
-    roof, per_step = roofline_of(ctx, profiled, psteps, N, C, wall=t, alone_pass=args.alone_pass)
+        roof, per_step = roofline_of(ctx, profiled, psteps, N, C, wall=t, alone_pass=args.alone_pass)
     if rank != 0:
         return None
-    headline = headline_scalars(roof, N, C, N / GIB * psteps / t["def"], N / GIB * psteps / t["inf"])
-    roof.update(headline)
     line = {
         "metric": METRIC,
         "value": world * N / GIB * args.steps / elapsed,
         "unit": "GiB/s",
+    }
+    if args.full:
+        headline = headline_scalars(roof, N, C, N / GIB * psteps / t["def"], N / GIB * psteps / t["inf"])
+        roof.update(headline)
         # the two directions by themselves (one rank's, over the profiled steps): at the head of the line, where a cut tail keeps them
-        "deflate_gib_s": N / GIB * psteps / t["def"],
-        "inflate_gib_s": N / GIB * psteps / t["inf"],
+        line["deflate_gib_s"] = N / GIB * psteps / t["def"]
+        line["inflate_gib_s"] = N / GIB * psteps / t["inf"]
+    line.update({
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
@@ -700,15 +718,16 @@ def run_c2(args, rank, local_rank, world, dev, cpu=None):
             "streams_per_gpu": n, "stream_len": L, "level": args.level,
             "compressed_ratio": C / N, "parallelism": "member-shard x%d" % world,
             "sampled_bytes_equal_oracle": same,
-            **headline,
         },
         **ranks,
-        "roofline": roof,
-        "kernels_ms_per_step": per_step,
-    }
+    })
+    if args.full:
+        line["config"].update(headline)
+        line["roofline"] = roof
+        line["kernels_ms_per_step"] = per_step
     if dumped:
         line["dump_outputs"] = dumped
-    if world == 1 and not args.no_extra_legs:
+    if world == 1 and args.full and not args.no_extra_legs:
         line.update(extra_legs(ctx, dev, n, L, cpu))
     return line
 
@@ -1015,20 +1034,18 @@ def run_c4(args, rank, local_rank, world, dev, cpu=None):
             "deflate_status": res["status"], "deflate_out_len": res["out_len"], "deflate_crc32": res["checksum"],
             "deflate_byte_sum": stream_byte_sums(comp, descs["dst_off"], res["out_len"]),
         }, {"deflate_bytes": (comp, descs["dst_off"], res["out_len"], cap)})
-    check = None if args.no_archive_check else c4_check(ctx, dev, rank, world, parts, paths, records, comp, descs, L, bits, args.level)
+    if args.full:
+        check = None if args.no_archive_check else c4_check(ctx, dev, rank, world, parts, paths, records, comp, descs, L, bits, args.level)
+        t4 = {"def": 0.0, "inf": 0.0}
 
-    t4 = {"def": 0.0, "inf": 0.0}
+        def profiled4():
+            a = time.perf_counter()
+            batch.deflate_batch(ctx, src, comp, d_descs, d_res, n, L, N, args.level, 1)
+            t4["def"] += time.perf_counter() - a
 
-    def profiled4():
-        a = time.perf_counter()
-        batch.deflate_batch(ctx, src, comp, d_descs, d_res, n, L, N, args.level, 1)
-        t4["def"] += time.perf_counter() - a
-
-    roof, per_step = roofline_of(ctx, profiled4, 1, N, int(res["out_len"].sum()), wall=t4)
+        roof, per_step = roofline_of(ctx, profiled4, 1, N, int(res["out_len"].sum()), wall=t4)
     if rank != 0:
         return None
-    headline = headline_scalars(roof, N, int(res["out_len"].sum()), N / GIB / t4["def"])
-    roof.update(headline)
     line = {
         "metric": METRIC,
         "value": members * L / GIB * args.steps / elapsed,
@@ -1048,13 +1065,16 @@ def run_c4(args, rank, local_rank, world, dev, cpu=None):
                         % (members, L, bits, LEVELS[args.level], world),
             "members": members, "member_len": L, "level": args.level, "compressed_ratio": C_all / (members * L),
             "parallelism": "member-shard x%d" % world, "members_per_rank": counts,
-            **{k: v for k, v in headline.items()},  # rank 0's own shard (N = its members' bytes)
         },
         **ranks,
-        "roofline": roof,
-        "kernels_ms_per_step": per_step,
-        "archive_check": check,
     }
+    if args.full:
+        headline = headline_scalars(roof, N, int(res["out_len"].sum()), N / GIB / t4["def"])
+        roof.update(headline)
+        line["config"].update(headline)  # rank 0's own shard (N = its members' bytes)
+        line["roofline"] = roof
+        line["kernels_ms_per_step"] = per_step
+        line["archive_check"] = check
     if dumped:
         line["dump_outputs"] = dumped
     return line
@@ -1164,7 +1184,7 @@ def main(argv=None):
     if os.environ.get("ZIPC_BENCH_TEST_HANG_RANK") == str(rank):  # tests/test_bench_launch.py: a rank that never arrives
         time.sleep(3600)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         # the oracle on this host's cores, timed before this process touches the GPU (its worker pool forks)
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-only"] + argv,
                            stdout=subprocess.PIPE)

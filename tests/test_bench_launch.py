@@ -52,6 +52,32 @@ def test_gpus_must_agree_with_world_size():
     assert r.returncode == 2 and b"WORLD_SIZE=4" in r.stderr
 
 
+def test_a_plain_run_leaves_the_cpu_baseline_to_full(monkeypatch):
+    """a plain run starts no cpu_baseline process (most of a minute of host time the headline does not need); --full starts
+    it, with the same arguments, before anything touches the GPU; --alone-pass is refused without --full"""
+    import pytest
+    import torch
+
+    import bench
+
+    started = []
+
+    class Done:
+        returncode = 0
+        stdout = b'{"value": 1.0}\n'
+
+    monkeypatch.setattr(bench.subprocess, "run", lambda cmd, **kw: started.append(cmd) or Done())
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    assert bench.main(["--steps", "1", "--warmup", "0"]) == 3 and started == []
+    assert bench.main(["--full", "--steps", "1", "--warmup", "0"]) == 3
+    assert len(started) == 1 and started[0][2:] == ["--cpu-baseline-only", "--full", "--steps", "1", "--warmup", "0"]
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--alone-pass"])
+    assert bench.parse_args(["--full", "--alone-pass"]).alone_pass
+
+
 def test_cpu_baseline_leg_reports_one_thread_and_all_threads():
     import bench
 

@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/$TAG/c4
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 B="$ROOT/bench.py"
-ARGS="--config c4 --no-cpu-baseline --no-archive-check --steps 1 --warmup 1"
+ARGS="--full --config c4 --no-cpu-baseline --no-archive-check --steps 1 --warmup 1"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/pmcF" -o p --output-format csv -- python3 "$B" $ARGS > "$OUT/pmcF.log" 2>&1 || echo "FETCH_SIZE pass failed"
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/pmcW" -o p --output-format csv -- python3 "$B" $ARGS > "$OUT/pmcW.log" 2>&1 || echo "WRITE_SIZE pass failed"
 python3 "$ROOT/tools/pmc_report.py" "$OUT/pmc[FW]/*counter_collection.csv" --workload c4 --hbm-json "$ROOT/profiles/${TAG}_hbm_traffic_c4.json" && cp "$ROOT/profiles/${TAG}_hbm_traffic_c4.json" "$OUT/"
@@ -25,7 +25,7 @@ python3 "$ROOT/tools/pmc_report.py" "$OUT/sq*/*counter_collection.csv" --workloa
 python3 "$ROOT/tools/pmc_report.py" "$OUT/sq*/*counter_collection.csv" > "$OUT/sq_counters_c4.txt"
 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o t --output-format csv -- python3 "$B" $ARGS > "$OUT/trace_bench_c4.json" 2> "$OUT/trace.err" || echo "kernel-trace pass failed"
 cd "$ROOT"
-python3 "$B" --config c4 --steps 3 --warmup 1 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
+python3 "$B" --full --config c4 --steps 3 --warmup 1 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
 python3 -c "
 import json
 d=json.load(open('$OUT/bench_c4.json'))
