@@ -125,7 +125,7 @@ int zipc_hip_lds_exchange_ordered(zipc_hip_ctx *ctx);
  * the first batch fails that batch's streams with ZIPC_HIP_ERR_HIP and moves the context to the ordering kernel.
  * Synchronises the context's stream. */
 int zipc_hip_chain_check(zipc_hip_ctx *ctx, unsigned long long *compared, unsigned long long *differences);
-/* Measurements only: the number of slices the batch forms cut a call into (side queues, api.hip batch_slices), for
+/* Measurements only: the number of slices the batch forms cut a call into (side queues, forms.h batch_slices), for
  * every context of the process from now on; 0 = the default again (two slices of at least 2048 streams, or
  * ZIPC_HIP_SLICES).  bench.py times a kernel alone on the device with 1.  Results are the same for every value. */
 void zipc_hip_debug_set_slices(long k);

@@ -5,7 +5,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libhost_sim.so")
-SRCS = ["sim_inflate.cpp", "sim_deflate.cpp", "sim_chain.cpp"]
+SRCS = ["sim_inflate.cpp", "sim_deflate.cpp", "sim_chain.cpp", "sim_forms.cpp"]
 
 
 def lib():
@@ -36,4 +36,82 @@ def _bind(L):
     L.sim_chain.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]
     L.sim_chain_serial.restype = None
     L.sim_chain_serial.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p]
+    tun = C.POINTER(C.c_longlong)
+    L.sim_deflate_grouping.restype = None
+    L.sim_deflate_grouping.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, tun, C.POINTER(C.c_uint64)]
+    L.sim_deflate_scratch_bytes.restype = C.c_uint64
+    L.sim_deflate_scratch_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, tun]
+    L.sim_deflate_forms.restype = None
+    L.sim_deflate_forms.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, tun, C.c_int, C.c_uint64, C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64)]
+    L.sim_inflate_blocks_gate.restype = C.c_int
+    L.sim_inflate_blocks_gate.argtypes = [C.c_uint64, C.c_uint64]
+    L.sim_inflate_few_streams.restype = C.c_int
+    L.sim_inflate_few_streams.argtypes = [C.c_uint64]
+    L.sim_inflate_blocks_pick.restype = C.c_uint64
+    L.sim_inflate_blocks_pick.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32),
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     return L
+
+
+# ---- zipc_amd/csrc/forms.h through sim_forms.cpp: the launch rules as dicts of plain numbers
+FORMS_FIELDS = ("grid_too_large", "K", "slices", "tps", "cps", "tpg", "gps", "segmented", "segments_required", "segp", "sps", "bps",
+                "n_slots", "tiles", "seg_syms", "xchg_chain", "chain_seg", "csegs", "xseg", "xsegs")
+SLICE_FIELDS = ("chain", "chain_grid", "match_window", "match_grid", "gpw", "streams", "segments", "blocks", "ppb", "bits_grid",
+                "pack_grid", "seal_grid")
+CHAIN_XCHG, CHAIN_XCHG_SEGMENTS, CHAIN_PEEL, CHAIN_PEEL_SEGMENTS = 0, 1, 2, 3
+
+
+def _tun(parse_segments=-1, parse_seg=0, match_tiles_per_group=0, deflate_group_bytes=8 << 30, slices=0, slice_min=0,
+         slices_override=0, segments_ok=1):
+    """the Tuning fields the deflate rules read (their defaults: api.hip tuning()), the debug override of the slices, and
+    whether the parse scratch could be had"""
+    return (C.c_longlong * 8)(parse_segments, parse_seg, match_tiles_per_group, deflate_group_bytes, slices, slice_min,
+                              slices_override, segments_ok)
+
+
+def deflate_forms(L, n, max_src_len, total_src_len=None, level=2, xchg_ok=1, m=None, **tun):
+    """forms.h deflate_forms of a group, and deflate_slice_forms of a slice of m of its streams (default: the whole group)"""
+    out, sl = (C.c_uint64 * len(FORMS_FIELDS))(), (C.c_uint64 * len(SLICE_FIELDS))()
+    L.sim_deflate_forms(n, max_src_len, n * max_src_len if total_src_len is None else total_src_len, level, _tun(**tun), xchg_ok,
+                        n if m is None else m, out, sl)
+    return dict(zip(FORMS_FIELDS, out)), dict(zip(SLICE_FIELDS, sl))
+
+
+def deflate_grouping(L, n, max_src_len, total_src_len, **tun):
+    out = (C.c_uint64 * 2)()
+    L.sim_deflate_grouping(n, max_src_len, total_src_len, _tun(**tun), out)
+    return out[0], out[1]
+
+
+def deflate_scratch_bytes(L, n, max_src_len, total_src_len, level, **tun):
+    return L.sim_deflate_scratch_bytes(n, max_src_len, total_src_len, level, _tun(**tun))
+
+
+def inflate_blocks_pick(L, streams):
+    """streams: (src_len, dst_cap) pairs -> (the indices that go by blocks, the ends of their groups)"""
+    n = len(streams)
+    src, cap = (C.c_uint64 * n)(*[s for s, c in streams]), (C.c_uint64 * n)(*[c for s, c in streams])
+    picked, ends, ng = (C.c_uint32 * max(n, 1))(), (C.c_uint64 * max(n, 1))(), C.c_uint64()
+    k = L.sim_inflate_blocks_pick(src, cap, n, picked, ends, C.byref(ng))
+    return list(picked[:k]), list(ends[:ng.value])
+
+
+def deflate_kernel_names(L, n, max_src_len, crc_op=1, **kw):
+    """the names zipc_hip_kernel_times records for one zipc_hip_deflate_batch of n streams at a compressing level
+    (deflate.hip launch_deflate_group's ZD_LAUNCH lines, slice by slice)"""
+    f, _ = deflate_forms(L, n, max_src_len, **kw)
+    names = {"deflate_offsets", "lz_chain", "lz_match"}
+    if crc_op == 1:
+        names |= {"crc32_segments", "crc32_finish"}
+    k = f["slices"]
+    for i in range(k):
+        _, s = deflate_forms(L, n, max_src_len, m=n * (i + 1) // k - n * i // k, **kw)
+        if f["segmented"]:
+            names |= {"lz_parse_spec", "lz_parse_meet", "lz_parse_stitch", "lz_parse_gather", "deflate_plan", "deflate_counts",
+                      "deflate_codelen", "deflate_scan", "deflate_pack", "deflate_seal"}
+            if s["ppb"] != 1:
+                names.add("deflate_bits")
+        else:
+            names |= {"lz_parse", "deflate_emit"}
+    return names

@@ -879,6 +879,60 @@ def _launched(ctx):
     return names
 
 
+# (shape, kernels the issue's table names for it, kernels it rules out) at `Default with CRC-32: both sides of "few long
+# streams" (8 parse segments of 4096 positions; 2048 streams) and of deflate_bits (2048 block slots in a slice)
+FORM_SHAPES = [
+    ((4, 16 << 10), {"lz_parse", "deflate_emit"}, {"lz_parse_spec"}),
+    ((2, 40 << 10), {"lz_parse_spec", "lz_parse_meet", "lz_parse_stitch", "lz_parse_gather", "deflate_plan", "deflate_counts",
+                     "deflate_codelen", "deflate_scan", "deflate_bits", "deflate_pack", "deflate_seal"}, {"lz_parse", "deflate_emit"}),
+    ((2048, 32 << 10), {"lz_parse_spec", "deflate_plan", "deflate_pack", "deflate_seal"}, {"deflate_bits", "lz_parse", "deflate_emit"}),  # 2048 * 2 block slots
+    ((2049, 32 << 10), {"lz_parse", "deflate_emit"}, {"lz_parse_spec", "deflate_plan", "deflate_bits"}),
+]
+
+
+def test_the_kernels_launched_are_the_ones_the_forms_predict(gpu_ctx, oracle):
+    """zipc_amd/csrc/forms.h decides what launch_deflate_group launches: for each shape the names zipc_hip_kernel_times
+    saw are exactly what the g++ build of the same header predicts (tests/host_sim), and every output is the oracle's."""
+    import torch
+
+    import host_sim
+    from zipc_amd import batch, synth
+
+    sim = host_sim.lib()
+    dev = torch.device("cuda", 0)
+    want_of = {}  # a shape's streams are one stream's bytes n times: one oracle run per length
+    first = True
+    for (n, ln), need, never in FORM_SHAPES:
+        one = synth.stream_bytes_np(2, 5, ln, 4)
+        if ln not in want_of:
+            st0, c0, crc0 = oracle.deflate(one.tobytes(), level=2, crc_op=oracle.CRC_CRC32)
+            assert st0 == 0
+            want_of[ln] = (c0, crc0)
+        c0, crc0 = want_of[ln]
+        src = torch.from_numpy(one).to(dev).repeat(n)
+        descs = batch.uniform_layout(n, ln, batch.deflate_bound(ln))
+        slot = int(descs["dst_off"][1])
+        d_descs = batch.to_device(descs, dev)
+        for profiled in ((False, True) if first else (True,)):  # (a context's first batch also checks its chain links: not in the profile)
+            comp = torch.zeros(n * slot + 256, dtype=torch.uint8, device=dev)
+            d_res = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+            if profiled:
+                _profiled(gpu_ctx)
+            try:
+                batch.deflate_batch(gpu_ctx, src, comp, d_descs, d_res, n, ln, n * ln, 2, 1)
+            finally:
+                launched = _launched(gpu_ctx) if profiled else None
+        first = False
+        predicted = host_sim.deflate_kernel_names(sim, n, ln, level=2, crc_op=1, xchg_ok=int(gpu_ctx.lds_exchange_ordered()))
+        assert launched == predicted, (n, ln, sorted(launched), sorted(predicted))
+        assert need <= launched and not (never & launched), (n, ln, sorted(launched))
+        res = batch.results_from_device(d_res)
+        assert (res["status"] == 0).all() and (res["out_len"] == len(c0)).all() and (res["checksum"] == crc0).all(), (n, ln)
+        want = torch.from_numpy(np.frombuffer(c0, dtype=np.uint8).copy()).to(dev)
+        got = comp[:n * slot].view(n, slot)[:, :len(c0)]
+        assert bool((got == want).all()), (n, ln)
+
+
 def test_deflate_host_forms_equal_the_second_readings_vectors(gpu_ctx):
     import hashlib
 

@@ -593,3 +593,235 @@ def test_block_header_search_finds_the_dynamic_headers_around_the_rule_cases(sim
         assert len(starts) >= 4 and starts <= found, (name, sorted(starts - found))
         n += 1
     assert n >= 25
+
+
+# ---- the launch rules (zipc_amd/csrc/forms.h, tests/host_sim/sim_forms.cpp) ------------------------------------------
+# Every expected value below is written out by hand from the rules as launch_deflate_group and inflate_by_blocks stated
+# them before they moved into forms.h, with the arithmetic beside it; none is the output of the functions under test.
+#   tps  = 1 if L - 4 < 49152 else 2 + (L - 4 - 49152) // 16384      cps = ceil(L / 1024)
+#   tpg  = n * tps // 8192 within [1, tps]                           gps = ceil(tps / tpg)
+#   segp = 4096 / 8192 / 16384 for L <= 4 MiB / <= 32 MiB / longer, doubled while < 32768 and n * ceil(L / (2 segp)) >= 65536
+#   sps  = ceil(L / segp)      bps = L // 65277 + 2
+#   segmented = sps >= 8 and (n <= 2048 or (n <= 4096 and L >= 512 KiB) or (n <= 8192 and L >= 1 MiB))
+#   slices = 2, one less while n // slices < 2048
+import host_sim as H
+
+KIB, MIB, GIB = 1 << 10, 1 << 20, 1 << 30
+
+FORMS_ROWS = [
+    # (what, arguments of host_sim.deflate_forms, expected fields of the group, expected fields of the slice)
+    # --- the matcher: streams of up to 8192 bytes keep lz_match_kernel, cps = 8 tiles of 1024: grid 4 * 8 = 32
+    ("matcher 8192", dict(n=4, max_src_len=8192), dict(cps=8, segmented=0), dict(match_window=0, match_grid=32)),
+    # 8193: the window kernel; tps = 1, tpg = 4 * 1 // 8192 = 0 -> 1, gps = 1, gpw = 4 // 2048 = 0 -> 1, 4 workgroups -> 8
+    ("matcher 8193", dict(n=4, max_src_len=8193), dict(tps=1, tpg=1, gps=1), dict(match_window=1, gpw=1, match_grid=8)),
+    # --- lz_chain by exchange, by segments: n < 1024 and L > 192 KiB
+    ("xchg 1023 x 192 KiB", dict(n=1023, max_src_len=192 * KIB), dict(xseg=0, xsegs=1), dict(chain=H.CHAIN_XCHG, chain_grid=1023)),
+    # xseg = 98304: 1023 * ceil(196609 / 196608) = 2046 < 2048, no doubling; xsegs = ceil(196609 / 98304) = 3; grid 1023 * 3
+    ("xchg 1023 x 192 KiB + 1", dict(n=1023, max_src_len=192 * KIB + 1), dict(xseg=98304, xsegs=3),
+     dict(chain=H.CHAIN_XCHG_SEGMENTS, chain_grid=3069)),
+    ("xchg 1024 x 192 KiB + 1", dict(n=1024, max_src_len=192 * KIB + 1), dict(xseg=0, xsegs=1), dict(chain=H.CHAIN_XCHG, chain_grid=1024)),
+    # 1023 * ceil(393217 / 196608) = 1023 * 3 >= 2048: xseg doubles to 196608; 1023 * ceil(393217 / 393216) = 2046: stays; xsegs = 3
+    ("xchg doubling", dict(n=1023, max_src_len=384 * KIB + 1), dict(xseg=196608, xsegs=3), dict(chain=H.CHAIN_XCHG_SEGMENTS, chain_grid=3069)),
+    # --- sps 7 / 8 (segp 4096): 28672 = 7 * 4096
+    ("sps 7", dict(n=2, max_src_len=28672), dict(segp=4096, sps=7, segmented=0, n_slots=0, tiles=0, seg_syms=0),
+     dict(streams=2, segments=0, blocks=0, ppb=0)),
+    # sps 8: P = 2 * 28673 + 512 * 2 + 256 = 58626; n_slots = 58626 // 4096 + 2 + 1 = 17; tiles = 58626 // 64 + 4 = 920;
+    # seg_syms = 4096 + 576; bps = 0 + 2; slice of 2: 16 segments, 4 blocks <= 2048 -> ppb 8, bits = pack = 32, seal ceil(32 / 256)
+    ("sps 8", dict(n=2, max_src_len=28673), dict(segp=4096, sps=8, segmented=1, segments_required=0, bps=2, n_slots=17, tiles=920, seg_syms=4672),
+     dict(chain=H.CHAIN_XCHG, chain_grid=2, streams=2, segments=16, blocks=4, ppb=8, bits_grid=32, pack_grid=32, seal_grid=1)),
+    # ... the same without the exchange: chain_seg 32768 (2 * 1 <= 512), csegs = 1: the whole-stream peel kernel
+    ("sps 8 peel", dict(n=2, max_src_len=28673, xchg_ok=0), dict(xchg_chain=0, chain_seg=32768, csegs=1), dict(chain=H.CHAIN_PEEL, chain_grid=2)),
+    # ... and when the parse scratch could not be had: the forms by a wave per stream
+    ("sps 8, no scratch", dict(n=2, max_src_len=28673, segments_ok=0), dict(sps=8, segmented=0, n_slots=0), dict(segments=0, ppb=0)),
+    # --- n 2048 / 2049 at 32 KiB: sps = 8 (2048 * ceil(32768 / 8192) = 8192 < 65536: segp stays 4096); one slice (2048 // 2 < 2048)
+    # P = 2048 * 32768 + 512 * 2048 + 256 = 68157696; n_slots = 16640 + 2048 + 1; tiles = 1064964 + 4
+    # blocks = 2048 * 2 = 4096 > 2048: ppb 1, no deflate_bits, pack 4096, seal 4096 / 256 = 16
+    ("2048 x 32 KiB", dict(n=2048, max_src_len=32 * KIB), dict(slices=1, sps=8, segmented=1, bps=2, n_slots=18689, tiles=1064968),
+     dict(chain=H.CHAIN_XCHG, chain_grid=2048, gpw=1, match_grid=2048, segments=16384, blocks=4096, ppb=1, bits_grid=0, pack_grid=4096, seal_grid=16)),
+    ("2049 x 32 KiB", dict(n=2049, max_src_len=32 * KIB), dict(slices=1, sps=8, segmented=0), dict(streams=2049, segments=0)),
+    # --- n 4096 / 4097 at 512 KiB: 4096 * ceil(524288 / 8192, / 16384, / 32768) = 262144, 131072, 65536, all >= 65536:
+    # segp 32768, sps = 16; two slices
+    ("4096 x 512 KiB", dict(n=4096, max_src_len=512 * KIB), dict(slices=2, segp=32768, sps=16, segmented=1), {}),
+    ("4097 x 512 KiB", dict(n=4097, max_src_len=512 * KIB), dict(slices=2, segp=32768, sps=16, segmented=0), {}),
+    ("4096 x 512 KiB - 1", dict(n=4096, max_src_len=512 * KIB - 1), dict(segp=32768, sps=16, segmented=0), {}),
+    # --- n 8192 / 8193 at 1 MiB: segp 32768 the same way, sps = 32
+    ("8192 x 1 MiB", dict(n=8192, max_src_len=MIB), dict(segp=32768, sps=32, segmented=1), {}),
+    ("8193 x 1 MiB", dict(n=8193, max_src_len=MIB), dict(segp=32768, sps=32, segmented=0), {}),
+    ("8192 x 1 MiB - 1", dict(n=8192, max_src_len=MIB - 1), dict(segp=32768, sps=32, segmented=0), {}),
+    # --- the segp steps: 4 MiB / 4096 = 1024; (4 MiB + 1) / 8192 -> 513; 32 MiB / 8192 = 4096; (32 MiB + 1) / 16384 -> 2049
+    ("segp 4 MiB", dict(n=1, max_src_len=4 * MIB), dict(segp=4096, sps=1024), {}),
+    ("segp 4 MiB + 1", dict(n=1, max_src_len=4 * MIB + 1), dict(segp=8192, sps=513), {}),
+    ("segp 32 MiB", dict(n=1, max_src_len=32 * MIB), dict(segp=8192, sps=4096), {}),
+    ("segp 32 MiB + 1", dict(n=1, max_src_len=32 * MIB + 1), dict(segp=16384, sps=2049), {}),
+    # --- the doubling at 65536 waves: 64 KiB streams, ceil(65536 / 8192) = 8: 8191 * 8 = 65528, 8192 * 8 = 65536 (then 8192 * 4: stays)
+    ("65528 waves", dict(n=8191, max_src_len=64 * KIB), dict(segp=4096, sps=16, segmented=0), {}),
+    ("65536 waves", dict(n=8192, max_src_len=64 * KIB), dict(segp=8192, sps=8, segmented=0), {}),
+    # --- the peel kernel by segments: segmented, csegs > 1, m <= 128.  1 MiB: 128 * 32 > 512, 128 * 16 > 1024: chain_seg 131072, csegs 8
+    ("peel m 128", dict(n=128, max_src_len=MIB, xchg_ok=0), dict(segmented=1, sps=256, chain_seg=131072, csegs=8),
+     dict(chain=H.CHAIN_PEEL_SEGMENTS, chain_grid=1024)),
+    ("peel m 129", dict(n=129, max_src_len=MIB, xchg_ok=0), dict(segmented=1, chain_seg=131072, csegs=8), dict(chain=H.CHAIN_PEEL, chain_grid=129)),
+    # chain_seg: 16 * 32 = 512 <= 512: 32768; 17 * 32 > 512, 17 * 16 <= 1024: 65536; 64 * 16 = 1024: 65536; 65 * 16 > 1024: 131072
+    ("chain_seg 16", dict(n=16, max_src_len=MIB, xchg_ok=0), dict(chain_seg=32768, csegs=32), dict(chain=H.CHAIN_PEEL_SEGMENTS, chain_grid=512)),
+    ("chain_seg 17", dict(n=17, max_src_len=MIB, xchg_ok=0), dict(chain_seg=65536, csegs=16), dict(chain_grid=272)),
+    ("chain_seg 64", dict(n=64, max_src_len=MIB, xchg_ok=0), dict(chain_seg=65536, csegs=16), dict(chain_grid=1024)),
+    ("chain_seg 65", dict(n=65, max_src_len=MIB, xchg_ok=0), dict(chain_seg=131072, csegs=8), dict(chain_grid=520)),
+    # --- ppb: m * bps 2048 / 2049.  32 KiB: bps 2, 1024 * 2 = 2048 -> 8 parts: bits = pack = 16384, seal 64; 1025 * 2 = 2050 -> 1
+    ("ppb 2048", dict(n=1024, max_src_len=32 * KIB), dict(segmented=1, bps=2), dict(blocks=2048, ppb=8, bits_grid=16384, pack_grid=16384, seal_grid=64)),
+    ("ppb 2050", dict(n=1025, max_src_len=32 * KIB), dict(segmented=1, bps=2), dict(blocks=2050, ppb=1, bits_grid=0, pack_grid=2050, seal_grid=9)),
+    # 64 KiB: bps = 65536 // 65277 + 2 = 3: 682 * 3 = 2046 -> 8 parts, 16368 waves, seal ceil(16368 / 256) = 64; 683 * 3 = 2049 -> 1, seal 9
+    ("ppb 2046", dict(n=682, max_src_len=64 * KIB), dict(segmented=1, bps=3), dict(blocks=2046, ppb=8, bits_grid=16368, pack_grid=16368, seal_grid=64)),
+    ("ppb 2049", dict(n=683, max_src_len=64 * KIB), dict(segmented=1, bps=3), dict(blocks=2049, ppb=1, bits_grid=0, pack_grid=2049, seal_grid=9)),
+    # --- gpw.  64 KiB: tps = 2 + (65532 - 49152) // 16384 = 2; tpg = 4096 * 2 // 8192 = 1; gps = 2; a slice of 2048:
+    # gpw = 2048 * 2 // 2048 = 2, ceil(4096 / 2) = 2048 workgroups; `Best (K = 4096 >= 1024): gpw 1, 4096 workgroups
+    ("gpw default", dict(n=4096, max_src_len=64 * KIB, m=2048), dict(K=128, slices=2, tps=2, tpg=1, gps=2), dict(gpw=2, match_grid=2048)),
+    ("gpw best", dict(n=4096, max_src_len=64 * KIB, m=2048, level=3), dict(K=4096, tps=2, tpg=1, gps=2), dict(gpw=1, match_grid=4096)),
+    ("gpw fast", dict(n=4096, max_src_len=64 * KIB, m=2048, level=1), dict(K=4), dict(gpw=2, match_grid=2048)),
+    # 256 KiB: tps = 2 + (262140 - 49152) // 16384 = 14; tpg = 4096 * 14 // 8192 = 7, gps 2; 8192 streams: tpg 14, gps 1
+    ("tpg 7", dict(n=4096, max_src_len=256 * KIB), dict(tps=14, tpg=7, gps=2), {}),
+    ("tpg 14", dict(n=8192, max_src_len=256 * KIB), dict(tps=14, tpg=14, gps=1), {}),
+    # match_tiles_per_group = 1: gps 14; a slice of 2048: gpw = 14 -> 8 at most; ceil(2048 * 14 / 8) = 3584 workgroups
+    ("tpg override", dict(n=4096, max_src_len=256 * KIB, m=2048, match_tiles_per_group=1), dict(tps=14, tpg=1, gps=14), dict(gpw=8, match_grid=3584)),
+    ("tpg override beyond tps", dict(n=4, max_src_len=256 * KIB, match_tiles_per_group=99), dict(tps=14, tpg=14, gps=1), {}),
+    # --- slices: 4095 // 2 < 2048
+    ("slices 4095", dict(n=4095, max_src_len=100), dict(slices=1), {}),
+    ("slices 4096", dict(n=4096, max_src_len=100), dict(slices=2), {}),
+    # slices = 4: 8192 // 4 = 2048; 8191 // 4 = 2047 -> 3 (8191 // 3 = 2730); at most 8; slice_min = 8: 32 // 4 = 8, 31 // 4 = 7 -> 3
+    ("slices env 4", dict(n=8192, max_src_len=100, slices=4), dict(slices=4), {}),
+    ("slices env 4, short", dict(n=8191, max_src_len=100, slices=4), dict(slices=3), {}),
+    ("slices env 100", dict(n=16384, max_src_len=100, slices=100), dict(slices=8), {}),
+    ("slice_min 8", dict(n=32, max_src_len=100, slices=4, slice_min=8), dict(slices=4), {}),
+    ("slice_min 8, short", dict(n=31, max_src_len=100, slices=4, slice_min=8), dict(slices=3), {}),
+    ("slices override", dict(n=8192, max_src_len=100, slices=4, slices_override=1), dict(slices=1), {}),
+    # --- parse_segments 0 / 1, parse_seg
+    ("segments never", dict(n=2, max_src_len=28673, parse_segments=0), dict(sps=8, segmented=0, segments_required=0), {}),
+    ("segments always, 2 segments", dict(n=5000, max_src_len=4097, parse_segments=1), dict(sps=2, segmented=1, segments_required=1), {}),
+    ("segments always, 1 segment", dict(n=5000, max_src_len=4096, parse_segments=1), dict(sps=1, segmented=0, segments_required=1), {}),
+    ("parse_seg 8192", dict(n=2, max_src_len=28673, parse_seg=8192), dict(segp=8192, sps=4, segmented=0), {}),
+    ("parse_seg below the least", dict(n=2, max_src_len=28673, parse_seg=4032), dict(segp=4096, sps=8), {}),
+    ("parse_seg no multiple of 64", dict(n=2, max_src_len=28673, parse_seg=8200), dict(segp=4096, sps=8), {}),
+    ("parse_seg 1 Mi", dict(n=2, max_src_len=4 * MIB, parse_seg=1 << 20), dict(segp=1 << 20, sps=4), {}),
+    ("parse_seg beyond 1 Mi", dict(n=2, max_src_len=4 * MIB, parse_seg=(1 << 20) + 64), dict(segp=4096, sps=1024), {}),
+    ("parse_seg and segments always", dict(n=3, max_src_len=8193, parse_segments=1, parse_seg=4096), dict(segp=4096, sps=3, segmented=1, seg_syms=4672), {}),
+    # --- the grid guards.  lz_match's fails the call: the longest stream, tps = 2 + (0xFFFF0000 - 4 - 49152) // 16384 = 262138;
+    # 8192 * 262138 = 2147434496 <= 2^31 - 1 < 8193 * 262138; 8 chunks of the short matcher: 268435455 * 8 = 2^31 - 8
+    ("match grid fits", dict(n=8192, max_src_len=0xFFFF0000, total_src_len=1 << 40, parse_segments=0), dict(tps=262138, grid_too_large=0), {}),
+    ("match grid too large", dict(n=8193, max_src_len=0xFFFF0000, total_src_len=1 << 40, parse_segments=0), dict(tps=262138, grid_too_large=1), {}),
+    ("short match grid fits", dict(n=268435455, max_src_len=8192, total_src_len=1 << 40), dict(cps=8, grid_too_large=0), {}),
+    ("short match grid too large", dict(n=268435456, max_src_len=8192, total_src_len=1 << 40), dict(cps=8, grid_too_large=1), {}),
+    # the segmented forms' only turn them off.  1 MiB in segments of 4096: sps 256, bps = 16 + 2: 8388607 * 256 = 2^31 - 256;
+    # 8388608 * 256 = 2^31 (n * bps * 8 = 144 n stays below)
+    ("segment grid fits", dict(n=8388607, max_src_len=MIB, parse_segments=1, parse_seg=4096), dict(sps=256, bps=18, segmented=1, grid_too_large=0), {}),
+    ("segment grid too large", dict(n=8388608, max_src_len=MIB, parse_segments=1, parse_seg=4096), dict(sps=256, segmented=0, grid_too_large=0), {}),
+    # 16 MiB in segments of 1 Mi: sps 16, bps = 257 + 2: 1000000 * 259 * 8 = 2072000000 fits, 1048576 * 259 * 8 = 2172649472 does not
+    ("block grid fits", dict(n=1000000, max_src_len=16 * MIB, parse_segments=1, parse_seg=1 << 20), dict(sps=16, bps=259, segmented=1, grid_too_large=0), {}),
+    ("block grid too large", dict(n=1048576, max_src_len=16 * MIB, parse_segments=1, parse_seg=1 << 20), dict(sps=16, bps=259, segmented=0, grid_too_large=0), {}),
+    # --- the edges of the helpers: no stream, streams too short for a match
+    ("empty streams", dict(n=3, max_src_len=0), dict(tps=1, cps=1, sps=0, bps=2, segmented=0, csegs=0), dict(match_window=0, match_grid=8, chain_grid=3)),
+    ("3 bytes", dict(n=3, max_src_len=3), dict(tps=1, cps=1, sps=1), {}),
+]
+
+
+@pytest.mark.parametrize("row", FORMS_ROWS, ids=[r[0] for r in FORMS_ROWS])
+def test_deflate_forms_equal_the_hand_written_rows(sim, row):
+    what, args, group, sl = row
+    f, s = H.deflate_forms(sim, **args)
+    assert {k: f[k] for k in group} == group, (what, f)
+    assert {k: s[k] for k in sl} == sl, (what, s)
+
+
+def test_deflate_grouping_past_the_group_bytes(sim):
+    # (n, max_src_len, total, group bytes) -> (streams per group, bytes a group holds at most)
+    rows = [
+        ((8192, MIB, 8 * GIB, 8 * GIB), (8192, 8 * GIB)),          # not MORE than a group's bytes: one group
+        ((8193, MIB, 8193 * MIB, 8 * GIB), (8192, 8 * GIB)),       # 8 GiB // 1 MiB streams, 8192 * 1 MiB < the total
+        ((10, 300, 1000, 1000), (10, 1000)),
+        ((10, 300, 1001, 1000), (3, 900)),                         # 1000 // 300 = 3 streams, 3 * 300 = 900 < 1001
+        ((10, 300, 2500, 1000), (3, 900)),
+        ((10, 300, 2500, 100), (1, 300)),                          # 100 // 300 = 0: a stream to a group at least
+        ((2, 300, 450, 400), (1, 300)),
+        ((10, 300, 2500, 5000), (10, 2500)),
+        ((1, 5000, 5000, 1000), (1, 5000)),                        # one stream is never cut
+        ((10, 0, 2500, 1000), (10, 2500)),                         # nothing declared to divide by
+        ((4, 600, 2400, 2399), (3, 1800)),                         # 2399 // 600 = 3
+    ]
+    for (n, L, total, gb), want in rows:
+        assert H.deflate_grouping(sim, n, L, total, deflate_group_bytes=gb) == want, (n, L, total, gb)
+
+
+def _scratch_bytes_as_it_was(n_all, max_src_len, total_all, level, group_bytes=8 * GIB):
+    """deflate_scratch_bytes as deflate.hip summed it before the layout became one carve function: the independent reading"""
+    n, total = n_all, total_all
+    if total_all > group_bytes and max_src_len > 0 and n_all > 1:
+        n = max(1, min(group_bytes // max_src_len, n_all))
+        total = min(n * max_src_len, total_all)
+    P = total + (256 + 256) * n + 256
+    Bk = total // 65277 + 2 * n + 16
+    up = lambda v: (v + 255) // 256 * 256
+    b = up(n * 8) * 2 + up(n * 4) * 2 + 256
+    if level != 0:
+        b += up(P * 2) + 2 * up(P * 4) + up(P * 4)
+        b += up(Bk * 16)
+    return b + 1024
+
+
+def test_deflate_scratch_bytes_equal_the_sums_they_were(sim):
+    rows = [(1, 0, 0, 2), (1, 1, 1, 1), (1, 100, 100, 2), (1, 1 << 19, 1 << 19, 2), (3, 70001, 150003, 3), (64, 65536, 64 * 65536, 2),
+            (64, 65536, 64 * 65536, 0), (1, 100, 100, 0), (33, 777, 20000, 0), (4096, 32768, 4096 * 32768, 3), (8192, MIB, 8 * GIB, 2),
+            (8193, MIB, 8193 * MIB, 2), (8193, MIB, 8193 * MIB, 0), (20000, MIB, 9 * GIB, 1)]
+    for n, L, total, level in rows:
+        assert H.deflate_scratch_bytes(sim, n, L, total, level) == _scratch_bytes_as_it_was(n, L, total, level), (n, L, total, level)
+    for n, L, total, level, gb in [(10, 300, 2500, 2, 1000), (10, 300, 2500, 0, 1000), (10, 300, 2500, 3, 100), (7, 70000, 400000, 2, 200000)]:
+        assert H.deflate_scratch_bytes(sim, n, L, total, level, deflate_group_bytes=gb) == _scratch_bytes_as_it_was(n, L, total, level, gb), (n, L, total, level, gb)
+    # one value by hand: one stream of 100 bytes at `Default: P = 100 + 512 + 256 = 868, Bk = 0 + 2 + 16 = 18;
+    # 4 * 256 + 256 | 1792 + 3 * 3584 | 512 | + 1024
+    assert H.deflate_scratch_bytes(sim, 1, 100, 100, 2) == 1280 + 1792 + 10752 + 512 + 1024
+
+
+def test_inflate_gates_at_their_thresholds(sim):
+    # one stream: from BLOCKS_MIN_SRC = 40 KiB of capacity; a batch: from BLOCKS_BATCH_MIN_DST = 256 KiB; at most
+    # MAX_STREAM_LEN = 0xFFFF0000 of capacity and BLOCKS_MAX_STREAMS = 2^20 streams
+    rows = [((1, 40 * KIB), 1), ((1, 40 * KIB - 1), 0), ((2, 256 * KIB), 1), ((2, 256 * KIB - 1), 0), ((2, 40 * KIB), 0),
+            ((1, 0xFFFF0000), 1), ((1, 0xFFFF0001), 0), ((64, 0xFFFF0001), 0), ((1 << 20, 256 * KIB), 1), (((1 << 20) + 1, 256 * KIB), 0)]
+    for (n, cap), want in rows:
+        assert sim.sim_inflate_blocks_gate(n, cap) == want, (n, cap)
+    assert [sim.sim_inflate_few_streams(n) for n in (1, 256, 257, 4096)] == [1, 1, 0, 0]
+
+
+def test_inflate_streams_picked_for_the_block_path(sim):
+    """ms = (1 + 0.09 per MiB taken, if any is taken) + 15 per MiB of the longest stream left to its one wave"""
+    half = 512 * KIB
+    # 64 x 1 MiB: none 15 ms, all 1 + 64 * 0.09 = 6.76 ms, any k between 1 + 0.09 k + 15: every stream, one group (64 * 12 MiB)
+    assert H.inflate_blocks_pick(sim, [(half, MIB)] * 64) == (list(range(64)), [64])
+    # 4096 x 1 MiB: none 15 ms, all 1 + 4096 * 0.09 = 369.64 ms: none
+    assert H.inflate_blocks_pick(sim, [(half, MIB)] * 4096) == ([], [])
+    # 1000 members below BLOCKS_MIN_SRC of input (64 KiB of output) and two of 8 MiB: none 8 * 15 = 120 ms, the longer one
+    # 1 + 0.72 + 120, both 1 + 16 * 0.09 + 15 / 16 = 3.38 ms
+    members = [(20000, 64 * KIB)] * 1002
+    members[500] = members[1001] = (4 * MIB, 8 * MIB)
+    assert H.inflate_blocks_pick(sim, members) == ([500, 1001], [2])
+    # runs: output beyond 64 x the input never goes by blocks (4194368 // 64 = 65537 > 65536); at 64 x it does (1.36 ms against 60)
+    assert H.inflate_blocks_pick(sim, [(65536, 64 * 65536 + 64)]) == ([], [])
+    assert H.inflate_blocks_pick(sim, [(65536, 64 * 65536 + 63)]) == ([0], [1])
+    # what the block path takes at all: 40 KiB .. 0x1FFFFFFF bytes of input, 8 .. 0xFFFF0000 bytes of capacity
+    assert H.inflate_blocks_pick(sim, [(40 * KIB - 1, MIB)]) == ([], [])
+    assert H.inflate_blocks_pick(sim, [(40 * KIB, MIB)]) == ([0], [1])
+    assert H.inflate_blocks_pick(sim, [(0x1FFFFFFF, 0x20000000)]) == ([0], [1])
+    assert H.inflate_blocks_pick(sim, [(0x20000000, 0x20000000)]) == ([], [])
+    assert H.inflate_blocks_pick(sim, [(1 << 28, 0xFFFF0000)]) == ([0], [1])
+    assert H.inflate_blocks_pick(sim, [(1 << 28, 0xFFFF0001)]) == ([], [])
+    # a long stream among equal ones that stay: 3000 x 1 MiB and one of 64 MiB: none 960 ms, the long one 1 + 5.76 + 15 = 21.76,
+    # one more 1 + 5.85 + 15
+    many = [(half, MIB)] * 3001
+    many[7] = (32 * MIB, 64 * MIB)
+    assert H.inflate_blocks_pick(sim, many) == ([7], [1])
+
+
+def test_inflate_groups_cut_at_the_token_budget(sim):
+    # 12 bytes of scratch per byte of capacity, 1 GiB to a group: 32 MiB members are 384 MiB each, two to a group
+    # (all five picked: 1 + 160 * 0.09 = 15.4 ms against 480)
+    assert H.inflate_blocks_pick(sim, [(16 * MIB, 32 * MIB)] * 5) == ([0, 1, 2, 3, 4], [2, 4, 5])
+    # 2 * 12 * 44739242 = 2^30 - 16 fits, 2 * 12 * 44739243 = 2^30 + 8 does not
+    assert H.inflate_blocks_pick(sim, [(16 * MIB, 44739242)] * 3) == ([0, 1, 2], [2, 3])
+    assert H.inflate_blocks_pick(sim, [(16 * MIB, 44739243)] * 3) == ([0, 1, 2], [1, 2, 3])
+    # a member beyond the budget has a group to itself: 128 MiB is 1.5 GiB of scratch
+    assert H.inflate_blocks_pick(sim, [(64 * MIB, 128 * MIB), (512 * KIB, MIB), (64 * MIB, 128 * MIB)]) == ([0, 1, 2], [1, 2, 3])

@@ -84,15 +84,17 @@ def test_oracle_under_address_sanitizer():
 
 
 def test_kernel_host_models_under_address_sanitizer():
-    """inflate_lane.h / inflate_span.h / deflate_lane.h as the host compiles them, on the fast cases of their own module"""
-    srcs = [os.path.join(SIM, s) for s in ("sim_inflate.cpp", "sim_deflate.cpp", "sim_chain.cpp")]
+    """inflate_lane.h / inflate_span.h / deflate_lane.h / forms.h as the host compiles them, on the fast cases of their own module"""
+    from host_sim import SRCS
+
+    srcs = [os.path.join(SIM, s) for s in SRCS]
     csrc = os.path.join(ROOT, "zipc_amd", "csrc")
     deps = srcs + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")] + [os.path.join(SIM, f) for f in os.listdir(SIM) if f.endswith(".h")]
     out = os.path.join(BUILD, "libhost_sim_asan.so")
     _build(out, ["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
                  "-fno-sanitize-recover=undefined", "-I", SIM, "-o", out] + srcs, deps)
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "asan"])
-    fast = "golden_streams or accept_reject or lane_logic_fuzz or header_fuzz or wide_turn or header_search or crc_combination or two_queues or chain_round or segments_model_bytes_equal_oracle-64"
+    fast = "golden_streams or accept_reject or lane_logic_fuzz or header_fuzz or wide_turn or header_search or crc_combination or two_queues or chain_round or segments_model_bytes_equal_oracle-64 or deflate_forms or deflate_grouping or scratch_bytes or inflate_gates or picked_for or token_budget"
     out = _pytest_under_asan({"ZD_HOST_SIM_LIB": out, "ZD_ORACLE_LIB": os.path.join(ROOT, "oracle", "libzd_oracle_asan.so")},
                              ["tests/test_host_sim.py", "-k", fast])
     assert " passed" in out

@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 #include "ctx.h"
+#include "deflate_scratch.h"
 #include "host_pipeline.h"
 #include "tuning.h"
 
@@ -235,17 +236,7 @@ const Tuning &tuning() {
   return t;
 }
 static long g_slices_override = 0;  // zipc_hip_debug_set_slices: measurements that want every kernel alone on the device
-size_t batch_slices(size_t n_streams) {
-  // Two slices by default (each of at least 2048 streams): since lz_chain is four waves per CU (round 4) the second
-  // slice's chain links are made beside the first one's parse and blocks -- C2 deflate 13.25 -> 12.67 ms, the step
-  // 16.97 -> 16.34; text the same either way; 3 / 4 / 6 slices lose 7 / 3 / 8 % (one box, tools/exp_wall.py).
-  const long env = g_slices_override > 0 ? g_slices_override : tuning().slices, env_min = tuning().slice_min;
-  size_t k = env > 0 ? (size_t)env : 2;
-  if (k > 8) k = 8;
-  const size_t least = env_min > 0 ? (size_t)env_min : 2048;
-  while (k > 1 && n_streams / k < least) k--;
-  return k;
-}
+long debug_slices_override() { return g_slices_override; }
 size_t crc32_segs(size_t max_len) {
   const size_t segs = (max_len + CRC_SEG_BYTES - 1) / CRC_SEG_BYTES;
   return segs ? segs : 1;
@@ -575,16 +566,7 @@ static int inflate_huge_stream(zipc_hip_ctx *ctx, const void *d_src_arena, void 
 // that is not a chain of dynamic blocks behind its first block, anything the dry run or the chain did not like: the
 // one-wave kernel owns the reference's messages.  It SYNCHRONISES the context's stream.  ZIPC_HIP_INFLATE_BLOCKS=0
 // turns it off.
-constexpr size_t BLOCKS_MIN_SRC = 40u << 10, BLOCKS_MAX_SRC = 0x1FFFFFFFull;  // (bit offsets are 32-bit words here)
-constexpr uint32_t BLOCKS_CAND_CAP = 65536, BLOCKS_REC_CAP = 262144;
-// (a call whose descriptors are worth reading back: its longest stream alone is 4 ms of one wave.  Round 4 began with
-// 1 MiB here and 96 KiB of input above: 64 x 512 KiB of text 8.5 -> 4.0 ms, 64 x 256 KiB 4.3 -> 2.6, one stream of
-// 256 KiB 3.8 -> 1.3, of 128 KiB 2.0 -> 1.2; the block path's own floor is a good millisecond)
-constexpr size_t BLOCKS_BATCH_MIN_DST = 256u << 10, BLOCKS_MAX_STREAMS = 1u << 20;
-// tok[] and the two lists: 12 bytes of scratch per output byte.  Streams share a group while their capacities fit
-// this much of it (a stream that needs more has a group to itself, and its scratch goes back afterwards)
-constexpr size_t BLOCKS_TOK_BUDGET = (size_t)1 << 30;
-
+// (the BLOCKS_* limits, which streams go that way and in which groups: forms.h)
 static int inflate_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, uint8_t *dst, const StreamDesc *dd, StreamResult *d_results,
                                 const StreamDesc *sds, const uint32_t *streams, size_t nj, int crc_op, uint8_t *handled) {
   const uint64_t EXPLORE_STRIDE = zd::tuning().explore_stride;  // bytes of input between two explorers
@@ -828,64 +810,14 @@ static int inflate_by_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, void *d
     HIP_TRY(ctx, hipMemcpyAsync(sds.data(), d_descs, n_streams * sizeof(StreamDesc), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
-  std::vector<uint32_t> group;
-  size_t group_cap = 0;
-  auto run = [&]() -> int {
-    if (group.empty()) return ZIPC_HIP_OK;
+  const std::vector<uint32_t> picked = inflate_blocks_pick(sds.data(), n_streams);
+  size_t begin = 0;
+  for (size_t end : inflate_blocks_groups(sds.data(), picked)) {
     const int st = inflate_blocks_group(ctx, (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs,
-                                        (StreamResult *)d_results, sds.data(), group.data(), group.size(), crc_op, handled.data());
-    group.clear();
-    group_cap = 0;
-    return st;
-  };
-  std::vector<uint32_t> fit;  // the streams the block path takes at all
-  for (size_t i = 0; i < n_streams; i++) {
-    const StreamDesc &sd = sds[i];
-    if (sd.src_len < BLOCKS_MIN_SRC || sd.src_len > BLOCKS_MAX_SRC || sd.dst_cap < 8 || sd.dst_cap > MAX_STREAM_LEN) continue;
-    // Runs (zeros, short periods: output beyond 64 x the input) are not for this path: a word of tok[] per byte of a
-    // run costs more than the run (16 MiB of zeros as zlib codes them, 4 blocks: token run 10-11 ms, the one wave
-    // 3.4-6.9), and where the reference's encoder has coded them with the fixed code, the explorers' walks never fall
-    // into step with a bit stream that has a period (64 MiB: the chain walks nearly every block itself, 65 ms).
-    if (sd.dst_cap / 64 > sd.src_len) continue;
-    fit.push_back((uint32_t)i);
+                                        (StreamResult *)d_results, sds.data(), picked.data() + begin, end - begin, crc_op, handled.data());
+    if (st) return st;
+    begin = end;
   }
-  // Which of them go by blocks: the one waves of a call run side by side, and a call of thousands of streams fills
-  // the device with them -- its time is the longest stream's, about 15 ms per MiB of output -- while the block path
-  // takes the streams' bytes one after the other, about 0.09 ms per MiB and 1 ms for a group's launches and
-  // read-backs (64 x 1 MiB: 5.0 ms against 17; 4096 x 1 MiB: 370 ms against 16).  So the k longest streams go by
-  // blocks, with the k that makes the sum of both parts smallest: all of a few long streams, the few long members
-  // among an archive's many short ones, none of thousands of equal ones.
-  {
-    constexpr double WAVE_MS_PER_MIB = 15.0, BLOCKS_MS_PER_MIB = 0.09, BLOCKS_MS_FIXED = 1.0, MIB = 1048576.0;
-    std::sort(fit.begin(), fit.end(), [&](uint32_t x, uint32_t y) { return sds[x].dst_cap != sds[y].dst_cap ? sds[x].dst_cap > sds[y].dst_cap : x < y; });
-    uint64_t longest_other = 0;  // (of the streams the block path does not take)
-    {
-      std::vector<uint8_t> in_fit(n_streams, 0);
-      for (uint32_t i : fit) in_fit[i] = 1;
-      for (size_t i = 0; i < n_streams; i++)
-        if (!in_fit[i] && sds[i].dst_cap > longest_other) longest_other = sds[i].dst_cap;
-    }
-    size_t best_k = 0;
-    double best_ms = 0, taken_mib = 0;
-    for (size_t k = 0; k <= fit.size(); k++) {
-      const uint64_t longest_left = k < fit.size() ? (sds[fit[k]].dst_cap > longest_other ? sds[fit[k]].dst_cap : longest_other) : longest_other;
-      const bool any_left = k < n_streams;
-      const double ms = (k ? BLOCKS_MS_FIXED + taken_mib * BLOCKS_MS_PER_MIB : 0.0) + (any_left ? (double)longest_left / MIB * WAVE_MS_PER_MIB : 0.0);
-      if (k == 0 || ms < best_ms) { best_ms = ms; best_k = k; }
-      if (k < fit.size()) taken_mib += (double)sds[fit[k]].dst_cap / MIB;
-    }
-    fit.resize(best_k);
-    std::sort(fit.begin(), fit.end());
-  }
-  for (uint32_t i : fit) {
-    // (what a stream may produce: its capacity; the group's share of tok[] is sized by what the chains then say)
-    const size_t may = (size_t)sds[i].dst_cap * 12;
-    if (!group.empty() && group_cap + may > BLOCKS_TOK_BUDGET) { const int st = run(); if (st) return st; }
-    group.push_back(i);
-    group_cap += may;
-  }
-  const int st = run();
-  if (st) return st;
   for (size_t i = 0; i < n_streams; i++) *n_handled += handled[i];
   return ZIPC_HIP_OK;
 }
@@ -913,10 +845,7 @@ static int inflate_batch_impl(zipc_hip_ctx *ctx, const void *d_src_arena, void *
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (n_streams == 1 && max_dst_cap > MAX_STREAM_LEN)
     return inflate_huge_stream(ctx, d_src_arena, d_dst_arena, d_descs, d_results, crc_op);
-  // one long stream, or a call of long streams (an archive's big members): by blocks, side by side -- their one
-  // waves take 10-17 ms per MiB of the longest
-  if (max_dst_cap <= MAX_STREAM_LEN && n_streams <= BLOCKS_MAX_STREAMS &&
-      max_dst_cap >= (n_streams == 1 ? BLOCKS_MIN_SRC : BLOCKS_BATCH_MIN_DST)) {
+  if (inflate_blocks_gate(n_streams, max_dst_cap)) {
     std::vector<StreamDesc> sds;
     std::vector<uint8_t> handled;
     size_t n_handled = 0;
@@ -948,15 +877,15 @@ static int inflate_batch_impl(zipc_hip_ctx *ctx, const void *d_src_arena, void *
 static int inflate_batch_one_wave(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
                                   zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op, bool marked) {
   const int k_crc_op = crc_op | (marked ? CRC_OP_MARKED : 0);  // what the kernels are told (inflate.hip inflate_skips_stream)
-  // one wave per stream (ZIPC_HIP_SLICES > 1: in slices on queues of their own, the CRC pass of one slice
-  // beside the inflate kernel of the next; measured, not the default: deflate.hip)
+  // one wave per stream (in slices on queues of their own, the CRC pass of one slice beside the inflate kernel of
+  // the next: two by default, forms.h batch_slices)
   HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_streams * INFLATE_SCRATCH_PER_STREAM));
   const size_t segs = crc32_segs(max_dst_cap);
   if (crc_op == ZIPC_HIP_CRC_CRC32) {
     if (n_streams * segs > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
     HIP_TRY(ctx, ctx->ensure(ctx->crc_partials, n_streams * segs * sizeof(uint32_t)));
   }
-  const size_t k = crc_op == ZIPC_HIP_CRC_CRC32 ? batch_slices(n_streams) : 1;
+  const size_t k = crc_op == ZIPC_HIP_CRC_CRC32 ? batch_slices(n_streams, zd::tuning(), debug_slices_override()) : 1;
   if (k > 1) HIP_TRY(ctx, ctx->fork(k));
   int st = ZIPC_HIP_OK;
   for (size_t i = 0; i < k && st == ZIPC_HIP_OK; i++) {
@@ -964,7 +893,7 @@ static int inflate_batch_one_wave(zipc_hip_ctx *ctx, const void *d_src_arena, vo
     if (k > 1) ctx->use_slice_stream(i);
     const StreamDesc *dd = (const StreamDesc *)d_descs + lo;
     StreamResult *dr = (StreamResult *)d_results + lo;
-    if (n_streams <= 256)  // (a few streams: the form that shares the tables of blocks with one and the same header, inflate.hip)
+    if (inflate_few_streams(n_streams))
       ZD_LAUNCH(ctx, "inflate_batch", inflate_batch_few_kernel, dim3((unsigned)(hi - lo)), dim3(64), 0,
                 (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, dd, dr, (uint32_t)(hi - lo),
                 (uint16_t *)ctx->inflate_scratch.p + lo * (INFLATE_SCRATCH_PER_STREAM / 2), k_crc_op);
@@ -995,7 +924,7 @@ int zipc_hip_deflate_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_d
   if (n_streams == 0) return ZIPC_HIP_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, ctx->ensure(ctx->deflate_scratch,
-                           deflate_scratch_bytes(n_streams, max_src_len, total_src_len, level)));
+                           deflate_scratch_bytes(n_streams, max_src_len, total_src_len, level, zd::tuning())));
   if (crc_op == ZIPC_HIP_CRC_CRC32) {  // (launch_deflate runs the pass, group by group)
     if (n_streams * crc32_segs(max_src_len) > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
     HIP_TRY(ctx, ctx->ensure(ctx->crc_partials, n_streams * crc32_segs(max_src_len) * sizeof(uint32_t)));
@@ -1012,7 +941,7 @@ int zipc_hip_debug_chain_links(zipc_hip_ctx *ctx, const void *d_src_arena, const
   if (!ctx || !d_descs || !d_links || which < 0 || which > 1 || n_streams == 0 || n_streams > 0x7FFFFFFFull || max_src_len > MAX_STREAM_LEN)
     return ZIPC_HIP_ERR_INVALID_ARG;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, ctx->ensure(ctx->deflate_scratch, deflate_scratch_bytes(n_streams, max_src_len, total_src_len, ZIPC_HIP_LEVEL_DEFAULT)));
+  HIP_TRY(ctx, ctx->ensure(ctx->deflate_scratch, deflate_scratch_bytes(n_streams, max_src_len, total_src_len, ZIPC_HIP_LEVEL_DEFAULT, zd::tuning())));
   HIP_TRY(ctx, zd::debug_chain_links(ctx, (const uint8_t *)d_src_arena, (const StreamDesc *)d_descs, n_streams, max_src_len, total_src_len,
                                      which, (uint16_t *)d_links, links_cap, (uint64_t *)d_pos_base));
   return ZIPC_HIP_OK;
@@ -1022,7 +951,7 @@ int zipc_hip_reserve(zipc_hip_ctx *ctx, size_t n_streams, size_t max_src_len, si
   if (!ctx) return ZIPC_HIP_ERR_INVALID_ARG;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, ctx->ensure(ctx->deflate_scratch,
-                           deflate_scratch_bytes(n_streams, max_src_len, total_src_len, ZIPC_HIP_LEVEL_BEST)));
+                           deflate_scratch_bytes(n_streams, max_src_len, total_src_len, ZIPC_HIP_LEVEL_BEST, zd::tuning())));
   size_t segs = (max_src_len + CRC_SEG_BYTES - 1) / CRC_SEG_BYTES + 1;
   HIP_TRY(ctx, ctx->ensure(ctx->crc_partials, n_streams * segs * sizeof(uint32_t)));
   return ZIPC_HIP_OK;

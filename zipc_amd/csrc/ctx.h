@@ -14,8 +14,8 @@ struct zipc_hip_ctx {
   // The stream ZD_LAUNCH enqueues on: `stream`, or one of `side` while a batch call has its
   // slices in flight (fork()/join() below).
   hipStream_t cur = nullptr;
-  // Side streams of the batch forms (ZIPC_HIP_SLICES > 1, not the default: deflate.hip has the
-  // measurement).  A large batch is cut into slices of consecutive streams and every slice's kernels
+  // Side streams of the batch forms (two slices by default, ZIPC_HIP_SLICES overrides: forms.h batch_slices
+  // has the measurement).  A large batch is cut into slices of consecutive streams and every slice's kernels
   // go to a queue of their own.  Work is still ordered behind everything enqueued on `stream` before
   // the call (fork) and everything enqueued on `stream` after the call is ordered behind the slices (join).
   std::vector<hipStream_t> side;
@@ -82,9 +82,8 @@ struct zipc_hip_ctx {
   } while (0)
 
 namespace zd {
-// api.hip: into how many slices of consecutive streams a batch of n is cut (1: no side streams).
-// ZIPC_HIP_SLICES overrides the default; a slice holds at least 2048 streams.
-size_t batch_slices(size_t n_streams);
+// api.hip: zipc_hip_debug_set_slices' number of slices for forms.h batch_slices (0: none set)
+long debug_slices_override();
 // api.hip: the two halves of the CRC-32 pass over n_ranges ranges of up to max_len bytes, on ctx->cur.
 // partials: n_ranges * crc32_segs(max_len) words.
 size_t crc32_segs(size_t max_len);
@@ -96,12 +95,11 @@ hipError_t crc32_finish_launch(zipc_hip_ctx *ctx, int mode, const StreamDesc *d_
                                uint32_t *d_single_out);
 // deflate.hip: the probe behind ctx->xchg_ordered
 bool xchg_order_probe(zipc_hip_ctx *ctx);
-// deflate.hip: bytes of scratch the pipeline needs, and the pipeline itself
-size_t deflate_scratch_bytes(size_t n_streams, size_t max_src_len, size_t total_src_len, int level);
 // deflate.hip (tests): the links one of the two chain kernels makes of a batch, and how many link slots that takes
 hipError_t debug_chain_links(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *d_descs, size_t n, size_t max_src_len,
                              size_t total_src_len, int which, uint16_t *d_links, size_t links_cap, uint64_t *d_pos_base);
 size_t debug_chain_positions(size_t n, size_t total_src_len);
+// deflate.hip: the pipeline itself (the scratch it needs: deflate_scratch.h deflate_scratch_bytes)
 hipError_t launch_deflate(zipc_hip_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst,
                           const StreamDesc *d_descs, StreamResult *d_results, size_t n_streams,
                           size_t max_src_len, size_t total_src_len, int level, int crc_op);

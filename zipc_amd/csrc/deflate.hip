@@ -40,69 +40,9 @@
 
 namespace zd {
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-static void scratch_caps(size_t n, size_t total_src_len, uint64_t &P, uint64_t &Bk) {
-  P = total_src_len + (uint64_t)(POS_PAD + 256) * n + 256;
-  Bk = total_src_len / MIN_BLOCK_SRC + 2 * (uint64_t)n + 16;
-}
-
-// A batch of more than DEFLATE_GROUP_BYTES of source (8 GiB) goes through the pipeline in groups of
-// consecutive streams, each group of at most that much, one after the other through the same
-// scratch: 14 bytes of scratch per source byte of a GROUP (2-byte links, 8-byte match entries,
-// 4-byte symbols), 112 GiB at most however large the batch.  Smaller groups were measured on C4
-// (8192 x 1 MiB): 4 GiB groups deflate 9 % slower and 2 GiB groups 23 % slower than one group --
-// lz_parse and deflate_emit are one wave per stream, and 2048 streams leave 2 waves per SIMD where
-// 8192 leave 8 -- so the scratch is bounded, not halved.  ZIPC_HIP_DEFLATE_GROUP_BYTES overrides
-// the size (tests run with groups of a few streams).
-static size_t deflate_group_bytes() { return tuning().deflate_group_bytes; }
-// streams per group, and the source bytes a group can hold at most
-static void deflate_grouping(size_t n, size_t max_src_len, size_t total_src_len, size_t &per_group, size_t &group_total) {
-  per_group = n;
-  group_total = total_src_len;
-  if (total_src_len > deflate_group_bytes() && max_src_len > 0 && n > 1) {
-    per_group = deflate_group_bytes() / max_src_len;
-    per_group = per_group < 1 ? 1 : (per_group > n ? n : per_group);
-    const unsigned __int128 bound = (unsigned __int128)per_group * max_src_len;
-    group_total = bound < total_src_len ? (size_t)bound : total_src_len;
-  }
-}
-
-size_t deflate_scratch_bytes(size_t n_all, size_t max_src_len, size_t total_all, int level) {
-  size_t n, total_src_len;
-  deflate_grouping(n_all, max_src_len, total_all, n, total_src_len);
-  uint64_t P, Bk;
-  scratch_caps(n, total_src_len, P, Bk);
-  size_t b = 0;
-  b += align_up(n * 8, 256) * 2 + align_up(n * 4, 256) * 2 + 256;
-  if (level != LEVEL_NONE) {
-    b += align_up(P * 2, 256) + 2 * align_up(P * 4, 256) + align_up(P * 4, 256);
-    b += align_up(Bk * sizeof(BlockDesc), 256);
-  }
-  return b + 1024;
-}
-
 static DeflateScratch carve(void *base, size_t n, size_t total_src_len, int level) {
   DeflateScratch s;
-  uint64_t P, Bk;
-  scratch_caps(n, total_src_len, P, Bk);
-  uint8_t *p = (uint8_t *)base;
-  s.pos_base = (uint64_t *)p; p += align_up(n * 8, 256);
-  s.blk_base = (uint64_t *)p; p += align_up(n * 8, 256);
-  s.n_blocks = (uint32_t *)p; p += align_up(n * 4, 256);
-  s.snap_used = (uint32_t *)p; p += align_up(n * 4, 256);
-  s.error = (uint32_t *)p; p += 256;
-  s.prev = nullptr; s.match = nullptr; s.snap = nullptr;
-  s.syms = nullptr; s.blocks = nullptr;
-  if (level != LEVEL_NONE) {
-    s.prev = (uint16_t *)p; p += align_up(P * 2, 256);
-    s.match = (uint32_t *)p; p += align_up(P * 4, 256);
-    s.snap = (uint32_t *)p; p += align_up(P * 4, 256);
-    s.syms = (uint32_t *)p; p += align_up(P * 4, 256);
-    s.blocks = (BlockDesc *)p; p += align_up(Bk * sizeof(BlockDesc), 256);
-  }
-  s.cap_positions = P;
-  s.cap_blocks = Bk;
+  carve_deflate_scratch((uintptr_t)base, n, total_src_len, level, s);
   return s;
 }
 
@@ -170,7 +110,6 @@ __global__ __launch_bounds__(1024) void deflate_offsets_kernel(const StreamDesc 
 constexpr uint32_t CHAIN_THREADS = 1024;
 constexpr int CHAIN_PPT = 1;                                // positions per thread and round
 constexpr uint32_t CHAIN_ROUND = CHAIN_THREADS * CHAIN_PPT;  // positions inserted per round
-constexpr uint32_t SWEEP_PERIOD = 16384;
 constexpr uint32_t SWEEP_MARK = 20000;
 constexpr int NEAR = 8;
 constexpr int PLAIN_TURNS = 4;  // peel turns before the neighbour short-cut is worth its LDS reads
@@ -180,9 +119,7 @@ static_assert(SWEEP_PERIOD % CHAIN_ROUND == 0, "sweeps fall on round boundaries"
 // a function of the 32 KiB before the position and nothing else.  So a long stream's links can be made by
 // several workgroups (SEG): each takes seg_positions of them, starts with an empty table at the sweep boundary at
 // least 32768 before its first one, and stores the links of its own positions only.
-// (seg_positions: a multiple of the sweep period; 32 or 64 Ki while that leaves the chip workgroups to spare -- twice
-// or half again the work for four times or twice the workgroups -- else 128 Ki)
-constexpr uint32_t CHAIN_SEG_MIN = 2 * SWEEP_PERIOD, CHAIN_SEG_MAX = 8 * SWEEP_PERIOD;
+// (seg_positions: CHAIN_SEG_MIN .. CHAIN_SEG_MAX, forms.h)
 template <bool SEG>
 __device__ __forceinline__ void lz_chain_workgroup(const uint8_t *__restrict__ src_arena,
                                                    const StreamDesc *__restrict__ descs,
@@ -588,7 +525,7 @@ bool xchg_order_probe(zipc_hip_ctx *ctx) {
   bool ok = false;
   do {
     if (ctx->ensure(src, len + 64) != hipSuccess || ctx->ensure(desc, sizeof sd) != hipSuccess) break;
-    if (ctx->ensure(ctx->deflate_scratch, deflate_scratch_bytes(1, len, len, LEVEL_DEFAULT)) != hipSuccess) break;
+    if (ctx->ensure(ctx->deflate_scratch, deflate_scratch_bytes(1, len, len, LEVEL_DEFAULT, tuning())) != hipSuccess) break;
     if (hipMemcpyAsync(src.p, v.data(), len, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) break;
     if (hipMemcpyAsync(desc.p, &sd, sizeof sd, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) break;
     DeflateScratch S = carve(ctx->deflate_scratch.p, 1, len, LEVEL_DEFAULT);
@@ -617,7 +554,7 @@ bool xchg_order_probe(zipc_hip_ctx *ctx) {
 // ---------------------------------------------------------------------------------
 constexpr uint32_t MATCH_THREADS = 256;
 constexpr int MATCH_NP = 4;  // positions per lane, their chain walks interleaved
-constexpr uint32_t MATCH_TILE = MATCH_THREADS * MATCH_NP;
+static_assert(MATCH_TILE == MATCH_THREADS * MATCH_NP, "the tile forms.h sizes the grid by");
 
 // A position's two answers into the tables; true when the second one went to snap[]
 __device__ __forceinline__ bool match_store(uint32_t *__restrict__ match, uint32_t *__restrict__ snap, uint32_t p, uint32_t best, uint32_t first) {
@@ -674,7 +611,6 @@ __global__ __launch_bounds__(MATCH_THREADS) void lz_match_kernel(const uint8_t *
 // global memory they are bound by the rate at which the vector memory pipeline
 // takes divergent addresses, out of LDS a wave's 64 addresses go in a few clocks.
 constexpr uint32_t MATCHW_THREADS = 1024;
-constexpr uint32_t MATCHW_TILE = 16384;
 constexpr int MATCHW_NP = 2;  // run slots per lane.  3 and 4 measured on C2 with the shared cursor: +3 % and +7.5 % (and
                                // +3 % / +8 % on 1 MiB streams of 3-bit symbols); 3 again under the tile-wide pool: +9 % on C2,
                                // +6 % on real text: the loop is nearer its vector bound than latency-bound
@@ -690,8 +626,6 @@ constexpr uint32_t MATCHW_SCAN_STEPS = 4;
 // second); the corpus' binaries -- a few long chains among many empty ones -- now take the second: 9.1 -> 3.6 ms per 64 MiB of
 // such chunks, the corpus' lz_match 17.1 -> 12.6 ms per 256 MiB
 constexpr uint32_t MATCHW_PROBE_DEEP = 192;
-constexpr size_t MATCHW_GROUPS_PER_WG = 8;  // groups a workgroup takes one behind the other, at most (launch_deflate_group)
-constexpr size_t MATCHW_SMALL = 8192;  // streams up to this long keep the global-memory kernel
 static_assert(MATCHW_TILE % MATCHW_THREADS == 0 && MATCHW_SRC_BYTES % 16 == 0, "tile shape");
 static_assert(MATCHW_SRC_BYTES + 2 * MATCHW_LINKS <= 160 * 1024, "LDS of one CU");
 
@@ -705,18 +639,8 @@ constexpr int ZD_PH_SLOTS = 1024;
 __device__ unsigned long long zd_match_phases[ZD_PH_SLOTS * 8];
 #endif
 
-// A stream's FIRST tile has no window in front of it, so the LDS that holds a window and a tile holds three tiles' worth of
-// the stream's start: tile 0 is 48 Ki positions, the others 16 Ki.  Every tile ends with its workgroup's waves running dry
-// one after the other -- the pool is empty, a wave's last walks go on with few lanes, and the longest chain of the last
-// positions sets how long: about 5 of a wave's 17 iterations of a 16 Ki tile on the benchmark's symbols (its lane use of
-// 0.58 is mostly that) -- and a 64 KiB stream now has two such ends where it had four (round 5).
-constexpr uint32_t MATCHW_TILE0 = MAX_MATCH_DIST + MATCHW_TILE;  // positions of a stream's first tile
+// (tile 0 is MATCHW_TILE0 positions, the others MATCHW_TILE: forms.h)
 __host__ __device__ inline uint32_t match_tile_start(uint32_t tile) { return tile == 0 ? 0u : MATCHW_TILE0 + (tile - 1u) * MATCHW_TILE; }
-// tiles of a stream of len bytes (len >= 4): a tile exists when its first position can start a match
-__host__ __device__ inline uint64_t match_tiles_of(uint64_t len) {
-  const uint64_t last = len - 4;  // the last position that can
-  return last < MATCHW_TILE0 ? 1 : 2 + (last - MATCHW_TILE0) / MATCHW_TILE;
-}
 // What one tile stages: source bytes [w0, src_end) and links [w0, link_end) of its stream
 struct MatchTile {
   uint32_t t0, w0;            // first position of the tile, first staged position
@@ -1078,11 +1002,7 @@ __device__ __forceinline__ void parse_tile_macro(int lane, uint32_t p, unsigned 
 
 // Streams parsed by several waves (lz_parse_spec_kernel / lz_parse_stitch_kernel / lz_parse_gather_kernel below):
 // what the waves leave for each other, per stream at the stream's position base (tiles: base / 64, segments: seg_base).
-// positions per segment (ParseSegs::seg_positions): a multiple of the tile, far above the longest step (63 + 512);
-// chosen per call -- the stitch takes a couple of microseconds per segment, one after the other, the waves of
-// lz_parse_spec_kernel a third of a microsecond per tile, side by side
-constexpr uint32_t PARSE_SEG_MIN = 4096;
-constexpr uint32_t PARSE_SEG_SLACK = 576;  // symbols of a segment at most: one per position before its last step, and that step's
+// (positions per segment, ParseSegs::seg_positions: forms.h PARSE_SEG_MIN and the rule of deflate_forms)
 struct ParseSegs {
   uint32_t *spec_syms;            // [segments * seg_syms] a segment's symbols as parsed from its first position
   unsigned long long *vis;        // [P / 64] per tile: the positions on the path (zeroed per call: a tile jumped over has none)
@@ -1579,7 +1499,6 @@ __device__ __forceinline__ ParseAgain parse_again(const ParseStream &P, uint32_t
 // lz_parse_meet_kernel: a wave per segment k >= 1 does that for the entry the segment has if the one before is left
 // where its OWN parse left it -- true of all segments but the few whose path never meets -- into the segment's
 // own small buffer (MEET_CAP symbols; more: left to the stitch).  The stitch then only checks the chain of exits.
-constexpr uint32_t MEET_CAP = 2048;
 __global__ __launch_bounds__(64) void lz_parse_meet_kernel(const uint8_t *__restrict__ src_arena,
                                                            const StreamDesc *__restrict__ descs,
                                                            DeflateScratch S, int good_match, ParseSegs G) {
@@ -2108,9 +2027,7 @@ __device__ __forceinline__ int wave_choose(const BlockCoder &c, uint32_t block_s
 // The blocks of a stream coded by a wave each (deflate_plan_kernel / deflate_scan_kernel / deflate_pack_kernel /
 // deflate_seal_kernel below): what they leave for each other, one record per block at the block's slot.
 constexpr uint32_t EMIT_SKIP = 0xFFu;  // kind of every block of a stream whose output does not fit
-constexpr uint32_t EMIT_PART = 8192;   // symbols a pack wave takes
-constexpr uint32_t EMIT_PARTS = 8;     // parts of a block at most (65534 symbols: all literals)
-static_assert(EMIT_PART * EMIT_PARTS >= (uint32_t)MAX_BLOCK_SRC_LEN, "a block's symbols fit its parts");
+// (EMIT_PART symbols a pack wave takes, EMIT_PARTS parts of a block at most: forms.h)
 // (split: a wave per part -- worth its per-wave set-up only while a call has few blocks; else a wave per block)
 __host__ __device__ inline uint32_t emit_parts_of(bool split, uint32_t kind, uint32_t n_syms) {
   return !split || kind == 0 || n_syms == 0 ? 1u : (n_syms + EMIT_PART - 1) / EMIT_PART;
@@ -2780,7 +2697,7 @@ __global__ __launch_bounds__(64) void deflate_stored_kernel(const uint8_t *__res
 hipError_t debug_chain_links(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *d_descs, size_t n, size_t max_src_len,
                              size_t total_src_len, int which, uint16_t *d_links, size_t links_cap, uint64_t *d_pos_base) {
   size_t per_group, group_total;
-  deflate_grouping(n, max_src_len, total_src_len, per_group, group_total);
+  deflate_grouping(n, max_src_len, total_src_len, tuning(), per_group, group_total);
   if (per_group != n) return hipErrorInvalidValue;  // one group (a batch of up to 8 GiB)
   DeflateScratch S = carve(ctx->deflate_scratch.p, n, total_src_len, LEVEL_DEFAULT);
   if (S.cap_positions > links_cap) return hipErrorInvalidValue;
@@ -2847,7 +2764,7 @@ hipError_t launch_deflate(zipc_hip_ctx *ctx, const uint8_t *d_src, uint8_t *d_ds
     return e;
   }
   size_t per_group, group_total;
-  deflate_grouping(n, max_src_len, total_src_len, per_group, group_total);
+  deflate_grouping(n, max_src_len, total_src_len, tuning(), per_group, group_total);
   for (size_t g0 = 0; g0 < n; g0 += per_group) {  // the descriptors carry arena offsets: a group is a slice of them
     const size_t ng = n - g0 < per_group ? n - g0 : per_group;
     const hipError_t e = launch_deflate_group(ctx, d_src, d_dst, d_descs + g0, d_results + g0, ng, max_src_len,
@@ -2857,79 +2774,10 @@ hipError_t launch_deflate(zipc_hip_ctx *ctx, const uint8_t *d_src, uint8_t *d_ds
   return hipSuccess;
 }
 
+// Which kernels, grids and segment sizes: forms.h deflate_forms (the group) and deflate_slice_forms (a slice of it).
 static hipError_t launch_deflate_group(zipc_hip_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst,
                                        const StreamDesc *d_descs, StreamResult *d_results, size_t n,
                                        size_t max_src_len, size_t total_src_len, int level, int crc_op) {
-  DeflateScratch S = carve(ctx->deflate_scratch.p, n, total_src_len, level);
-  int good_match, K;
-  level_params(level, good_match, K);
-  ZD_LAUNCH(ctx, "deflate_offsets", deflate_offsets_kernel, dim3(1), dim3(1024), 0, d_descs, (uint32_t)n, S,
-            (uint64_t)max_src_len);
-  // The pipeline of a slice of the group's streams: the slices share the scratch arrays (one
-  // scan above gave every stream its base) and the error word, and differ in where their
-  // per-stream arrays start.
-  const size_t tps = max_src_len >= 4 ? (size_t)match_tiles_of(max_src_len) : 1;
-  const size_t cps = max_src_len ? (max_src_len + MATCH_TILE - 1) / MATCH_TILE : 1;
-  if (n * (max_src_len <= MATCHW_SMALL ? cps : tps) > 0x7FFFFFFFull) return hipErrorInvalidValue;
-  // consecutive tiles of a stream per workgroup: as many as leave the grid >= 8192
-  // workgroups (32 per CU: with 2048 a group of 2048 long streams had one workgroup per stream
-  // and a long tail), so few long streams still spread over the chip
-  // (ZIPC_HIP_MATCH_TILES_PER_GROUP, read once, overrides the rule: tuning and tests)
-  const long tpg_env = tuning().match_tiles_per_group;
-  const int form_env = tuning().match_form;
-  size_t tpg = tpg_env > 0 ? (size_t)tpg_env : n * tps / 8192;
-  tpg = tpg < 1 ? 1 : (tpg > tps ? tps : tpg);
-  const size_t gps = (tps + tpg - 1) / tpg;
-  // Few long streams: lz_parse by a wave per segment (lz_parse_spec_kernel) and the blocks coded by a wave each
-  // (deflate_plan_kernel); many streams fill the chip with a wave each.  ZIPC_HIP_PARSE_SEGMENTS=0 never, =1
-  // whenever a stream has more than one segment (tests).
-  const long segs_env = tuning().parse_segments;
-  const long segp_env = tuning().parse_seg;  // positions per segment (tuning)
-  // segment size: the stitch's serial time per stream is segments x ~0.25 us, the parallel part's a segment's tiles x ~0.3 us
-  // (one stream alone, 4-bit symbols, whole deflate, ms at 4096 / 8192 / 16384 / 32768 / 65536 positions: 1 MiB 0.91 / 1.04 /
-  // 1.09 / 1.38 / 1.94, 16 MiB 2.18 / 1.89 / 1.87 / 2.10 / 2.57 -- since lz_parse_meet_kernel the stitch's turn per
-  // segment is a quarter of a microsecond)
-  size_t segp = max_src_len <= ((size_t)4 << 20) ? 4096 : max_src_len <= ((size_t)32 << 20) ? 8192 : 16384;
-  // (many long streams: as long as the call keeps 64 Ki waves, longer segments -- fewer seams to stitch and to gather across.
-  // 8192 x 1 MiB, ms a step at 4096 / 8192 / 16 384 / 32 768 positions: 175.2 / 174.3 / 172.7 / 171.9, profiles/r06_c4_parse_segments.txt)
-  while (segp < 32768 && n * ((max_src_len + 2 * segp - 1) / (2 * segp)) >= 65536) segp *= 2;
-  if (segp_env >= (long)PARSE_SEG_MIN && segp_env % 64 == 0 && segp_env <= (1L << 20)) segp = (size_t)segp_env;
-  const size_t sps = (max_src_len + segp - 1) / segp;
-  // (4096 x 1 MiB: 133 -> 124 ms; 64 KiB streams, 256 / 1024 / 2048 / 4096 / 16 384 of them:
-  // 1.77 -> 0.73, 2.38 -> 1.67, 3.16 -> 2.85, 4.78 -> 5.11, 15.6 -> 17.4 ms; 8192 x 1 MiB, BASELINE's C4: the same either way
-  // until round 6, then -- both parses a third shorter in instructions, the one wave per member still waiting for the LDS
-  // 60 % of its cycles -- 182.1 -> 175.2 ms a step, profiles/r06_c4_parse_segments.txt)
-  bool segmented = segs_env == 0 ? false : segs_env == 1 ? sps > 1
-                   : (sps >= 8 && (n <= 2048 || (n <= 4096 && max_src_len >= ((size_t)512 << 10)) || (n <= 8192 && max_src_len >= ((size_t)1 << 20))));
-  const size_t bps = (size_t)max_blocks_of(max_src_len);  // block slots of the longest stream
-  const size_t chain_seg = n * ((max_src_len + CHAIN_SEG_MIN - 1) / CHAIN_SEG_MIN) <= 512 ? CHAIN_SEG_MIN
-                           : n * ((max_src_len + 2 * CHAIN_SEG_MIN - 1) / (2 * CHAIN_SEG_MIN)) <= 1024 ? 2 * CHAIN_SEG_MIN : CHAIN_SEG_MAX;
-  const size_t csegs = (max_src_len + chain_seg - 1) / chain_seg;  // lz_chain: workgroups of the longest stream
-  if (segmented && (n * sps > 0x7FFFFFFFull || n * bps * EMIT_PARTS > 0x7FFFFFFFull)) segmented = false;
-  ParseSegs segs{};
-  EmitPlan *plans = nullptr;
-  if (segmented) {
-    const size_t n_slots = (size_t)(S.cap_positions / segp) + n + 1, tiles = (size_t)(S.cap_positions / 64) + 4;  // (ParseSegs::slot)
-    const size_t seg_syms = segp + PARSE_SEG_SLACK;
-    if (ctx->ensure(ctx->parse_scratch, carve_parse_scratch(0, S.cap_blocks, n_slots, tiles, seg_syms, plans, segs)) != hipSuccess) {
-      // (8192 members of 1 MiB ask for 39 GB of segment symbols here: where the device cannot give them, the forms by a wave per
-      // stream -- which need none -- take the call, as they did for this shape until round 6; only a call that ASKED for segments fails)
-      (void)hipGetLastError();
-      if (segs_env == 1) return hipErrorOutOfMemory;
-      segmented = false;
-      plans = nullptr;
-      segs = ParseSegs{};
-    } else {
-      carve_parse_scratch((uintptr_t)ctx->parse_scratch.p, S.cap_blocks, n_slots, tiles, seg_syms, plans, segs);
-      segs.segs_per_stream = (uint32_t)sps;
-      segs.seg_positions = (uint32_t)segp; segs.seg_syms = (uint32_t)seg_syms;
-      const hipError_t me = hipMemsetAsync(segs.vis, 0, tiles * 8, ctx->cur);
-      if (me != hipSuccess) return me;
-    }
-  }
-  // lz_chain: by ordered exchange where the context's probe passed (ZIPC_HIP_CHAIN=peel keeps the peel kernel: tests, A/B).
-  // A wave per stream leaves most of the chip idle while there are fewer streams than CUs: a long stream is then cut into
-  // segments of xseg positions, each warmed up with the 32 Ki positions before it (at most a third more work at 96 Ki).
   // A context whose first batch's check found a difference (counted in device-visible host memory, read here without waiting:
   // the next call at the latest sees it) keeps the other kernel from then on.
   if (ctx->xchg_ordered && ctx->chain_check_host && ctx->chain_check_host[0] != 0) {
@@ -2937,96 +2785,106 @@ static hipError_t launch_deflate_group(zipc_hip_ctx *ctx, const uint8_t *d_src, 
     ctx->last_error = "zipc_hip: lz_chain by ordered LDS exchange disagreed with the ordering kernel on this context's first batch; "
                       "that batch's streams reported ZIPC_HIP_ERR_HIP, the context now orders equal hashes itself";
   }
-  const bool xchg_chain = ctx->xchg_ordered && !tuning().chain_peel;
+  const bool xchg_ok = ctx->xchg_ordered && !tuning().chain_peel;
+  DeflateForms F = deflate_forms(n, max_src_len, total_src_len, level, tuning(), xchg_ok, debug_slices_override());
+  DeflateScratch S = carve(ctx->deflate_scratch.p, n, total_src_len, level);
+  ZD_LAUNCH(ctx, "deflate_offsets", deflate_offsets_kernel, dim3(1), dim3(1024), 0, d_descs, (uint32_t)n, S,
+            (uint64_t)max_src_len);
+  if (F.grid_too_large) return hipErrorInvalidValue;
+  ParseSegs segs{};
+  EmitPlan *plans = nullptr;
+  if (F.segmented &&
+      ctx->ensure(ctx->parse_scratch, carve_parse_scratch(0, S.cap_blocks, F.n_slots, F.tiles, F.seg_syms, plans, segs)) != hipSuccess) {
+    // (8192 members of 1 MiB ask for 39 GB of segment symbols here: where the device cannot give them, the forms by a wave per
+    // stream -- which need none -- take the call, as they did for this shape until round 6; only a call that ASKED for segments fails)
+    (void)hipGetLastError();
+    if (F.segments_required) return hipErrorOutOfMemory;
+    F = deflate_forms(n, max_src_len, total_src_len, level, tuning(), xchg_ok, debug_slices_override(), false);
+  }
+  if (F.segmented) {
+    carve_parse_scratch((uintptr_t)ctx->parse_scratch.p, S.cap_blocks, F.n_slots, F.tiles, F.seg_syms, plans, segs);
+    segs.segs_per_stream = (uint32_t)F.sps;
+    segs.seg_positions = (uint32_t)F.segp; segs.seg_syms = (uint32_t)F.seg_syms;
+    const hipError_t me = hipMemsetAsync(segs.vis, 0, F.tiles * 8, ctx->cur);
+    if (me != hipSuccess) return me;
+  }
   // The first 32 streams of the context's FIRST batch -- as many of them as hold 16 MiB of source -- are chained by both
   // kernels and compared (chain_check_enqueue)
   size_t check_k = 0;
-  if (xchg_chain && !ctx->chain_checked && ctx->chain_check_host) {
+  if (F.xchg_chain && !ctx->chain_checked && ctx->chain_check_host) {
     check_k = n < 32 ? n : 32;
     const size_t fit = max_src_len ? ((size_t)16 << 20) / max_src_len : check_k;
     check_k = check_k > fit ? (fit ? fit : 1) : check_k;
     ctx->chain_checked = true;
   }
-  size_t xseg = 0, xsegs = 1;
-  if (xchg_chain && n < 1024 && max_src_len > ((size_t)192 << 10)) {
-    xseg = (size_t)96 << 10;
-    while (n * ((max_src_len + 2 * xseg - 1) / (2 * xseg)) >= 2048) xseg *= 2;  // twice the chip's CUs of waves is plenty
-    xsegs = (max_src_len + xseg - 1) / xseg;
-  }
+  const int good_match = F.good_match, K = F.K;
   hipError_t slice_err = hipSuccess;
+  // The pipeline of a slice of the group's streams: the slices share the scratch arrays (one
+  // scan above gave every stream its base) and the error word, and differ in where their
+  // per-stream arrays start.
   auto slice = [&](size_t lo, size_t hi) {
     const size_t m = hi - lo;
+    const DeflateSliceForms L = deflate_slice_forms(F, m);
     DeflateScratch Q = S;
     Q.pos_base += lo; Q.blk_base += lo; Q.n_blocks += lo; Q.snap_used += lo;
     const StreamDesc *dd = d_descs + lo;
-    if (xchg_chain) {  // one wave per stream (per segment of a long one while there are few): ordered LDS exchange
-      if (m * xsegs > m && m * xsegs <= 0x7FFFFFFFull)
-        ZD_LAUNCH(ctx, "lz_chain", lz_chain_xchg_segments_kernel, dim3((unsigned)(m * xsegs)), dim3(64 * XCHG_WAVES), 0, d_src, dd, Q,
-                  (uint32_t)xsegs, (uint32_t)xseg);
-      else
-        ZD_LAUNCH(ctx, "lz_chain", lz_chain_xchg_kernel, dim3((unsigned)m), dim3(64 * XCHG_WAVES), 0, d_src, dd, Q);
-      if (lo == 0 && check_k) {
-        const hipError_t ce = chain_check_enqueue(ctx, d_src, dd, Q, check_k < m ? check_k : m, max_src_len, ctx->chain_check_host);
-        if (ce != hipSuccess) slice_err = ce;
-      }
-    } else if (segmented && csegs > 1 && m <= 128)  // (the run-up is a quarter more work: only while workgroups are what is missing)
-      ZD_LAUNCH(ctx, "lz_chain", lz_chain_segments_kernel, dim3((unsigned)(m * csegs)), dim3(CHAIN_THREADS), 0, d_src, dd,
-                Q, (uint32_t)csegs, (uint32_t)chain_seg);
-    else
-      ZD_LAUNCH(ctx, "lz_chain", lz_chain_kernel, dim3((unsigned)m), dim3(CHAIN_THREADS), 0, d_src, dd, Q);
-    if (max_src_len <= MATCHW_SMALL)  // short streams: a whole-CU window per tile would sit mostly idle
-      ZD_LAUNCH(ctx, "lz_match", lz_match_kernel, dim3((unsigned)((m * cps + 7) / 8 * 8)), dim3(MATCH_THREADS), 0,
-                d_src, dd, Q, (uint32_t)m, (uint32_t)cps, K, K / 4);
-    else {
-      // groups a workgroup takes one behind the other: as many as leave 2048 workgroups and more, 8 at most (measured 1 / 2 / 4 / 8:
-      // the benchmark's streams 4.70 / 4.60 / 4.50 / 4.50 ms, text 48.6 / 47.0 / 45.7 / 46.2, 1 MiB members of 3-bit symbols 31.9 / 32.2 / 32.7 / 30.6)
-      size_t gpw = m * gps / 2048;
-      gpw = gpw < 1 ? 1 : gpw > MATCHW_GROUPS_PER_WG ? MATCHW_GROUPS_PER_WG : gpw;
-      // (... of groups that are short: a launch ends when its last workgroup does, and at `Best a group of text takes milliseconds --
-      // 2048 streams: 8 workgroups of two groups a CU 76.8 ms, 16 of one 66.5.  Taking the groups from a counter instead of by
-      // position in the grid evened that out -- 66.0 -- and cost 1 MiB members 13 % and the benchmark's streams 2-10 %; three
-      // quarters of the groups in workgroups of several and the rest in workgroups of one: 73.0.  Both measured, neither kept.)
-      if (K >= 1024) gpw = 1;
-      const size_t wgs = (m * gps + gpw - 1) / gpw;
-      ZD_LAUNCH(ctx, "lz_match", lz_match_window_kernel, dim3((unsigned)((wgs + 7) / 8 * 8)), dim3(MATCHW_THREADS),
-                0, d_src, dd, Q, (uint32_t)m, (uint32_t)tps, (uint32_t)tpg, (uint32_t)gpw, K, K / 4, form_env);
+    switch (L.chain) {
+    case CHAIN_XCHG_SEGMENTS:
+      ZD_LAUNCH(ctx, "lz_chain", lz_chain_xchg_segments_kernel, dim3((unsigned)L.chain_grid), dim3(64 * XCHG_WAVES), 0, d_src, dd, Q,
+                (uint32_t)F.xsegs, (uint32_t)F.xseg);
+      break;
+    case CHAIN_XCHG:
+      ZD_LAUNCH(ctx, "lz_chain", lz_chain_xchg_kernel, dim3((unsigned)L.chain_grid), dim3(64 * XCHG_WAVES), 0, d_src, dd, Q);
+      break;
+    case CHAIN_PEEL_SEGMENTS:
+      ZD_LAUNCH(ctx, "lz_chain", lz_chain_segments_kernel, dim3((unsigned)L.chain_grid), dim3(CHAIN_THREADS), 0, d_src, dd,
+                Q, (uint32_t)F.csegs, (uint32_t)F.chain_seg);
+      break;
+    case CHAIN_PEEL:
+      ZD_LAUNCH(ctx, "lz_chain", lz_chain_kernel, dim3((unsigned)L.chain_grid), dim3(CHAIN_THREADS), 0, d_src, dd, Q);
+      break;
     }
-    if (segmented) {
+    if (lo == 0 && check_k) {
+      const hipError_t ce = chain_check_enqueue(ctx, d_src, dd, Q, check_k < m ? check_k : m, max_src_len, ctx->chain_check_host);
+      if (ce != hipSuccess) slice_err = ce;
+    }
+    if (!L.match_window)
+      ZD_LAUNCH(ctx, "lz_match", lz_match_kernel, dim3((unsigned)L.match_grid), dim3(MATCH_THREADS), 0,
+                d_src, dd, Q, (uint32_t)m, (uint32_t)F.cps, K, K / 4);
+    else
+      ZD_LAUNCH(ctx, "lz_match", lz_match_window_kernel, dim3((unsigned)L.match_grid), dim3(MATCHW_THREADS),
+                0, d_src, dd, Q, (uint32_t)m, (uint32_t)F.tps, (uint32_t)F.tpg, (uint32_t)L.gpw, K, K / 4, tuning().match_form);
+    if (F.segmented) {
       ParseSegs G = segs;
       const size_t o = lo;  // the slice's segment slots: ParseSegs::slot counts streams from the slice's first (Q.pos_base is the slice's too)
       G.spec_syms += o * G.seg_syms;
       G.seg_exit += o; G.seg_total += o; G.seg_dst += o; G.seg_from += o; G.seg_n += o;
       G.meet_syms += o * MEET_CAP;
       G.meet_f += o; G.meet_from += o; G.meet_exit += o; G.meet_end += o; G.fix_dst += o; G.fix_n += o;
-      ZD_LAUNCH(ctx, "lz_parse_spec", lz_parse_spec_kernel, dim3((unsigned)(m * sps)), dim3(64), 0, d_src, dd, Q,
+      ZD_LAUNCH(ctx, "lz_parse_spec", lz_parse_spec_kernel, dim3((unsigned)L.segments), dim3(64), 0, d_src, dd, Q,
                 good_match, G);
-      ZD_LAUNCH(ctx, "lz_parse_meet", lz_parse_meet_kernel, dim3((unsigned)(m * sps)), dim3(64), 0, d_src, dd, Q,
+      ZD_LAUNCH(ctx, "lz_parse_meet", lz_parse_meet_kernel, dim3((unsigned)L.segments), dim3(64), 0, d_src, dd, Q,
                 good_match, G);
-      ZD_LAUNCH(ctx, "lz_parse_stitch", lz_parse_stitch_kernel, dim3((unsigned)m), dim3(64), 0, d_src, dd, Q,
+      ZD_LAUNCH(ctx, "lz_parse_stitch", lz_parse_stitch_kernel, dim3((unsigned)L.streams), dim3(64), 0, d_src, dd, Q,
                 good_match, G);
-      ZD_LAUNCH(ctx, "lz_parse_gather", lz_parse_gather_kernel, dim3((unsigned)(m * sps)), dim3(64), 0, dd, Q, G);
-    } else {
-      ZD_LAUNCH(ctx, "lz_parse", lz_parse_kernel, dim3((unsigned)m), dim3(64), 0, d_src, dd, Q, good_match);
-    }
-    if (segmented) {
-      ZD_LAUNCH(ctx, "deflate_plan", deflate_plan_kernel, dim3((unsigned)(m * bps)), dim3(64), 0, d_src, dd, Q, crc_op,
-                (uint32_t)bps, plans);
-      ZD_LAUNCH(ctx, "deflate_counts", deflate_counts_kernel, dim3((unsigned)m), dim3(64), 0, dd, Q, plans);
-      ZD_LAUNCH(ctx, "deflate_codelen", deflate_codelen_kernel, dim3((unsigned)(m * bps)), dim3(64), 0, dd, Q,
-                (uint32_t)bps, plans);
-      ZD_LAUNCH(ctx, "deflate_scan", deflate_scan_kernel, dim3((unsigned)m), dim3(64), 0, dd, d_results + lo, Q, crc_op,
+      ZD_LAUNCH(ctx, "lz_parse_gather", lz_parse_gather_kernel, dim3((unsigned)L.segments), dim3(64), 0, dd, Q, G);
+      ZD_LAUNCH(ctx, "deflate_plan", deflate_plan_kernel, dim3((unsigned)L.blocks), dim3(64), 0, d_src, dd, Q, crc_op,
+                (uint32_t)F.bps, plans);
+      ZD_LAUNCH(ctx, "deflate_counts", deflate_counts_kernel, dim3((unsigned)L.streams), dim3(64), 0, dd, Q, plans);
+      ZD_LAUNCH(ctx, "deflate_codelen", deflate_codelen_kernel, dim3((unsigned)L.blocks), dim3(64), 0, dd, Q,
+                (uint32_t)F.bps, plans);
+      ZD_LAUNCH(ctx, "deflate_scan", deflate_scan_kernel, dim3((unsigned)L.streams), dim3(64), 0, dd, d_results + lo, Q, crc_op,
                 plans);
-      // few blocks in the call: a coded block's symbols by a wave per EMIT_PART of them
-      const size_t ppb = m * bps <= 2048 ? EMIT_PARTS : 1;
-      if (ppb != 1)
-        ZD_LAUNCH(ctx, "deflate_bits", deflate_bits_kernel, dim3((unsigned)(m * bps * EMIT_PARTS)), dim3(64), 0, d_src, dd, Q,
-                  crc_op, (uint32_t)bps, plans);
-      ZD_LAUNCH(ctx, "deflate_pack", deflate_pack_kernel, dim3((unsigned)(m * bps * ppb)), dim3(64), 0, d_src, d_dst,
-                dd, Q, crc_op, (uint32_t)bps, plans, (uint32_t)ppb);
-      ZD_LAUNCH(ctx, "deflate_seal", deflate_seal_kernel, dim3((unsigned)((m * bps * ppb + 255) / 256)), dim3(256), 0,
-                d_dst, dd, Q, (uint32_t)m, (uint32_t)bps, (const EmitPlan *)plans, (uint32_t)ppb);
+      if (L.ppb != 1)
+        ZD_LAUNCH(ctx, "deflate_bits", deflate_bits_kernel, dim3((unsigned)L.bits_grid), dim3(64), 0, d_src, dd, Q,
+                  crc_op, (uint32_t)F.bps, plans);
+      ZD_LAUNCH(ctx, "deflate_pack", deflate_pack_kernel, dim3((unsigned)L.pack_grid), dim3(64), 0, d_src, d_dst,
+                dd, Q, crc_op, (uint32_t)F.bps, plans, (uint32_t)L.ppb);
+      ZD_LAUNCH(ctx, "deflate_seal", deflate_seal_kernel, dim3((unsigned)L.seal_grid), dim3(256), 0,
+                d_dst, dd, Q, (uint32_t)m, (uint32_t)F.bps, (const EmitPlan *)plans, (uint32_t)L.ppb);
     } else {
-      ZD_LAUNCH(ctx, "deflate_emit", deflate_emit_kernel, dim3((unsigned)m), dim3(64), 0, d_src, d_dst, dd,
+      ZD_LAUNCH(ctx, "lz_parse", lz_parse_kernel, dim3((unsigned)L.streams), dim3(64), 0, d_src, dd, Q, good_match);
+      ZD_LAUNCH(ctx, "deflate_emit", deflate_emit_kernel, dim3((unsigned)L.streams), dim3(64), 0, d_src, d_dst, dd,
                 d_results + lo, Q, crc_op);
     }
     // The CRC-32 pass over the slice's source (deflated_block_src_crc, zd.ml:1081-1086: exact across blocks for
@@ -3041,11 +2899,11 @@ static hipError_t launch_deflate_group(zipc_hip_ctx *ctx, const uint8_t *d_src, 
       if (ce != hipSuccess) slice_err = ce;
     }
   };
-  // ZIPC_HIP_SLICES > 1: the group goes out in slices on queues of their own (ctx.h).  Measured on the
-  // three shapes of tools/exp_wall.py and NOT the default: the kernels are each near their issue bound and
-  // share the chip by workgroup, so slices changed the time by -4 .. +3 % (2 slices) or lost (more) -- until lz_chain
-  // became four waves per CU (round 4): two slices are the default now, api.hip batch_slices has the numbers.
-  const size_t k = batch_slices(n);
+  // The group goes out in slices on queues of their own (ctx.h): two by default, forms.h batch_slices has the numbers.
+  // Measured on the three shapes of tools/exp_wall.py: the kernels are each near their issue bound and share the chip by
+  // workgroup, so slices changed the time by -4 .. +3 % (2 slices) or lost (more) -- until lz_chain became four waves per
+  // CU (round 4).
+  const size_t k = F.slices;
   hipError_t e = hipSuccess;
   if (k > 1) {
     e = ctx->fork(k);

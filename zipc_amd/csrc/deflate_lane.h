@@ -25,16 +25,6 @@ struct BlockDesc {
   uint32_t sym_start, n_syms;   // slice of the stream's symbol array (no EOB stored)
 };
 
-// level_params zd.ml:754-764: (good_match, max_chain_len); the other two are never read
-ZD_HD void level_params(int level, int &good_match, int &max_chain) {
-  switch (level) {
-  case LEVEL_FAST: good_match = 4; max_chain = 4; break;
-  case LEVEL_DEFAULT: good_match = 8; max_chain = 128; break;
-  case LEVEL_BEST: good_match = 32; max_chain = 4096; break;
-  default: good_match = 0; max_chain = 0; break;
-  }
-}
-
 // Common prefix of s[q..] and s[p..], capped at maxlen (match_bwd/match_fwd,
 // zd.ml:1154-1174, without the early-out order: the result is the same length).
 // (from: bytes already known to agree, a multiple of 8 not above maxlen)

@@ -29,7 +29,7 @@ struct Tuning {
   size_t deflate_group_bytes;  // ZIPC_HIP_DEFLATE_GROUP_BYTES  source bytes per pass through the scratch (default 8 GiB; the tests: a
                                //                          few streams).  test_gpu_fuzz
   long slices, slice_min;      // ZIPC_HIP_SLICES, ZIPC_HIP_SLICE_MIN  a batch cut into slices on side queues (default 0: two slices of at
-                               //                          least 2048 streams each, api.hip batch_slices; the tests force more and smaller
+                               //                          least 2048 streams each, forms.h batch_slices; the tests force more and smaller
                                //                          ones).  test_gpu_fuzz
   // ---- inflate of one long stream by blocks (api.hip inflate_by_blocks)
   bool inflate_blocks;         // ZIPC_HIP_INFLATE_BLOCKS=0  the stream's one wave instead.  tools/measure_round.sh

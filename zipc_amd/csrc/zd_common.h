@@ -53,6 +53,16 @@ constexpr uint32_t ADLER_BASE = 65521; // zd.ml:172
 constexpr uint32_t ADLER_CHUNK = 5552; // zd.ml:180,196
 constexpr uint32_t CRC_POLY = 0xedb88320u;  // zd.ml:113
 
+// level_params zd.ml:754-764: (good_match, max_chain_len); the other two are never read
+ZD_HD void level_params(int level, int &good_match, int &max_chain) {
+  switch (level) {
+  case LEVEL_FAST: good_match = 4; max_chain = 4; break;
+  case LEVEL_DEFAULT: good_match = 8; max_chain = 128; break;
+  case LEVEL_BEST: good_match = 32; max_chain = 4096; break;
+  default: good_match = 0; max_chain = 0; break;
+  }
+}
+
 // stream descriptor / result: binary-identical to zipc_hip_stream_desc /
 // zipc_hip_stream_result of include/zipc_hip.h
 struct StreamDesc {
