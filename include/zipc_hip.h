@@ -143,7 +143,7 @@ typedef struct {
   double total_ms;
 } zipc_hip_kernel_time;
 int zipc_hip_set_profiling(zipc_hip_ctx *ctx, int enabled);
-/* enabled != 0: zipc_hip_zlib_compress / _decompress and zipc_hip_checksum_device's Adler-32 of this
+/* enabled != 0: the zlib forms (single, _many and _batch) and zipc_hip_checksum_device's Adler-32 of this
  * context follow RFC 1950 (see ZIPC_HIP_CRC_ADLER32_RFC1950); 0 (the default): the reference's. */
 int zipc_hip_set_adler_rfc1950(zipc_hip_ctx *ctx, int enabled);
 int zipc_hip_reset_kernel_times(zipc_hip_ctx *ctx);
@@ -232,6 +232,23 @@ int zipc_hip_inflate_many_check(zipc_hip_ctx *ctx, size_t n, const void *const *
                                 const size_t *limit, int crc_op, const size_t *dst_cap,
                                 struct zipc_hip_stream_result_s *results);
 
+/* The zlib container around many host streams: zlib_decompress / zlib_compress (zipc_deflate.ml:720-740, 1262-1277,
+ * start = 0) of every stream in one go, through the same pipeline as zipc_hip_inflate_many / _deflate_many.  The six
+ * container bytes of a stream are read and written on the host (csrc/zlib_container.h: the reference's checks in its
+ * order, the body range [2, len-2), the big-endian Adler-32); the bodies go through the kernels with the context's
+ * Adler-32 flavour (zipc_hip_set_adler_rfc1950).  results[i]: ZIPC_HIP_OK, the checksum and the length -- to compress,
+ * of the whole zlib stream in dst[i] -- or the stream's own error: the reference's header messages,
+ * ZIPC_HIP_ERR_CHECKSUM with checksum = the Adler-32 FOUND and out_len 0 (the expected one is the stream's last four
+ * bytes, big-endian), inflate's statuses, ZIPC_HIP_ERR_DST_TOO_SMALL for a dst_cap under 6 or under what the stream
+ * takes (zipc_hip_zlib_bound).  A stream that fails its header check never reaches the device and leaves dst[i] as it
+ * was.  results[] is defined on every return, bad arguments included (every entry then carries the call's status), and
+ * no C++ exception crosses the boundary. */
+int zipc_hip_zlib_decompress_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len,
+                                  const size_t *limit, void *const *dst, const size_t *dst_cap,
+                                  struct zipc_hip_stream_result_s *results);
+int zipc_hip_zlib_compress_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len, int level,
+                                void *const *dst, const size_t *dst_cap, struct zipc_hip_stream_result_s *results);
+
 /* ---- batch forms (device-resident) ----------------------------------------- */
 
 /* One independent stream: bytes [src_off, src_off+src_len) of the source arena
@@ -287,6 +304,31 @@ int zipc_hip_deflate_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_d
                            zipc_hip_stream_result *d_results, size_t n_streams,
                            size_t max_src_len, size_t total_src_len, int level,
                            int crc_op);
+
+/* The zlib container on the device: stream i of the source arena is a WHOLE zlib stream (decompress), or becomes one
+ * in its destination slot (compress; dst_cap of zipc_hip_zlib_bound(src_len) always fits).  Same descriptors, results
+ * and contract as the two forms above -- all pointers are device pointers, the work is enqueued on the context's stream
+ * and not synchronised, except where zipc_hip_inflate_batch itself synchronises (max_dst_cap of 256 KiB and more) -- and
+ * the same kernels, between two small ones that handle the container, a lane per stream (csrc/zlib.hip):
+ *   before: the reference's checks in its order (zipc_deflate.ml:723-730; to compress: dst_cap < 6 is
+ *     ZIPC_HIP_ERR_DST_TOO_SMALL), a flag bit other than ZIPC_HIP_STREAM_HAS_LIMIT is ZIPC_HIP_ERR_INVALID_ARG; a stream
+ *     that fails reports that status with checksum 0 and out_len 0, and nothing is written to its destination.  The
+ *     codec is handed the reference's body range [2, len-2) / the room [2, dst_cap-4) (the descriptors it runs with
+ *     live in the context's scratch);
+ *   behind: to decompress, the Adler-32 of the output (the reference's, or RFC 1950's after
+ *     zipc_hip_set_adler_rfc1950) against the stream's last four bytes: a stream whose checksum differs reports
+ *     ZIPC_HIP_ERR_CHECKSUM with checksum = the value FOUND and out_len 0 -- the value EXPECTED is not in the result:
+ *     it is the big-endian word in the stream's own last four bytes.  To compress, CMF / FLG and the Adler-32 are
+ *     stored around deflate's bytes, out_len counts them and checksum is the Adler-32.  Every other result is the
+ *     codec's (the batch-wide ZIPC_HIP_ERR_INVALID_ARG of zipc_hip_deflate_batch's declared sizes among them).
+ * level outside 0..3 fails the call.  ONE stream with max_dst_cap above ZIPC_HIP_MAX_STREAM_LEN fails the call with
+ * ZIPC_HIP_ERR_INVALID_ARG: inflate's path for stored streams beyond 4 GiB computes no Adler-32. */
+int zipc_hip_zlib_decompress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                   const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                                   size_t n_streams, size_t max_dst_cap);
+int zipc_hip_zlib_compress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                 const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                                 size_t n_streams, size_t max_src_len, size_t total_src_len, int level);
 
 /* CRC-32 and Adler-32 of one device buffer (Crc_32.string + Adler_32.string).  Both asked for: ONE pass over the bytes
  * leaves the CRC-32 partials and the Adler-32 chunk sums (len bytes of traffic), then the two short finishes.  d_out receives {crc32, adler32}.  Either selector may be 0 to

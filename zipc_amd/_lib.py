@@ -81,8 +81,12 @@ SYMBOLS = [
     ("zipc_hip_deflate_many", C.c_int, [_P, _SZ, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     ("zipc_hip_inflate_many", C.c_int, [_P, _SZ, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("zipc_hip_inflate_many_check", C.c_int, [_P, _SZ, _P, _P, _P, C.c_int, _P, _P]),
+    ("zipc_hip_zlib_decompress_many", C.c_int, [_P, _SZ, _P, _P, _P, _P, _P, _P]),
+    ("zipc_hip_zlib_compress_many", C.c_int, [_P, _SZ, _P, _P, C.c_int, _P, _P, _P]),
     ("zipc_hip_inflate_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, C.c_int]),
     ("zipc_hip_deflate_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int, C.c_int]),
+    ("zipc_hip_zlib_decompress_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ]),
+    ("zipc_hip_zlib_compress_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int]),
     ("zipc_hip_checksum_device", C.c_int, [_P, _P, _SZ, C.c_int, C.c_int, _P]),
     ("zipc_hip_reserve", C.c_int, [_P, _SZ, _SZ, _SZ]),
 ]

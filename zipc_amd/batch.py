@@ -68,6 +68,31 @@ def deflate_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int
         ctx.synchronize()
 
 
+def zlib_decompress_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, max_dst_cap: int, sync: bool = True):
+    """zipc_hip_zlib_decompress_batch: stream i of `src` is a whole zlib stream; header checks, inflate and the Adler-32
+    comparison all on the device (the context's Adler-32 flavour: Context.set_adler_rfc1950)."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_zlib_decompress_batch(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(),
+                                              results_dev.data_ptr(), n_streams, max_dst_cap)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def zlib_compress_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, max_src_len: int,
+                        total_src_len: int, level: int, sync: bool = True):
+    """zipc_hip_zlib_compress_batch: every stream's destination slot receives a whole zlib stream (out_len counts its six
+    container bytes, checksum is the Adler-32); slots of zlib_bound(src_len) always fit."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_zlib_compress_batch(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(),
+                                            results_dev.data_ptr(), n_streams, max_src_len, total_src_len, level)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
 def debug_chain_links(ctx: Context, src, descs_dev, n_streams: int, max_src_len: int, total_src_len: int, which: int):
     """Tests only (include/zipc_hip.h zipc_hip_debug_chain_links): the hash-chain links of a device-resident batch as the
     library's chain kernel `which` makes them (0: ordered LDS exchange, 1: the kernel that orders equal hashes itself):
@@ -108,6 +133,10 @@ def deflate_bound(n: int) -> int:
     return lib().zipc_hip_deflate_bound(n)
 
 
+def zlib_bound(n: int) -> int:
+    return lib().zipc_hip_zlib_bound(n)
+
+
 def uniform_layout(n_streams: int, src_len: int, dst_cap: int, limit=None) -> np.ndarray:
     """n equal streams laid back to back in both arenas (dst slots 256-byte aligned)."""
     slot = (dst_cap + 255) // 256 * 256
@@ -130,5 +159,6 @@ def compact_descs(results: np.ndarray, descs: np.ndarray, dst_cap_of_out, limit_
 
 
 __all__ = ["DESC_DTYPE", "RESULT_DTYPE", "make_descs", "to_device", "results_from_device",
-           "inflate_batch", "deflate_batch", "checksum_device", "reserve", "deflate_bound",
+           "inflate_batch", "deflate_batch", "zlib_decompress_batch", "zlib_compress_batch", "checksum_device", "reserve",
+           "deflate_bound", "zlib_bound",
            "uniform_layout", "compact_descs", "OK"]

@@ -22,6 +22,7 @@
 #include "deflate_scratch.h"
 #include "host_pipeline.h"
 #include "tuning.h"
+#include "zlib_container.h"
 
 using namespace zd;
 
@@ -361,6 +362,7 @@ void zipc_hip_destroy(zipc_hip_ctx *ctx) {
   free_buf(ctx->blocks_scratch);
   free_buf(ctx->tok_scratch);
   free_buf(ctx->descs_marked);
+  free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre);
   free_buf(ctx->stored_list);
   free_buf(ctx->chain_check_links);
   if (ctx->chain_check_host) (void)hipHostFree(ctx->chain_check_host);
@@ -1445,26 +1447,143 @@ int zipc_hip_inflate_many_check(zipc_hip_ctx *ctx, size_t n, const void *const *
   catch (...) { return many_threw(ctx, n, results); }
 }
 
-// zlib_decompress src/zipc_deflate.ml:720-740 (start = 0): header checks on the
-// host (6 bytes of parsing), body through the inflate kernel with Adler-32
+// ---- the zlib container (zlib_container.h has the rules; zlib.hip the two kernels of the batch forms) --------------
+
+static int zlib_crc_op(const zipc_hip_ctx *ctx) { return ctx->adler_rfc1950 ? ZIPC_HIP_CRC_ADLER32_RFC1950 : ZIPC_HIP_CRC_ADLER32; }
+
+// zlib_open_kernel over the caller's descriptors: the codec's descriptors and the checks' verdicts, in the context's scratch
+static int zlib_open(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, size_t n, int compress) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->ensure(ctx->zlib_descs, n * sizeof(StreamDesc)));
+  HIP_TRY(ctx, ctx->ensure(ctx->zlib_pre, n * sizeof(ZlibPre)));
+  ZD_LAUNCH(ctx, "zlib_open", zlib_open_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint8_t *)d_src_arena,
+            (const StreamDesc *)d_descs, (uint32_t)n, compress, (StreamDesc *)ctx->zlib_descs.p, (ZlibPre *)ctx->zlib_pre.p);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+static int zlib_close(zipc_hip_ctx *ctx, void *d_dst_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                      size_t n, int compress, int level) {
+  ZD_LAUNCH(ctx, "zlib_close", zlib_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (uint8_t *)d_dst_arena,
+            (const StreamDesc *)d_descs, (const ZlibPre *)ctx->zlib_pre.p, (StreamResult *)d_results, (uint32_t)n, compress, level);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+
+int zipc_hip_zlib_decompress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                   zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  if (n_streams == 1 && max_dst_cap > MAX_STREAM_LEN) return ZIPC_HIP_ERR_INVALID_ARG;  // (that path has no Adler-32: inflate_huge_stream)
+  int st = zlib_open(ctx, d_src_arena, d_descs, n_streams, 0);
+  if (st) return st;
+  st = zipc_hip_inflate_batch(ctx, d_src_arena, d_dst_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, d_results, n_streams,
+                              max_dst_cap, zlib_crc_op(ctx));
+  if (st) return st;
+  return zlib_close(ctx, d_dst_arena, d_descs, d_results, n_streams, 0, 0);
+}
+
+int zipc_hip_zlib_compress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                 zipc_hip_stream_result *d_results, size_t n_streams, size_t max_src_len, size_t total_src_len,
+                                 int level) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull || level < 0 || level > 3) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (max_src_len > MAX_STREAM_LEN) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = zlib_open(ctx, d_src_arena, d_descs, n_streams, 1);
+  if (st) return st;
+  st = zipc_hip_deflate_batch(ctx, d_src_arena, d_dst_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, d_results, n_streams,
+                              max_src_len, total_src_len, level, zlib_crc_op(ctx));
+  if (st) return st;
+  return zlib_close(ctx, d_dst_arena, d_descs, d_results, n_streams, 1, level);
+}
+
+// The many-stream host forms: the same two steps on the host around many_streams -- the streams' bodies (or the room
+// behind their headers) go through it as raw streams, a stream that fails the container's check as one of no bytes and
+// no room.  results[] is defined on every return: an entry the pipeline never wrote carries the call's status.
+constexpr uint32_t ZLIB_RESULT_UNSET = 0xFFFFFFFFu;
+static int zlib_many(zipc_hip_ctx *ctx, bool decompress, size_t n, const void *const *src, const size_t *src_len, const size_t *limit,
+                     int level, void *const *dst, const size_t *dst_cap, zipc_hip_stream_result *results) {
+  auto fail = [&](int st) {
+    if (results) for (size_t i = 0; i < n; i++) results[i] = zipc_hip_stream_result{(uint32_t)st, 0, 0};
+    return st;
+  };
+  if (!ctx || (n && (!src || !src_len || !dst || !dst_cap || !results)) || level < 0 || level > 3) return fail(ZIPC_HIP_ERR_INVALID_ARG);
+  for (size_t i = 0; i < n; i++)
+    if ((!src[i] && src_len[i]) || (!dst[i] && dst_cap[i])) return fail(ZIPC_HIP_ERR_INVALID_ARG);
+  if (n == 0) return ZIPC_HIP_OK;
+  std::vector<const void *> in_src(src, src + n);
+  std::vector<void *> in_dst(dst, dst + n);
+  std::vector<size_t> in_len(src_len, src_len + n), in_cap(dst_cap, dst_cap + n);
+  std::vector<ZlibPre> pre(n);
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t *s = (const uint8_t *)src[i];
+    ZlibPre &p = pre[i];
+    p.expect = 0;
+    if (decompress) {
+      const bool whole = src_len[i] >= ZLIB_MIN_LEN;
+      p.status = zlib_open_status(src_len[i], whole ? s[0] : 0, whole ? s[1] : 0);
+      if (p.status == ST_OK) {
+        p.expect = zlib_expect(s + src_len[i] - 4);
+        in_src[i] = s + zlib_body_off(0);
+        in_len[i] = (size_t)zlib_body_len(src_len[i]);
+      }
+    } else {
+      p.status = dst_cap[i] < ZLIB_OVERHEAD ? (uint32_t)ST_DST_TOO_SMALL : (uint32_t)ST_OK;
+      if (p.status == ST_OK) {
+        in_dst[i] = (uint8_t *)dst[i] + zlib_payload_off(0);
+        in_cap[i] = (size_t)zlib_payload_cap(dst_cap[i]);
+      }
+    }
+    if (p.status != ST_OK) { in_len[i] = 0; in_cap[i] = 0; }
+    results[i] = zipc_hip_stream_result{ZLIB_RESULT_UNSET, 0, 0};
+  }
+  const int st = many_streams(ctx, decompress, n, in_src.data(), in_len.data(), decompress ? limit : nullptr, level, zlib_crc_op(ctx),
+                              in_dst.data(), in_cap.data(), results);
+  for (size_t i = 0; i < n; i++) {
+    StreamResult inner{results[i].status, results[i].checksum, results[i].out_len};
+    if (inner.status == ZLIB_RESULT_UNSET) { inner.status = (uint32_t)(st ? st : ZIPC_HIP_ERR_HIP); inner.checksum = 0; inner.out_len = 0; }
+    StreamResult r;
+    if (decompress) {
+      r = zlib_close_decompress(pre[i].status, pre[i].expect, inner);
+    } else {
+      bool wrap;
+      r = zlib_close_compress(pre[i].status, inner, &wrap);
+      if (wrap) {
+        uint8_t *o = (uint8_t *)dst[i];
+        o[0] = (uint8_t)zlib_cmf();
+        o[1] = (uint8_t)zlib_flg(level);
+        zlib_put_trailer(o + 2 + inner.out_len, inner.checksum);
+      }
+    }
+    results[i] = zipc_hip_stream_result{r.status, r.checksum, r.out_len};
+  }
+  return st;
+}
+int zipc_hip_zlib_decompress_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len, const size_t *limit,
+                                  void *const *dst, const size_t *dst_cap, zipc_hip_stream_result *results) {
+  try { return zlib_many(ctx, true, n, src, src_len, limit, 0, dst, dst_cap, results); }
+  catch (...) { return many_threw(ctx, n, results); }
+}
+int zipc_hip_zlib_compress_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len, int level,
+                                void *const *dst, const size_t *dst_cap, zipc_hip_stream_result *results) {
+  try { return zlib_many(ctx, false, n, src, src_len, nullptr, level, dst, dst_cap, results); }
+  catch (...) { return many_threw(ctx, n, results); }
+}
+
+// zlib_decompress src/zipc_deflate.ml:720-740 (start = 0): the container's six bytes on the
+// host (zlib_container.h), body through the inflate kernel with Adler-32
 int zipc_hip_zlib_decompress(zipc_hip_ctx *ctx, const void *src, size_t len, int has_limit,
                              size_t limit, void *dst, size_t dst_cap, size_t *out_len,
                              uint32_t *adler, uint32_t *expect, uint32_t *found) {
   if (!ctx || (!src && len) || !out_len) return ZIPC_HIP_ERR_INVALID_ARG;
   *out_len = 0;
   const uint8_t *s = (const uint8_t *)src;
-  if (len < 6) return ZIPC_HIP_ERR_CORRUPTED;
-  const int cmf = s[0], flg = s[1];
-  if ((256 * cmf + flg) % 31 != 0) return ZIPC_HIP_ERR_CORRUPTED;
-  if ((cmf & 0x0F) != 8) return ZIPC_HIP_ERR_ZLIB_METHOD;
-  if ((cmf >> 4) > 7) return ZIPC_HIP_ERR_ZLIB_WINDOW;
-  if ((flg & 0x20) != 0) return ZIPC_HIP_ERR_ZLIB_DICT;
-  const uint32_t e = ((uint32_t)s[len - 4] << 24) | ((uint32_t)s[len - 3] << 16) |
-                     ((uint32_t)s[len - 2] << 8) | (uint32_t)s[len - 1];
+  const bool whole = len >= ZLIB_MIN_LEN;
+  const uint32_t pre = zlib_open_status(len, whole ? s[0] : 0, whole ? s[1] : 0);
+  if (pre != ST_OK) return (int)pre;
+  const uint32_t e = zlib_expect(s + len - 4);
   uint32_t f = 0;
   // the reference hands inflate the range [2, len-2) (src/zipc_deflate.ml:732)
-  int st = zipc_hip_inflate(ctx, s + 2, len - 4, has_limit, limit,
-                            ctx->adler_rfc1950 ? ZIPC_HIP_CRC_ADLER32_RFC1950 : ZIPC_HIP_CRC_ADLER32, dst, dst_cap,
+  int st = zipc_hip_inflate(ctx, s + zlib_body_off(0), (size_t)zlib_body_len(len), has_limit, limit, zlib_crc_op(ctx), dst, dst_cap,
                             out_len, &f);
   if (st) return st;
   if (expect) *expect = e;
@@ -1479,24 +1598,17 @@ int zipc_hip_zlib_compress(zipc_hip_ctx *ctx, const void *src, size_t len, int l
                            size_t dst_cap, size_t *out_len, uint32_t *adler) {
   if (!ctx || !dst || !out_len || level < 0 || level > 3) return ZIPC_HIP_ERR_INVALID_ARG;
   *out_len = 0;
-  if (dst_cap < 6) return ZIPC_HIP_ERR_DST_TOO_SMALL;
+  if (dst_cap < ZLIB_OVERHEAD) return ZIPC_HIP_ERR_DST_TOO_SMALL;
   uint8_t *o = (uint8_t *)dst;
-  const int cmf = (7 << 4) | 8;
-  const int header = (cmf << 8) | (level << 6);
-  const int flg = (header + 31 - (header % 31)) & 0xFF;
-  o[0] = (uint8_t)cmf;
-  o[1] = (uint8_t)flg;
+  o[0] = (uint8_t)zlib_cmf();
+  o[1] = (uint8_t)zlib_flg(level);
   size_t body = 0;
   uint32_t a = 0;
-  int st = zipc_hip_deflate(ctx, src, len, level,
-                            ctx->adler_rfc1950 ? ZIPC_HIP_CRC_ADLER32_RFC1950 : ZIPC_HIP_CRC_ADLER32, o + 2, dst_cap - 6,
+  int st = zipc_hip_deflate(ctx, src, len, level, zlib_crc_op(ctx), o + zlib_payload_off(0), (size_t)zlib_payload_cap(dst_cap),
                             &body, &a);
   if (st) return st;
-  o[2 + body] = (uint8_t)(a >> 24);
-  o[3 + body] = (uint8_t)(a >> 16);
-  o[4 + body] = (uint8_t)(a >> 8);
-  o[5 + body] = (uint8_t)a;
-  *out_len = body + 6;
+  zlib_put_trailer(o + 2 + body, a);
+  *out_len = body + ZLIB_OVERHEAD;
   if (adler) *adler = a;
   return ZIPC_HIP_OK;
 }

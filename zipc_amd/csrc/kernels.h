@@ -122,6 +122,14 @@ __global__ void stored_list_copy_kernel(const uint8_t *__restrict__ src_arena, u
                                         const StreamDesc *__restrict__ descs, const StoredBlock *__restrict__ list,
                                         uint32_t n_blocks);
 
+// ---- zlib.hip: the container around a batch's streams, a lane per stream (rules: zlib_container.h)
+struct ZlibPre { uint32_t status, expect; };  // the container check's verdict; to decompress, the Adler-32 the stream says it has
+__global__ void zlib_open_kernel(const uint8_t *__restrict__ src_arena, const StreamDesc *__restrict__ descs, uint32_t n_streams,
+                                 int compress, StreamDesc *__restrict__ inner, ZlibPre *__restrict__ pre);
+__global__ void zlib_close_kernel(uint8_t *__restrict__ dst_arena, const StreamDesc *__restrict__ descs,
+                                  const ZlibPre *__restrict__ pre, StreamResult *__restrict__ results, uint32_t n_streams,
+                                  int compress, int level);
+
 // ---- checksum.hip
 constexpr uint32_t CRC_PIECE_BYTES = 128;  // bytes per thread of crc32_segments_kernel
 constexpr uint32_t CRC_SEG_BYTES = 32768;   // per workgroup (256 threads)

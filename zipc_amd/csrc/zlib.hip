@@ -1,0 +1,86 @@
+// zlib.hip -- the zlib container of a batch of device-resident streams (zipc_hip_zlib_decompress_batch / _compress_batch).
+//
+// Two kernels around the codec's, a lane per stream each, six bytes of a stream touched between them:
+//   zlib_open_kernel   reads a stream's descriptor (and, to decompress, its two header and four trailer bytes), applies
+//                      the container's checks and writes the descriptor the codec is to run with -- the body of the
+//                      stream, or the room behind the header -- into the context's scratch, with the check's verdict;
+//   zlib_close_kernel  puts that verdict and the codec's result together: the Adler-32 compared with the stream's own,
+//                      or the header and the trailer stored around what deflate wrote.
+// The rules themselves are zlib_container.h's (the host forms and the tests compile the same functions).  Nothing is
+// read back: the calls enqueue and return like the raw batch forms.
+#include "kernels.h"
+#include "zlib_container.h"
+
+namespace zd {
+
+// A stream the codec is not to touch: nothing to read, no room to write.  (inflate reports a corrupted stream for it,
+// deflate a destination too small, neither stores a byte; zlib_close_kernel puts the container's verdict in its place.)
+__device__ __forceinline__ StreamDesc zlib_no_stream(const StreamDesc &sd) {
+  StreamDesc in = sd;
+  in.src_len = 0;
+  in.dst_cap = 0;
+  in.flags = 0;
+  return in;
+}
+
+__global__ __launch_bounds__(256) void zlib_open_kernel(const uint8_t *__restrict__ src_arena, const StreamDesc *__restrict__ descs,
+                                                        uint32_t n_streams, int compress, StreamDesc *__restrict__ inner,
+                                                        ZlibPre *__restrict__ pre) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_streams) return;
+  const StreamDesc sd = descs[i];
+  ZlibPre p;
+  p.status = ST_OK;
+  p.expect = 0;
+  StreamDesc in = sd;
+  if ((sd.flags & ~STREAM_HAS_LIMIT) != 0) {
+    p.status = ST_INVALID_ARG;
+  } else if (compress) {
+    if (sd.dst_cap < ZLIB_OVERHEAD) {
+      p.status = ST_DST_TOO_SMALL;
+    } else {
+      in.dst_off = zlib_payload_off(sd.dst_off);
+      in.dst_cap = zlib_payload_cap(sd.dst_cap);
+    }
+  } else {
+    uint32_t cmf = 0, flg = 0;
+    if (sd.src_len >= ZLIB_MIN_LEN) {  // (the reference looks at the length first, and so nothing is read of a shorter one)
+      const uint8_t *s = src_arena + sd.src_off;
+      cmf = s[0];
+      flg = s[1];
+      p.expect = zlib_expect(s + sd.src_len - 4);
+    }
+    p.status = zlib_open_status(sd.src_len, cmf, flg);
+    if (p.status == ST_OK) {
+      in.src_off = zlib_body_off(sd.src_off);
+      in.src_len = zlib_body_len(sd.src_len);
+    }
+  }
+  if (p.status != ST_OK) { in = zlib_no_stream(sd); p.expect = 0; }
+  inner[i] = in;
+  pre[i] = p;
+}
+
+__global__ __launch_bounds__(256) void zlib_close_kernel(uint8_t *__restrict__ dst_arena, const StreamDesc *__restrict__ descs,
+                                                         const ZlibPre *__restrict__ pre, StreamResult *__restrict__ results,
+                                                         uint32_t n_streams, int compress, int level) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_streams) return;
+  const ZlibPre p = pre[i];
+  const StreamResult inner = results[i];
+  if (!compress) {
+    results[i] = zlib_close_decompress(p.status, p.expect, inner);
+    return;
+  }
+  bool wrap;
+  const StreamResult r = zlib_close_compress(p.status, inner, &wrap);
+  if (wrap) {  // (inner.out_len <= dst_cap - 6: deflate said its bytes fit)
+    uint8_t *o = dst_arena + descs[i].dst_off;
+    o[0] = (uint8_t)zlib_cmf();
+    o[1] = (uint8_t)zlib_flg(level);
+    zlib_put_trailer(o + 2 + inner.out_len, inner.checksum);
+  }
+  results[i] = r;
+}
+
+}  // namespace zd

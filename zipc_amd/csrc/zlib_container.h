@@ -1,0 +1,78 @@
+// zlib_container.h -- the six bytes RFC 1950 puts around a deflate stream, as the reference reads and writes them: free
+// of HIP.
+//
+// zlib_decompress (src/zipc_deflate.ml:720-740) and zlib_compress (:1262-1277) are inflate / deflate with Adler-32 plus
+// the rules below.  They are pure functions of plain numbers, so the same code is compiled three times:
+//   * into zlib.hip's two kernels (zipc_hip_zlib_*_batch: a lane per stream opens and closes the container on the device);
+//   * into api.hip's host forms (zipc_hip_zlib_compress / _decompress and the *_many forms);
+//   * into tests/zlib_sim/sim_zlib.cpp with g++, where tests/test_zlib_rules.py holds every (CMF, FLG) pair to the oracle.
+#pragma once
+
+#include "zd_common.h"
+
+namespace zd {
+
+// the statuses of include/zipc_hip.h that only the container has (zd_common.h has the codec's)
+enum : uint32_t { ST_ZLIB_METHOD = 3, ST_ZLIB_WINDOW = 4, ST_ZLIB_DICT = 5, ST_CHECKSUM = 6 };
+
+constexpr uint64_t ZLIB_MIN_LEN = 6;   // CMF, FLG and the Adler-32: zd.ml:723
+constexpr uint64_t ZLIB_OVERHEAD = 6;  // what zlib_compress adds to deflate's bytes
+
+// The reference's checks of a stream of `len` bytes that begins with cmf, flg, in the reference's order (zd.ml:723-730).
+// (len < ZLIB_MIN_LEN: the two bytes are not looked at -- callers that cannot read them pass anything.)
+ZD_HD uint32_t zlib_open_status(uint64_t len, uint32_t cmf, uint32_t flg) {
+  if (len < ZLIB_MIN_LEN) return ST_CORRUPTED;
+  if ((256u * cmf + flg) % 31u != 0) return ST_CORRUPTED;
+  if ((cmf & 0x0Fu) != 8u) return ST_ZLIB_METHOD;
+  if ((cmf >> 4) > 7u) return ST_ZLIB_WINDOW;
+  if ((flg & 0x20u) != 0) return ST_ZLIB_DICT;
+  return ST_OK;
+}
+
+// What inflate is handed of a stream at [off, off + len): the range [2, len - 2) (zd.ml:732).  It ends two bytes
+// short of the stream, not four: the first two bytes of the trailer are inside it, and a deflate stream that runs into
+// them reads them as the reference does.  (len >= ZLIB_MIN_LEN.)
+ZD_HD uint64_t zlib_body_off(uint64_t off) { return off + 2; }
+ZD_HD uint64_t zlib_body_len(uint64_t len) { return len - 4; }
+
+// the Adler-32 a stream says it has: its last four bytes, big-endian (zd.ml:731)
+ZD_HD uint32_t zlib_expect(const uint8_t *last4) {
+  return ((uint32_t)last4[0] << 24) | ((uint32_t)last4[1] << 16) | ((uint32_t)last4[2] << 8) | (uint32_t)last4[3];
+}
+
+// what zlib_compress writes in front (zd.ml:1266-1270): deflate with a 32 KiB window, the level in FLG's top bits,
+// FCHECK making the two bytes a multiple of 31
+ZD_HD uint32_t zlib_cmf() { return (7u << 4) | 8u; }
+ZD_HD uint32_t zlib_flg(int level) {
+  const uint32_t header = (zlib_cmf() << 8) | ((uint32_t)level << 6);
+  return (header + 31u - header % 31u) & 0xFFu;
+}
+// where deflate's bytes go in a destination at [off, off + cap), and how many there may be (cap >= ZLIB_OVERHEAD)
+ZD_HD uint64_t zlib_payload_off(uint64_t off) { return off + 2; }
+ZD_HD uint64_t zlib_payload_cap(uint64_t cap) { return cap - ZLIB_OVERHEAD; }
+// ... and behind them (zd.ml:1274)
+ZD_HD void zlib_put_trailer(uint8_t *p, uint32_t adler) {
+  p[0] = (uint8_t)(adler >> 24);
+  p[1] = (uint8_t)(adler >> 16);
+  p[2] = (uint8_t)(adler >> 8);
+  p[3] = (uint8_t)adler;
+}
+
+// ---- a stream's result, from what the container check said before the codec ran (pre) and what the codec said (inner)
+// zlib_decompress: a stream that failed its own check says so; one that inflated to another Adler-32 than it says
+// reports the one found and no bytes (zd.ml:735-737); everything else is inflate's.
+ZD_HD StreamResult zlib_close_decompress(uint32_t pre, uint32_t expect, StreamResult inner) {
+  if (pre != ST_OK) { inner.status = pre; inner.checksum = 0; inner.out_len = 0; }
+  else if (inner.status == ST_OK && inner.checksum != expect) { inner.status = ST_CHECKSUM; inner.out_len = 0; }
+  return inner;
+}
+// zlib_compress: `inner` is deflate's, the result counts the container's bytes too.  *wrap: the caller has to put the
+// header and the trailer (inner.checksum, behind inner.out_len bytes of payload) around what deflate wrote.
+ZD_HD StreamResult zlib_close_compress(uint32_t pre, StreamResult inner, bool *wrap) {
+  *wrap = false;
+  if (pre != ST_OK) { inner.status = pre; inner.checksum = 0; inner.out_len = 0; }
+  else if (inner.status == ST_OK) { inner.out_len += ZLIB_OVERHEAD; *wrap = true; }
+  return inner;
+}
+
+}  // namespace zd

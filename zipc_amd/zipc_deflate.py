@@ -238,3 +238,80 @@ def zlib_compress(s, level=None, start=0, len=None, ctx=None):
     if st != OK:
         ctx.check(st)
     return Ok((adler.value, dst.raw[:out_len.value]))
+
+
+# ---- many streams in one call (include/zipc_hip.h zipc_hip_zlib_*_many): what a caller with a pack of git objects, the
+# IDAT chunks of many images or a table's pages uses instead of n calls of the two functions above.  The reference has
+# no such values; every element of the result is what the single-stream function gives for that stream.
+
+def _many_arrays(bufs):
+    n = len(bufs)
+    keep = [C.create_string_buffer(b, max(len(b), 1)) if isinstance(b, bytes) else b for b in bufs]
+    ptrs = (C.c_void_p * max(n, 1))(*[C.addressof(k) for k in keep])
+    return keep, ptrs
+
+
+def zlib_compress_many(streams, level=None, ctx=None):
+    """[zlib_compress(s, level) for s in streams] in one call: a list of Ok((adler, bytes))"""
+    ctx = ctx or default_context()
+    data = [bytes(s) for s in streams]
+    n = len(data)
+    if n == 0:
+        return []
+    caps = [lib().zipc_hip_zlib_bound(len(d)) for d in data]
+    keep, sp = _many_arrays(data)  # (the copies the pointers point into live until the call is through)
+    outs = [C.create_string_buffer(c) for c in caps]
+    _, dp = _many_arrays(outs)
+    res = (_lib.StreamResult * n)()
+    st = lib().zipc_hip_zlib_compress_many(ctx.handle, n, sp, (C.c_size_t * n)(*[len(d) for d in data]), _level(level), dp,
+                                           (C.c_size_t * n)(*caps), res)
+    if st != OK:
+        ctx.check(st)
+    for r in res:
+        if r.status != OK:
+            ctx.check(r.status)
+    del keep
+    return [Ok((int(r.checksum), o.raw[:r.out_len])) for r, o in zip(res, outs)]
+
+
+def zlib_decompress_many(streams, decompressed_size=None, ctx=None):
+    """[zlib_decompress(s, decompressed_size[i]) for s in streams] in one call: a list of Ok((bytes, adler)) |
+    Error(((expect, found) | None, msg)).  decompressed_size: None, or one size per stream.  Without sizes every stream
+    starts with room for three times its length, as zlib_decompress does, and the streams that need more go again."""
+    ctx = ctx or default_context()
+    data = [bytes(s) for s in streams]
+    n = len(data)
+    has_limit = decompressed_size is not None
+    if has_limit and len(decompressed_size) != n:
+        raise ValueError("decompressed_size: one size per stream")
+    out = [None] * n
+    todo = list(range(n))
+    caps = {i: (decompressed_size[i] if has_limit else max(3 * len(data[i]), 1024)) for i in todo}
+    while todo:
+        m = len(todo)
+        keep, sp = _many_arrays([data[i] for i in todo])  # (the copies the pointers point into live until the call is through)
+        bufs = [C.create_string_buffer(max(caps[i], 1)) for i in todo]
+        _, dp = _many_arrays(bufs)
+        res = (_lib.StreamResult * m)()
+        lim = (C.c_size_t * m)(*[decompressed_size[i] for i in todo]) if has_limit else None
+        st = lib().zipc_hip_zlib_decompress_many(ctx.handle, m, sp, (C.c_size_t * m)(*[len(data[i]) for i in todo]), lim, dp,
+                                                 (C.c_size_t * m)(*[caps[i] for i in todo]), res)
+        if st != OK:
+            ctx.check(st)
+        del keep
+        again = []
+        for i, r, b in zip(todo, res, bufs):
+            if r.status == ERR_DST_TOO_SMALL and not has_limit:
+                caps[i] *= 2
+                again.append(i)
+            elif r.status == OK:
+                out[i] = Ok((b.raw[:r.out_len], int(r.checksum)))
+            elif r.status == ERR_CHECKSUM:
+                expect = int.from_bytes(data[i][-4:], "big")  # (the result carries the value found: include/zipc_hip.h)
+                out[i] = Error(((expect, int(r.checksum)), crc_error(expect, int(r.checksum))))
+            elif r.status in (_lib.ERR_HIP, _lib.ERR_INVALID_ARG, _lib.ERR_NO_DEVICE, _lib.ERR_NOMEM):
+                ctx.check(r.status)
+            else:
+                out[i] = Error((None, _message(r.status, data[i][0] & 0x0F if data[i] else 0)))
+        todo = again
+    return out
