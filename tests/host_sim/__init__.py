@@ -51,6 +51,23 @@ def _bind(L):
     L.sim_inflate_blocks_pick.restype = C.c_uint64
     L.sim_inflate_blocks_pick.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32),
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    L.sim_blocks_caps.restype = None
+    L.sim_blocks_caps.argtypes = [C.c_uint64, C.c_uint64, u64p]
+    L.sim_blocks_read_candidates.restype = C.c_int
+    L.sim_blocks_read_candidates.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
+    L.sim_blocks_scratch.restype = C.c_uint64
+    L.sim_blocks_scratch.argtypes = [C.c_uint64, u64p, C.c_uint64, C.c_uint64, u64p, u64p]
+    L.sim_blocks_verdicts.restype = None
+    L.sim_blocks_verdicts.argtypes = [u64p, u64p]
+    L.sim_blocks_token_plan.restype = None
+    L.sim_blocks_token_plan.argtypes = [u64p, C.c_uint64, C.c_int, u64p, u64p]
+    L.sim_resolve_rounds.restype = C.c_int
+    L.sim_resolve_rounds.argtypes = [C.c_int, C.c_int]
+    L.sim_resolve_grid.restype = C.c_uint32
+    L.sim_resolve_grid.argtypes = [C.c_int, C.c_uint32]
+    L.sim_blocks_shares.restype = None
+    L.sim_blocks_shares.argtypes = [u32p, u32p, C.c_uint64, u64p, u64p, u64p]
     return L
 
 
@@ -115,3 +132,51 @@ def deflate_kernel_names(L, n, max_src_len, crc_op=1, **kw):
         else:
             names |= {"lz_parse", "deflate_emit"}
     return names
+
+
+# ---- zipc_amd/csrc/inflate_blocks.h through sim_forms.cpp: the rules of inflate by blocks between its launches
+BLOCKS_LISTS = ("counts", "first", "cand", "recs", "sorted", "sorted_src", "chain", "chain_end", "chain_iv", "cks", "stream")
+NO_MISS = (1 << 64) - 1  # FindCounts::miss_bit: the chain did not stop anywhere
+
+
+def blocks_caps(L, src_len, explore_stride=16384):
+    """(first_cap, cand_cap, max_explorers, rec_cap) of one stream's lists"""
+    out = (C.c_uint64 * 4)()
+    L.sim_blocks_caps(src_len, explore_stride, out)
+    return tuple(out)
+
+
+def blocks_scratch(L, src_lens, base=0, explore_stride=16384):
+    """carve_blocks_scratch -> (the end, where the counts and the job list begin, a dict of addresses per stream)"""
+    n = len(src_lens)
+    head, lists = (C.c_uint64 * 2)(), (C.c_uint64 * (len(BLOCKS_LISTS) * n))()
+    end = L.sim_blocks_scratch(base, (C.c_uint64 * n)(*src_lens), n, explore_stride, head, lists)
+    k = len(BLOCKS_LISTS)
+    return end, tuple(head), [dict(zip(BLOCKS_LISTS, lists[k * j:k * j + k])) for j in range(n)]
+
+
+def blocks_verdicts(L, src_len=1 << 20, explore_stride=16384, n_cand=1, chain_ok=1, miss_bit=NO_MISS, n_recs=0, n_blocks=2, out_len=1,
+                    token_bad=0, more_at=-1, rounds=6):
+    """what the host makes of one stream's counts: dict(found, chained, explorers, waves, taken, done)"""
+    out = (C.c_uint64 * 6)()
+    L.sim_blocks_verdicts((C.c_uint64 * 11)(src_len, explore_stride, n_cand, chain_ok, miss_bit, n_recs, n_blocks, out_len, token_bad,
+                                            more_at & NO_MISS, rounds), out)
+    return dict(zip(("found", "chained", "explorers", "waves", "taken", "done"), out))
+
+
+def blocks_token_plan(L, streams, follow_env=-1):
+    """streams: (src_len, chain_ok, n_blocks, out_len, n_intervals) -> (per stream None or dict(follow, n, tok_at, out_len),
+    call_out, tok_bytes)"""
+    n = len(streams)
+    out, total = (C.c_uint64 * (5 * n))(), (C.c_uint64 * 2)()
+    L.sim_blocks_token_plan((C.c_uint64 * (5 * n))(*[v for s in streams for v in s]), n, follow_env, out, total)
+    per = [dict(zip(("follow", "n", "tok_at", "out_len"), out[5 * j + 1:5 * j + 5])) if out[5 * j] else None for j in range(n)]
+    return per, total[0], total[1]
+
+
+def blocks_shares(L, waves, chunks):
+    """-> (span_at, span bytes, sums_at, sums bytes) of streams with that many waves / Adler chunks"""
+    n = len(waves)
+    span_at, sums_at, total = (C.c_uint64 * n)(), (C.c_uint64 * n)(), (C.c_uint64 * 2)()
+    L.sim_blocks_shares((C.c_uint32 * n)(*waves), (C.c_uint32 * n)(*chunks), n, span_at, sums_at, total)
+    return list(span_at), total[0], list(sums_at), total[1]

@@ -1,10 +1,11 @@
-// The launch rules of zipc_amd/csrc/forms.h and the scratch layout of deflate_scratch.h behind a C view.
-// TEST TOOLING ONLY: the very headers deflate.hip and api.hip compile, so that tests/test_host_sim.py can hold
+// The launch rules of zipc_amd/csrc/forms.h and inflate_blocks.h and the scratch layout of deflate_scratch.h behind a C view.
+// TEST TOOLING ONLY: the very headers deflate.hip, inflate.hip and api.hip compile, so that tests/test_host_sim.py can hold
 // every threshold to rows written out by hand.
 #include <string.h>
 
 #include "../../zipc_amd/csrc/deflate_scratch.h"
 #include "../../zipc_amd/csrc/forms.h"
+#include "../../zipc_amd/csrc/inflate_blocks.h"
 
 using namespace zd;
 
@@ -67,4 +68,114 @@ extern "C" uint64_t sim_inflate_blocks_pick(const uint64_t *src_len, const uint6
   for (size_t i = 0; i < e.size(); i++) group_ends[i] = e[i];
   *n_groups = e.size();
   return p.size();
+}
+
+// ---- inflate_blocks.h
+
+// out[4]: first_cap, cand_cap, max_explorers, rec_cap
+extern "C" void sim_blocks_caps(uint64_t src_len, uint64_t explore_stride, uint64_t *out) {
+  const BlocksJob J = blocks_job(0, src_len, explore_stride);
+  const uint64_t o[4] = {J.first_cap, J.cand_cap, blocks_max_explorers(src_len, explore_stride), J.rec_cap};
+  if (J.chain_cap != J.rec_cap) return;  // (one length for both lists: the rows would miss an unset out[])
+  memcpy(out, o, sizeof o);
+}
+
+extern "C" int sim_blocks_read_candidates(uint64_t nj, uint64_t src_len_of_first, uint64_t explore_stride) {
+  return blocks_read_candidates(nj, blocks_job(0, src_len_of_first, explore_stride).cand_cap) ? 1 : 0;
+}
+
+// the layout of a group of n streams carved from base: head[2] = counts, the job list; lists[11 * j ..]: stream j's counts,
+// first, cand, recs, sorted, sorted_src, chain, chain_end, chain_iv, cks, and the stream the job says it is; returns the end
+extern "C" uint64_t sim_blocks_scratch(uint64_t base, const uint64_t *src_len, uint64_t n, uint64_t explore_stride, uint64_t *head,
+                                       uint64_t *lists) {
+  std::vector<BlocksJob> jobs(n);
+  for (uint64_t j = 0; j < n; j++) jobs[j] = blocks_job((uint32_t)(100 + j), src_len[j], explore_stride);
+  FindCounts *counts;
+  BlocksJob *job_list;
+  const uint64_t end = carve_blocks_scratch((uintptr_t)base, jobs, counts, job_list);
+  head[0] = (uintptr_t)counts;
+  head[1] = (uintptr_t)job_list;
+  for (uint64_t j = 0; j < n; j++) {
+    const BlocksJob &J = jobs[j];
+    const uint64_t o[11] = {(uintptr_t)J.counts, (uintptr_t)J.first, (uintptr_t)J.cand, (uintptr_t)J.recs, (uintptr_t)J.sorted,
+                            (uintptr_t)J.sorted_src, (uintptr_t)J.chain, (uintptr_t)J.chain_end, (uintptr_t)J.chain_iv, (uintptr_t)J.cks,
+                            J.stream};
+    memcpy(lists + 11 * j, o, sizeof o);
+  }
+  return end;
+}
+
+// One stream's counts as the host reads them back.  in[11]: src_len, explore_stride, n_cand, chain_ok, miss_bit, n_recs,
+// n_blocks, out_len, token_bad, the resolve round whose more[] is set (or -1), rounds;
+// out[6]: found, chained (0 dropped, 1 kept, 2 lost), explorers and waves of the explore launch, taken into the token run, done
+extern "C" void sim_blocks_verdicts(const uint64_t *in, uint64_t *out) {
+  BlocksJob J = blocks_job(0, in[0], in[1]);
+  FindCounts c;
+  memset(&c, 0, sizeof c);
+  c.n_cand = (uint32_t)in[2];
+  c.chain_ok = (uint32_t)in[3];
+  c.miss_bit = in[4];
+  c.n_recs = (uint32_t)in[5];
+  c.n_blocks = (uint32_t)in[6];
+  c.out_len = in[7];
+  c.token_bad = (uint32_t)in[8];
+  if ((int64_t)in[9] >= 0) c.more[in[9]] = 1;
+  const uint64_t found = blocks_found(c, J), chained = (uint64_t)blocks_chained(c, J);
+  blocks_explore_waves(c, J, in[0], in[1]);
+  const uint64_t o[6] = {found, chained, J.n_blocks, J.n, blocks_token_taken(c), blocks_done(c, (int)in[10])};
+  memcpy(out, o, sizeof o);
+}
+
+// The token run of n streams.  per stream in[5 * j ..]: src_len, chain_ok, n_blocks, out_len, n_intervals;
+// out[5 * j ..]: taken, follow, n (its waves), where its tok[] begins in bytes, its output bytes as the job has them;
+// total[2]: call_out, tok_bytes
+extern "C" void sim_blocks_token_plan(const uint64_t *in, uint64_t n, int follow_env, uint64_t *out, uint64_t *total) {
+  std::vector<StreamDesc> sds(n);
+  std::vector<BlocksJob> jobs(n);
+  std::vector<FindCounts> fc(n);
+  std::vector<uint32_t> alive(n);
+  for (uint64_t j = 0; j < n; j++) {
+    memset(&sds[j], 0, sizeof(StreamDesc));
+    memset(&fc[j], 0, sizeof(FindCounts));
+    sds[j].src_len = in[5 * j];
+    jobs[j] = blocks_job((uint32_t)j, in[5 * j], 16384);
+    fc[j].chain_ok = (uint32_t)in[5 * j + 1];
+    fc[j].n_blocks = (uint32_t)in[5 * j + 2];
+    fc[j].out_len = in[5 * j + 3];
+    fc[j].n_intervals = (uint32_t)in[5 * j + 4];
+    alive[j] = (uint32_t)j;
+  }
+  const TokenPlan p = blocks_token_plan(jobs, fc, alive, sds.data(), follow_env);
+  memset(out, 0, 5 * n * sizeof(uint64_t));
+  for (size_t k = 0; k < p.taken.size(); k++) {
+    const BlocksJob &J = jobs[p.taken[k]];
+    const uint64_t o[5] = {1, (uint64_t)J.follow, J.n, p.tok_at[k], J.out_len};
+    memcpy(out + 5 * p.taken[k], o, sizeof o);
+  }
+  total[0] = p.call_out;
+  total[1] = p.tok_bytes;
+}
+
+extern "C" int sim_resolve_rounds(int hops0, int hops1) { return resolve_rounds(hops0, hops1); }
+extern "C" uint32_t sim_resolve_grid(int r, uint32_t out_grid) { return resolve_grid(r, out_grid); }
+
+// The shares of n streams in the buffers they share.  waves[n] -> span_at[n] (bytes), chunks[n] -> sums_at[n] (bytes);
+// total[2]: bytes of the span index, bytes of the Adler sums
+extern "C" void sim_blocks_shares(const uint32_t *waves, const uint32_t *chunks, uint64_t n, uint64_t *span_at, uint64_t *sums_at,
+                                  uint64_t *total) {
+  std::vector<BlocksJob> jobs(n);
+  std::vector<FindCounts> fc(n);
+  std::vector<uint32_t> which(n);
+  for (uint64_t j = 0; j < n; j++) {
+    memset(&jobs[j], 0, sizeof(BlocksJob));
+    memset(&fc[j], 0, sizeof(FindCounts));
+    jobs[j].n = waves[j];
+    fc[j].n_chunks = chunks[j];
+    which[j] = (uint32_t)j;
+  }
+  std::vector<size_t> at;
+  total[0] = blocks_span_slots(jobs, which, at);
+  for (uint64_t j = 0; j < n; j++) span_at[j] = at[j];
+  total[1] = blocks_adler_sums(fc, which, at);
+  for (uint64_t j = 0; j < n; j++) sums_at[j] = at[j];
 }

@@ -569,7 +569,7 @@ def test_corpus_every_chunk_against_the_oracle(gpu_ctx, oracle):
 
 def test_one_stream_of_48_mib_inflates_by_blocks_with_following(gpu_ctx, oracle):
     """48 MiB of text and 4-bit symbols in ONE stream -- long enough for the form in which a block's wave writes down
-    what its sources are copies of (api.hip: from 32 MiB of output on, output at least 1.5 x the input) -- as zlib
+    what its sources are copies of (inflate_blocks.h: from 32 MiB of output on, output at least 1.5 x the input) -- as zlib
     codes it and as the reference's encoder does (most of its blocks fixed: explorers): the source's bytes, CRC-32."""
     import zlib
 

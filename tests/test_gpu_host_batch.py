@@ -150,7 +150,7 @@ def test_many_streams_chunked_staging_equals_oracle(gpu_ctx, oracle):
 
 def test_a_few_long_members_inflate_by_blocks(gpu_ctx, oracle):
     """zipc_hip_inflate_many with a handful of long members (an archive of a few big files): each goes by a wave per
-    block (api.hip zipc_hip_inflate_batch), the damaged one and the one over its limit through the stream's one wave
+    block (inflate.hip launch_inflate), the damaged one and the one over its limit through the stream's one wave
     -- bytes, lengths, CRC-32 and statuses against the oracle, guard bytes intact"""
     from zipc_amd import _lib
 

@@ -825,3 +825,169 @@ def test_inflate_groups_cut_at_the_token_budget(sim):
     assert H.inflate_blocks_pick(sim, [(16 * MIB, 44739243)] * 3) == ([0, 1, 2], [1, 2, 3])
     # a member beyond the budget has a group to itself: 128 MiB is 1.5 GiB of scratch
     assert H.inflate_blocks_pick(sim, [(64 * MIB, 128 * MIB), (512 * KIB, MIB), (64 * MIB, 128 * MIB)]) == ([0, 1, 2], [1, 2, 3])
+
+
+# ---- inflate by blocks between its launches (zipc_amd/csrc/inflate_blocks.h).  As above, every expected value is the reading of
+# the launch code as it stood inline before the rules moved, with the arithmetic beside it; none is the header's own output.
+#   first_cap = src_len // 8 + 4096           cand_cap = min(src_len // 512 + 64, 65536)
+#   max_explorers = src_len // stride + 1     rec_cap = chain_cap = min(2 * cand_cap + 4 * max_explorers, 262144)
+def test_inflate_blocks_caps_equal_the_hand_written_rows(sim):
+    rows = [
+        # (src_len, stride) -> (first_cap, cand_cap, max_explorers, rec_cap)
+        ((40960, 16384), (5120 + 4096, 80 + 64, 2 + 1, 288 + 12)),
+        ((67108864, 16384), (8388608 + 4096, 65536, 4096 + 1, 131072 + 16388)),         # cand_cap capped (131072 + 64)
+        ((0x1FFFFFFF, 16384), (67108863 + 4096, 65536, 32767 + 1, 262144)),             # 131072 + 4 * 32768: exactly the cap
+        ((0x1FFFFFFF, 1024), (67108863 + 4096, 65536, 524287 + 1, 262144)),             # 131072 + 4 * 524288: capped
+        # cand_cap reaching 65536: 65471 + 64, 65472 + 64 (the cap itself, not capped), 65473 + 64 (capped)
+        ((33521663, 16384), (4190207 + 4096, 65535, 2045 + 1, 131070 + 8184)),
+        ((33521664, 16384), (4190208 + 4096, 65536, 2046 + 1, 131072 + 8188)),
+        ((33522176, 16384), (4190272 + 4096, 65536, 2046 + 1, 131072 + 8188)),
+        ((100000, 16384), (12500 + 4096, 195 + 64, 6 + 1, 518 + 28)),
+        ((5000000, 16384), (625000 + 4096, 9765 + 64, 305 + 1, 19658 + 1224)),
+    ]
+    for args, want in rows:
+        assert H.blocks_caps(sim, *args) == want, args
+
+
+def test_inflate_blocks_candidates_are_read_back_when_lists_are_long_or_many(sim):
+    # one stream: the kernels read the count themselves up to a list of 8192 (4161536 // 512 + 64 = 8192 = 4162047 // 512 + 64)
+    assert sim.sim_blocks_read_candidates(1, 4161536, 16384) == 0
+    assert sim.sim_blocks_read_candidates(1, 4162047, 16384) == 0
+    assert sim.sim_blocks_read_candidates(1, 4162048, 16384) == 1      # a list of 8193
+    assert sim.sim_blocks_read_candidates(1, 40 * KIB, 16384) == 0
+    assert sim.sim_blocks_read_candidates(2, 40 * KIB, 16384) == 1      # two streams, whatever their lists
+    assert sim.sim_blocks_read_candidates(64, 4161536, 16384) == 1
+
+
+_up256 = lambda v: (v + 255) // 256 * 256
+FIND_COUNTS_BYTES, BLOCKS_JOB_BYTES = 104, 144  # 4 + 2 words, 13 + 3 words, 4 words; 10 words and 13 pointers
+
+
+def _blocks_list_bytes(first_cap, cand_cap, rec_cap):
+    """a stream's nine lists in the order they lie: first | cand | recs | sorted | sorted_src | chain | chain_end | chain_iv | cks
+    (4-byte offsets, 32-byte BlockRec, 16-byte BlockStart, 24-byte BlockEnd, 8-byte ChainIv, 256-byte BlockCk for listed and walked)"""
+    return [first_cap * 4, cand_cap * 4, rec_cap * 32, rec_cap * 32, rec_cap * 4, rec_cap * 16, rec_cap * 24, rec_cap * 8,
+            (rec_cap + rec_cap) * 256]
+
+
+def test_inflate_blocks_scratch_is_one_layout_for_the_size_and_the_pointers(sim):
+    names = H.BLOCKS_LISTS[1:10]
+    # one stream of 40 KiB: caps 9216, 144, 300 (above)
+    end, head, lists = H.blocks_scratch(sim, [40960])
+    assert end == 256 + 256 + 36864 + 768 + 2 * 9728 + 1280 + 4864 + 7424 + 2560 + 153600 == 227328
+    assert end == _up256(FIND_COUNTS_BYTES) + _up256(BLOCKS_JOB_BYTES) + sum(_up256(b) for b in _blocks_list_bytes(9216, 144, 300))
+    assert head == (0, 256) and lists[0]["counts"] == 0 and lists[0]["first"] == 512 and lists[0]["stream"] == 100
+    # three streams of unequal length, their caps as the rows above have them
+    src_lens, caps = [40960, 100000, 5000000], [(9216, 144, 300), (16596, 259, 546), (629096, 9829, 20882)]
+    want_end = _up256(3 * FIND_COUNTS_BYTES) + _up256(3 * BLOCKS_JOB_BYTES) + sum(_up256(b) for c in caps for b in _blocks_list_bytes(*c))
+    end0, head0, lists0 = H.blocks_scratch(sim, src_lens)
+    assert end0 == want_end
+    # ... and from a base: every pointer is the base plus the running sum, in the documented order
+    for base in (0, (1 << 40) + 0x300):
+        end, head, lists = H.blocks_scratch(sim, src_lens, base=base)
+        assert end == base + want_end
+        assert head == (base, base + _up256(3 * FIND_COUNTS_BYTES))
+        at = base + _up256(3 * FIND_COUNTS_BYTES) + _up256(3 * BLOCKS_JOB_BYTES)
+        arrays = [(head[0], 3 * FIND_COUNTS_BYTES), (head[1], 3 * BLOCKS_JOB_BYTES)]
+        for j, c in enumerate(caps):
+            assert lists[j]["counts"] == base + j * FIND_COUNTS_BYTES and lists[j]["stream"] == 100 + j
+            for name, size in zip(names, _blocks_list_bytes(*c)):
+                assert lists[j][name] == at, (base, j, name)
+                arrays.append((at, size))
+                at += _up256(size)
+        assert at == end
+        # every array on a 256-byte boundary, no two overlap, none beyond the end
+        assert all(a % 256 == 0 for a, _ in arrays)
+        arrays.sort()
+        assert all(a + size <= b for (a, size), (b, _) in zip(arrays, arrays[1:])) and arrays[-1][0] + arrays[-1][1] <= end
+
+
+def test_inflate_blocks_verdicts_after_each_read_back(sim):
+    # 1 MiB of input: cand_cap 2048 + 64 = 2112, max_explorers 64 + 1, rec_cap 2 * 2112 + 4 * 65 = 4484; 8388608 bits,
+    # an explorer every 16384 * 8 = 131072 of them
+    v = lambda **kw: H.blocks_verdicts(sim, src_len=MIB, **kw)
+    # after the find: no candidate, or more than the list holds
+    assert [v(n_cand=n)["found"] for n in (0, 1, 2112, 2113)] == [0, 1, 1, 0]
+    assert [v(n_cand=n, chain_ok=0, miss_bit=5)["chained"] for n in (0, 2112, 2113)] == [0, 2, 0]  # dropped whatever the chain says
+    # after the first chain: lost only with a place where it stopped
+    assert v(chain_ok=0, miss_bit=0)["chained"] == 2
+    assert v(chain_ok=0, miss_bit=H.NO_MISS)["chained"] == 1
+    assert v(chain_ok=1, miss_bit=H.NO_MISS)["chained"] == 1
+    assert v(chain_ok=1, miss_bit=0)["chained"] == 1
+    # explorers: ceil(bits left / 131072) -- exactly three strides before the end 3, one bit earlier 4, the whole stream 64
+    lost = lambda miss_bit, n_recs=0, **kw: (lambda d: (d["explorers"], d["waves"]))(v(chain_ok=0, miss_bit=miss_bit, n_recs=n_recs, **kw))
+    assert lost(8388608 - 3 * 131072) == (3, 3)
+    assert lost(8388608 - 3 * 131072 - 1) == (4, 4)
+    assert lost(8388608 - 1) == (1, 1)
+    assert lost(0) == (64, 64)
+    # ... at most max_explorers.  A place inside the input never needs more (ceil(bits left / stride) <= src_len // stride + 1);
+    # the cap is what holds when the counts say a place two strides BEHIND the input, whose distance to the end wraps around:
+    # 65, not (2^64 - 262144 + 131071) // 131072
+    assert lost(8388608 + 2 * 131072) == (65, 65)
+    assert lost(8388608 + 2 * 131072, n_recs=7) == (65, 72)
+    assert H.blocks_verdicts(sim, src_len=MIB, explore_stride=1024, chain_ok=0, miss_bit=8388608 + 2 * 8192)["explorers"] == 1024 + 1
+    assert H.blocks_verdicts(sim, src_len=MIB, explore_stride=1024, chain_ok=0, miss_bit=8388608 - 8192 - 1)["explorers"] == 2
+    # followers: a wave per block listed so far, at most the list (n_recs counts on when it overflows)
+    assert lost(8388608 - 3 * 131072, n_recs=10) == (3, 13)
+    assert lost(8388608 - 3 * 131072, n_recs=4483) == (3, 3 + 4483)
+    assert lost(8388608 - 3 * 131072, n_recs=4484) == (3, 3 + 4484)
+    assert lost(8388608 - 3 * 131072, n_recs=4485) == (3, 3 + 4484)
+    assert lost(8388608 - 3 * 131072, n_recs=100000) == (3, 3 + 4484)
+    # into the token run: a chain of two blocks and more with output
+    assert v(chain_ok=1, n_blocks=2, out_len=1)["taken"] == 1
+    assert v(chain_ok=1, n_blocks=1, out_len=1)["taken"] == 0
+    assert v(chain_ok=1, n_blocks=2, out_len=0)["taken"] == 0
+    assert v(chain_ok=0, n_blocks=2, out_len=1)["taken"] == 0
+    # after the gather: done unless a block ended elsewhere or the LAST round left bytes short
+    assert v(rounds=6)["done"] == 1
+    assert v(rounds=6, token_bad=1)["done"] == 0
+    assert v(rounds=6, more_at=5)["done"] == 0
+    assert v(rounds=6, more_at=4)["done"] == 1
+    assert v(rounds=6, more_at=6)["done"] == 1
+    assert v(rounds=12, more_at=11)["done"] == 0
+    assert v(rounds=12, more_at=5)["done"] == 1
+
+
+def test_inflate_blocks_token_plan(sim):
+    plan = lambda streams, **kw: H.blocks_token_plan(sim, streams, **kw)
+    one = lambda src_len, out_len, **kw: plan([(src_len, 1, 5, out_len, 9)], **kw)[0][0]
+    # follow from 32 MiB of output of the whole call on: a wave per block (5) instead of one per interval (9)
+    assert one(MIB, 32 * MIB - 1) == dict(follow=0, n=9, tok_at=0, out_len=32 * MIB - 1)
+    assert one(MIB, 32 * MIB) == dict(follow=1, n=5, tok_at=0, out_len=32 * MIB)
+    per, call_out, _ = plan([(MIB, 1, 5, 16 * MIB, 9), (MIB, 1, 5, 16 * MIB, 9)])
+    assert call_out == 32 * MIB and [p["follow"] for p in per] == [1, 1]
+    per, call_out, _ = plan([(MIB, 1, 5, 16 * MIB, 9), (MIB, 1, 5, 16 * MIB - 1, 9)])
+    assert call_out == 32 * MIB - 1 and [p["follow"] for p in per] == [0, 0]
+    # (streams that stay out of the token run do not count: one block, no chain)
+    per, call_out, _ = plan([(MIB, 1, 1, 16 * MIB, 9), (MIB, 1, 5, 16 * MIB, 9), (MIB, 0, 5, 16 * MIB, 9)])
+    assert call_out == 16 * MIB and per[0] is None and per[2] is None and per[1]["follow"] == 0 and per[1]["tok_at"] == 0
+    # ... and output of at least 1.5 x the input: out_len * 2 against src_len * 3 = 90000003 / 90000000
+    assert one(30000001, 45000001)["follow"] == 0   # 90000002: one short
+    assert one(30000001, 45000002)["follow"] == 1
+    assert one(30000000, 44999999)["follow"] == 0
+    assert one(30000000, 45000000)["follow"] == 1   # equal
+    # the override wins both ways
+    assert one(MIB, 32 * MIB, follow_env=0) == dict(follow=0, n=9, tok_at=0, out_len=32 * MIB)
+    assert one(MIB, 100, follow_env=1) == dict(follow=1, n=5, tok_at=0, out_len=100)
+    assert one(MIB, 100, follow_env=-1)["follow"] == 0
+    # tok[]: three words per output byte in steps of 64 words -- 21 bytes: 63 -> 64 words, 22: 66 -> 128 -- one stream's behind the other's
+    per, _, tok_bytes = plan([(MIB, 1, 2, 21, 2), (MIB, 1, 2, 22, 2)])
+    assert [p["tok_at"] for p in per] == [0, 64 * 4] and tok_bytes == (64 + 128) * 4
+    per, _, tok_bytes = plan([(MIB, 1, 2, 22, 2), (MIB, 1, 1, 50, 2), (MIB, 1, 2, 21, 2)])
+    assert per[1] is None and [per[0]["tok_at"], per[2]["tok_at"]] == [0, 128 * 4] and tok_bytes == (128 + 64) * 4
+    assert plan([(MIB, 1, 2, 64, 2)])[2] == 192 * 4 and plan([(MIB, 1, 2, 65, 2)])[2] == 256 * 4
+    assert plan([(MIB, 1, 2, 43, 2)])[2] == 192 * 4  # 129 words: one beyond a step is a whole step more
+    # resolve rounds: 6 when both hop counts reach 16 (16^6 links), else all 12
+    assert [sim.sim_resolve_rounds(*h) for h in ((16, 16), (15, 16), (16, 15), (3, 5), (256, 256))] == [6, 12, 12, 12, 6]
+    # the resolve grid: the first round a thread per byte, later rounds 2048 workgroups at most
+    assert [sim.sim_resolve_grid(0, g) for g in (2047, 2048, 5000)] == [2047, 2048, 5000]
+    assert [sim.sim_resolve_grid(1, g) for g in (2047, 2048, 5000)] == [2047, 2048, 2048]
+    assert sim.sim_resolve_grid(5, 2049) == 2048
+
+
+def test_inflate_blocks_shares_of_the_span_index_and_the_adler_sums(sim):
+    # a slot of 64 * 18 * 2 = 2304 bytes per wave; three words per Adler chunk and a chunk to spare
+    span_at, span_bytes, sums_at, sums_bytes = H.blocks_shares(sim, [3, 0, 5], [4, 1, 7])
+    assert span_at == [0, 3 * 2304, 3 * 2304] and span_bytes == 8 * 2304
+    assert sums_at == [0, 4 * 12, 5 * 12] and sums_bytes == (12 + 1) * 12
+    assert H.blocks_shares(sim, [1], [0]) == ([0], 2304, [0], 12)

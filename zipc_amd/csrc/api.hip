@@ -1,9 +1,10 @@
-// api.hip -- the C ABI of include/zipc_hip.h: context, scratch, kernel launches.
+// api.hip -- the C ABI of include/zipc_hip.h: the context and its scratch, tuning(), the CRC-32 pass and the checksum
+// launches, the batch forms as argument checks around launch_deflate / launch_inflate (deflate.hip, inflate.hip), the
+// host forms, the many-stream pipeline's device half and the zlib forms.
 //
 // Host forms stage one stream through device scratch and run the same kernels as
 // the batch forms (a batch of one).  Nothing here computes on the CPU: with no
 // usable device the calls fail with ZIPC_HIP_ERR_NO_DEVICE / ZIPC_HIP_ERR_HIP.
-#include "../../include/zipc_hip.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,7 +14,6 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
-#include <deque>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -21,6 +21,7 @@
 #include "ctx.h"
 #include "deflate_scratch.h"
 #include "host_pipeline.h"
+#include "inflate_blocks.h"
 #include "tuning.h"
 #include "zlib_container.h"
 
@@ -28,15 +29,6 @@ using namespace zd;
 
 static_assert(sizeof(zipc_hip_stream_desc) == sizeof(StreamDesc), "desc layout");
 static_assert(sizeof(zipc_hip_stream_result) == sizeof(StreamResult), "result layout");
-
-#define HIP_TRY(ctx, expr)                                                             \
-  do {                                                                                 \
-    hipError_t _e = (expr);                                                            \
-    if (_e != hipSuccess) {                                                            \
-      (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);           \
-      return ZIPC_HIP_ERR_HIP;                                                         \
-    }                                                                                  \
-  } while (0)
 
 // ---- context internals -------------------------------------------------------
 
@@ -153,7 +145,7 @@ hipError_t zipc_hip_ctx::collect_times() {
   return hipSuccess;
 }
 
-static void free_buf(zipc_hip_ctx::Buf &b) {
+void zd::free_buf(zipc_hip_ctx::Buf &b) {
   if (b.p) (void)hipFree(b.p);
   b.p = nullptr;
   b.cap = 0;
@@ -265,13 +257,10 @@ hipError_t crc32_finish_launch(zipc_hip_ctx *ctx, int mode, const StreamDesc *d_
               partials, d_single_out);
   return hipGetLastError();
 }
-}  // namespace zd
-
-// the whole CRC-32 pass on ctx->cur; partials: the context's buffer from word `partials_at` on
-static int crc32_pass(zipc_hip_ctx *ctx, const uint8_t *base, int mode, const StreamDesc *d_descs,
-                      StreamResult *d_results, size_t n_ranges, uint64_t single_off,
-                      uint64_t single_len, size_t max_len, uint32_t *d_single_out, size_t partials_at = 0,
-                      bool ensured = false) {
+int crc32_pass(zipc_hip_ctx *ctx, const uint8_t *base, int mode, const StreamDesc *d_descs,
+               StreamResult *d_results, size_t n_ranges, uint64_t single_off,
+               uint64_t single_len, size_t max_len, uint32_t *d_single_out, size_t partials_at,
+               bool ensured) {
   const size_t segs = crc32_segs(max_len);
   if (n_ranges * segs > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
   if (!ensured) HIP_TRY(ctx, ctx->ensure(ctx->crc_partials, (partials_at + n_ranges * segs) * sizeof(uint32_t)));
@@ -281,6 +270,7 @@ static int crc32_pass(zipc_hip_ctx *ctx, const uint8_t *base, int mode, const St
   HIP_TRY(ctx, crc32_finish_launch(ctx, mode, d_descs, d_results, n_ranges, single_len, max_len, partials, d_single_out));
   return ZIPC_HIP_OK;
 }
+}  // namespace zd
 
 extern "C" {
 
@@ -451,468 +441,12 @@ size_t zipc_hip_zlib_bound(size_t len) { return zipc_hip_deflate_bound(len) + 6;
 
 // ---- batch forms ---------------------------------------------------------------
 
-// One stream beyond ZIPC_HIP_MAX_STREAM_LEN: the stored blocks it has to start with (inflate.hip) are found
-// and copied with 64-bit offsets -- a chain of equal blocks all at once, blocks of other lengths by a walk over
-// their headers -- and what follows, if anything, goes through the batch kernel as a stream of its own; the
-// results are put together.  A damaged or cut-short stored header, and a block that does not fit the limit,
-// get the reference's messages.  This path copies a few words to the host between its steps: it SYNCHRONISES
-// the context's stream, unlike the rest of zipc_hip_inflate_batch.
-static int inflate_huge_stream(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
-                               const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results, int crc_op) {
-  if (crc_op == ZIPC_HIP_CRC_ADLER32 || crc_op == ZIPC_HIP_CRC_ADLER32_RFC1950) return ZIPC_HIP_ERR_INVALID_ARG;
-  HIP_TRY(ctx, ctx->ensure(ctx->io_small, 256));
-  StoredChain *d_st = (StoredChain *)ctx->io_small.p;
-  StreamDesc sd;
-  HIP_TRY(ctx, hipMemcpyAsync(&sd, d_descs, sizeof sd, hipMemcpyDeviceToHost, ctx->stream));
-  ZD_LAUNCH(ctx, "stored_chain_probe", stored_chain_probe_kernel, dim3(1), dim3(1), 0, (const uint8_t *)d_src_arena,
-            (const StreamDesc *)d_descs, d_st);
-  StoredChain st;
-  HIP_TRY(ctx, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  StreamResult res;
-  res.status = ZIPC_HIP_ERR_INVALID_ARG; res.checksum = 0; res.out_len = 0;
-  uint64_t blocks = 0;
-  bool done = false;
-  if (st.len0 != 0 && st.candidates != 0) {
-    ZD_LAUNCH(ctx, "stored_chain_scan", stored_chain_scan_kernel, dim3((unsigned)(((uint64_t)st.candidates + 255) / 256)), dim3(256), 0,
-              (const uint8_t *)d_src_arena, (const StreamDesc *)d_descs, d_st);
-    HIP_TRY(ctx, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    blocks = st.first_bad;
-    if (st.final_at < blocks) { blocks = (uint64_t)st.final_at + 1; done = true; }  // the final block is one of the chain
-    // blocks that would overrun the destination are left to the walk below: it reports the reference's error
-    {
-      const uint64_t lim = (sd.flags & STREAM_HAS_LIMIT) ? sd.limit : ~0ull;
-      const uint64_t room = lim < sd.dst_cap ? lim : sd.dst_cap;
-      if (blocks * st.len0 > room) { blocks = room / st.len0; done = false; }
-    }
-    if (blocks)
-      ZD_LAUNCH(ctx, "stored_chain_copy", stored_chain_copy_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs, st.len0);
-  }
-  uint64_t used_src = blocks * (5ull + st.len0), made = blocks * (uint64_t)st.len0;
-  const uint64_t limit = (sd.flags & STREAM_HAS_LIMIT) ? sd.limit : ~0ull;
-  const uint64_t room_all = limit < sd.dst_cap ? limit : sd.dst_cap;
-  bool settled = done;  // the result is known without the batch kernel
-  if (done) {
-    res.status = ZIPC_HIP_OK;
-    res.out_len = made;
-  }
-  if (!settled) {
-    // stored blocks of other lengths: walked header by header (64 at a time while the length stays), listed and
-    // copied, a list at a time
-    constexpr uint32_t LIST_CAP = 1u << 20;
-    HIP_TRY(ctx, ctx->ensure(ctx->stored_list, (size_t)LIST_CAP * sizeof(StoredBlock)));
-    StoredWalk *d_walk = (StoredWalk *)((uint8_t *)ctx->io_small.p + 192);
-    static_assert(192 + sizeof(StoredWalk) <= 256, "io_small layout");
-    for (;;) {
-      StoredWalk w;
-      w.src_pos = used_src; w.dst_pos = made; w.room = room_all - made; w.n_blocks = 0; w.stop = WALK_MORE;
-      HIP_TRY(ctx, hipMemcpyAsync(d_walk, &w, sizeof w, hipMemcpyHostToDevice, ctx->stream));
-      ZD_LAUNCH(ctx, "stored_walk", stored_walk_kernel, dim3(1), dim3(64), 0, (const uint8_t *)d_src_arena,
-                (const StreamDesc *)d_descs, d_walk, (StoredBlock *)ctx->stored_list.p, LIST_CAP);
-      HIP_TRY(ctx, hipMemcpyAsync(&w, d_walk, sizeof w, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      if (w.n_blocks)
-        ZD_LAUNCH(ctx, "stored_list_copy", stored_list_copy_kernel, dim3(w.n_blocks < 65536u ? w.n_blocks : 65536u), dim3(256), 0,
-                  (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs,
-                  (const StoredBlock *)ctx->stored_list.p, w.n_blocks);
-      used_src = w.src_pos;
-      made = w.dst_pos;
-      if (w.stop == WALK_MORE && w.n_blocks) continue;  // the list was full
-      if (w.stop == WALK_FINAL) { res.status = ZIPC_HIP_OK; res.out_len = made; settled = true; }
-      else if (w.stop == WALK_CORRUPT) { res.status = ZIPC_HIP_ERR_CORRUPTED; settled = true; }  // zd.ml:672-677
-      else if (w.stop == WALK_ROOM) {  // Buf.add_string past the fixed size (zd.ml:29), or the caller's buffer is full
-        res.status = (sd.flags & STREAM_HAS_LIMIT) && limit <= sd.dst_cap ? ZIPC_HIP_ERR_SIZE_EXCEEDED : ZIPC_HIP_ERR_DST_TOO_SMALL;
-        settled = true;
-      }
-      break;  // WALK_OTHER: a block of another kind follows
-    }
-  }
-  if (!settled) {
-    StreamDesc rest = sd;
-    rest.src_off += used_src; rest.src_len -= used_src;
-    rest.dst_off += made; rest.dst_cap -= made;
-    if (rest.flags & STREAM_HAS_LIMIT) rest.limit -= made;
-    if (rest.src_len <= MAX_STREAM_LEN) {
-      if (rest.dst_cap > MAX_STREAM_LEN) rest.dst_cap = MAX_STREAM_LEN;  // (the rest is an ordinary stream: it may produce up to that much)
-      // the remainder's descriptor and result live in io_small, behind the StoredChain: the host forms hand
-      // THEIR descriptors in io_desc / io_res to this function (d_descs, d_results), which must stay as they are
-      // for the CRC pass below
-      zipc_hip_stream_desc *d_rest = (zipc_hip_stream_desc *)((uint8_t *)ctx->io_small.p + 64);
-      zipc_hip_stream_result *d_rest_res = (zipc_hip_stream_result *)((uint8_t *)ctx->io_small.p + 128);
-      static_assert(sizeof(StoredChain) <= 64 && sizeof(StreamDesc) <= 64 && 128 + sizeof(StreamResult) <= 192, "io_small layout");
-      HIP_TRY(ctx, hipMemcpyAsync(d_rest, &rest, sizeof rest, hipMemcpyHostToDevice, ctx->stream));
-      const int stb = zipc_hip_inflate_batch(ctx, d_src_arena, d_dst_arena, d_rest, d_rest_res, 1, (size_t)rest.dst_cap,
-                                             ZIPC_HIP_CRC_NOP);
-      if (stb) return stb;
-      HIP_TRY(ctx, hipMemcpyAsync(&res, d_rest_res, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      if (res.status == ZIPC_HIP_OK) res.out_len += made;
-      else res.out_len = 0;
-    }  // else: compressed blocks begin too early for the rest to be one ordinary stream (32-bit positions): INVALID_ARG stands
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(d_results, &res, sizeof res, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (crc_op == ZIPC_HIP_CRC_CRC32 && res.status == ZIPC_HIP_OK)
-    return crc32_pass(ctx, (const uint8_t *)d_dst_arena, RANGE_INFLATE_OUT, (const StreamDesc *)d_descs,
-                      (StreamResult *)d_results, 1, 0, 0, (size_t)res.out_len, nullptr);
-  return ZIPC_HIP_OK;
-}
-
-// Streams of at least BLOCKS_MIN_SRC bytes by a wave per block (inflate.hip: find, dry, explore, chain, token, resolve;
-// Adler-32 block by block as the reference updates it; CRC-32 is the caller's pass over the output).  The streams of
-// a call go through every step side by side -- the kernels' grids have them as their second dimension -- and the
-// host reads the counts of all of them back at once between the steps (three or four times a group, not per stream).
-// handled[i]: stream i went that way (its result is in d_results); else it is left to inflate_batch_kernel -- a stream
-// that is not a chain of dynamic blocks behind its first block, anything the dry run or the chain did not like: the
-// one-wave kernel owns the reference's messages.  It SYNCHRONISES the context's stream.  ZIPC_HIP_INFLATE_BLOCKS=0
-// turns it off.
-// (the BLOCKS_* limits, which streams go that way and in which groups: forms.h)
-static int inflate_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, uint8_t *dst, const StreamDesc *dd, StreamResult *d_results,
-                                const StreamDesc *sds, const uint32_t *streams, size_t nj, int crc_op, uint8_t *handled) {
-  const uint64_t EXPLORE_STRIDE = zd::tuning().explore_stride;  // bytes of input between two explorers
-  const bool adler = crc_op == ZIPC_HIP_CRC_ADLER32 || crc_op == ZIPC_HIP_CRC_ADLER32_RFC1950;
-  std::vector<BlocksJob> jobs(nj);
-  std::vector<uint32_t> max_explorers(nj);
-  // scratch: counts of every stream | the launches' job lists | per stream: first | cand | recs | sorted | sorted_src |
-  // chain | chain_end | chain_iv | cks (listed blocks, then blocks the chain walked)
-  size_t off = 0;
-  auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
-  const size_t o_counts = carve(nj * sizeof(FindCounts)), o_jobs = carve(nj * sizeof(BlocksJob));
-  struct Lists { size_t first, cand, recs, sorted, sorted_src, chain, chain_end, chain_iv, cks; };
-  std::vector<Lists> at(nj);
-  for (size_t j = 0; j < nj; j++) {
-    const StreamDesc &sd = sds[streams[j]];
-    BlocksJob &J = jobs[j];
-    memset(&J, 0, sizeof J);
-    J.stream = streams[j];
-    J.first_cap = (uint32_t)(sd.src_len / 8 + 4096);
-    J.cand_cap = (uint32_t)(sd.src_len / 512 + 64);
-    if (J.cand_cap > BLOCKS_CAND_CAP) J.cand_cap = BLOCKS_CAND_CAP;
-    // explorers (blocks without a findable header): one every EXPLORE_STRIDE bytes at most, 4 blocks listed each on average
-    max_explorers[j] = (uint32_t)(sd.src_len / EXPLORE_STRIDE + 1);
-    uint64_t rec_cap64 = 2ull * J.cand_cap + 4ull * max_explorers[j];  // (candidates, the blocks behind them, the explorers')
-    if (rec_cap64 > BLOCKS_REC_CAP) rec_cap64 = BLOCKS_REC_CAP;
-    J.rec_cap = J.chain_cap = (uint32_t)rec_cap64;
-    Lists &L = at[j];
-    L.first = carve((size_t)J.first_cap * 4); L.cand = carve((size_t)J.cand_cap * 4);
-    L.recs = carve((size_t)J.rec_cap * sizeof(BlockRec)); L.sorted = carve((size_t)J.rec_cap * sizeof(BlockRec));
-    L.sorted_src = carve((size_t)J.rec_cap * 4);
-    L.chain = carve((size_t)J.chain_cap * sizeof(BlockStart)); L.chain_end = carve((size_t)J.chain_cap * sizeof(BlockEnd));
-    L.chain_iv = carve((size_t)J.chain_cap * sizeof(ChainIv)); L.cks = carve(((size_t)J.rec_cap + J.chain_cap) * sizeof(BlockCk));
-  }
-  if (ctx->ensure(ctx->blocks_scratch, off) != hipSuccess) {
-    (void)hipGetLastError();  // (no room for the lists: the streams' one waves need none)
-    return ZIPC_HIP_OK;
-  }
-  uint8_t *base = (uint8_t *)ctx->blocks_scratch.p;
-  FindCounts *d_counts = (FindCounts *)(base + o_counts);
-  BlocksJob *d_jobs = (BlocksJob *)(base + o_jobs);
-  for (size_t j = 0; j < nj; j++) {
-    BlocksJob &J = jobs[j];
-    const Lists &L = at[j];
-    J.counts = d_counts + j;
-    J.first = (uint32_t *)(base + L.first); J.cand = (uint32_t *)(base + L.cand);
-    J.recs = (BlockRec *)(base + L.recs); J.sorted = (BlockRec *)(base + L.sorted);
-    J.sorted_src = (uint32_t *)(base + L.sorted_src);
-    J.chain = (BlockStart *)(base + L.chain); J.chain_end = (BlockEnd *)(base + L.chain_end);
-    J.chain_iv = (ChainIv *)(base + L.chain_iv); J.cks = (BlockCk *)(base + L.cks);
-  }
-  std::vector<FindCounts> fc(nj);
-  auto read_counts = [&]() -> hipError_t {
-    const hipError_t e = hipMemcpyAsync(fc.data(), d_counts, nj * sizeof(FindCounts), hipMemcpyDeviceToHost, ctx->stream);
-    return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
-  };
-  // a launch's streams: the jobs still on their way, as the kernels index them by blockIdx.y (the lists handed to
-  // the copies stay until the group is through)
-  std::deque<std::vector<BlocksJob>> handed;
-  auto hand = [&](const std::vector<uint32_t> &which) -> hipError_t {
-    handed.emplace_back();
-    std::vector<BlocksJob> &v = handed.back();
-    for (uint32_t j : which) v.push_back(jobs[j]);
-    return hipMemcpyAsync(d_jobs, v.data(), v.size() * sizeof(BlocksJob), hipMemcpyHostToDevice, ctx->stream);
-  };
-  // the span decoder's index, a slot per wave of a launch: every stream's waves behind those of the one before
-  auto span_slots = [&](const std::vector<uint32_t> &which) -> hipError_t {
-    size_t waves = 0;
-    for (uint32_t j : which) waves += jobs[j].n;
-    const hipError_t e = ctx->ensure(ctx->inflate_scratch, waves * INFLATE_SCRATCH_PER_STREAM);
-    if (e != hipSuccess) return e;
-    waves = 0;
-    for (uint32_t j : which) {
-      jobs[j].span = (uint16_t *)ctx->inflate_scratch.p + waves * (INFLATE_SCRATCH_PER_STREAM / 2);
-      waves += jobs[j].n;
-    }
-    return hipSuccess;
-  };
-  auto widest = [&](const std::vector<uint32_t> &which, auto need) {
-    unsigned w = 1;
-    for (uint32_t j : which) { const unsigned x = (unsigned)need(jobs[j], j); if (x > w) w = x; }
-    return w;
-  };
-  std::vector<uint32_t> alive(nj), keep;
-  for (size_t j = 0; j < nj; j++) alive[j] = (uint32_t)j;
-  const unsigned ny = (unsigned)nj;
-
-  HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, nj * sizeof(FindCounts), ctx->stream));
-  HIP_TRY(ctx, hand(alive));
-  ZD_LAUNCH(ctx, "inflate_find_headers", inflate_find_headers_kernel,
-            dim3(widest(alive, [&](const BlocksJob &J, uint32_t) { return (sds[J.stream].src_len + 1023) / 1024; }), ny), dim3(256), 0, src, dd,
-            (const BlocksJob *)d_jobs);
-  ZD_LAUNCH(ctx, "inflate_find_lengths", inflate_find_lengths_kernel,
-            dim3(widest(alive, [](const BlocksJob &J, uint32_t) { return (J.first_cap + 63u) / 64u; }), ny), dim3(64), 0, src, dd,
-            (const BlocksJob *)d_jobs);
-  // (how many candidates there are: the host asks when the lists are long or many -- a wave each is launched -- and lets
-  // the kernels read it themselves for one stream of a few MiB: a round trip less)
-  if (nj > 1 || jobs[0].cand_cap > 8192u) {
-    HIP_TRY(ctx, read_counts());
-    keep.clear();
-    for (uint32_t j : alive)
-      if (fc[j].n_cand != 0 && fc[j].n_cand <= jobs[j].cand_cap) { jobs[j].n = fc[j].n_cand; keep.push_back(j); }
-    alive.swap(keep);
-    if (alive.empty()) return ZIPC_HIP_OK;
-  } else {
-    jobs[0].n = jobs[0].cand_cap;
-  }
-  if (span_slots(alive) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }  // (no room for the waves' span index: the streams' one waves need 2304 bytes each)
-  HIP_TRY(ctx, hand(alive));
-  unsigned na = (unsigned)alive.size();
-  const unsigned dry_waves = widest(alive, [](const BlocksJob &J, uint32_t) { return J.n; });
-  ZD_LAUNCH(ctx, "inflate_blocks_dry", inflate_blocks_dry_kernel, dim3(dry_waves, na), dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs);
-  ZD_LAUNCH(ctx, "inflate_sort_blocks", inflate_sort_blocks_kernel, dim3((dry_waves + 255u) / 256u, na), dim3(256), 0, (const BlocksJob *)d_jobs);
-  ZD_LAUNCH(ctx, "inflate_chain", inflate_chain_kernel, dim3(1, na), dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs, 0);
-  HIP_TRY(ctx, read_counts());
-  keep.clear();
-  std::vector<uint32_t> lost;  // streams whose chain came to a block nobody listed
-  for (uint32_t j : alive) {
-    if (fc[j].n_cand == 0 || fc[j].n_cand > jobs[j].cand_cap) continue;
-    if (!fc[j].chain_ok && fc[j].miss_bit != ~0ull) lost.push_back(j);
-    keep.push_back(j);
-  }
-  alive.swap(keep);
-  if (!lost.empty()) {
-    // explorers from there on, then the chain again (which now walks what is still missing itself)
-    for (uint32_t j : lost) {
-      const uint64_t bits_left = sds[jobs[j].stream].src_len * 8u - fc[j].miss_bit;
-      uint64_t ne = (bits_left + EXPLORE_STRIDE * 8u - 1) / (EXPLORE_STRIDE * 8u);
-      if (ne > max_explorers[j]) ne = max_explorers[j];
-      // (behind the explorers a wave per block listed so far: the block that follows it, inflate.hip)
-      const uint32_t listed = fc[j].n_recs < jobs[j].rec_cap ? fc[j].n_recs : jobs[j].rec_cap;
-      jobs[j].n_blocks = (uint32_t)ne;
-      jobs[j].n = (uint32_t)ne + listed;
-    }
-    if (span_slots(lost) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }
-    HIP_TRY(ctx, hand(lost));
-    const unsigned nl = (unsigned)lost.size();
-    ZD_LAUNCH(ctx, "inflate_explore", inflate_explore_kernel, dim3(widest(lost, [](const BlocksJob &J, uint32_t) { return J.n; }), nl), dim3(64), 0,
-              src, dst, dd, (const BlocksJob *)d_jobs, (uint32_t)(EXPLORE_STRIDE * 8u));
-    ZD_LAUNCH(ctx, "inflate_sort_blocks", inflate_sort_blocks_kernel,
-              dim3(widest(lost, [](const BlocksJob &J, uint32_t) { return (J.rec_cap + 255u) / 256u; }), nl), dim3(256), 0, (const BlocksJob *)d_jobs);
-    ZD_LAUNCH(ctx, "inflate_chain", inflate_chain_kernel, dim3(1, nl), dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs, 1);
-    HIP_TRY(ctx, read_counts());
-  }
-  // (sources written down as what they are copies of -- inflate_span.h -- cost the token run 0.2-0.4 ms a block and a
-  // wave per block instead of one per interval, and save the resolve rounds of a long stream more: with 256 hops a
-  // round, 64 MiB of text 6.3-10.8 -> 5.7-6.5 ms, 16 MiB 2.7-4.4 <- 3.3-4.2)
-  const int follow_env = zd::tuning().inflate_follow;
-  // (what counts is the output of the whole call, whose bytes the rounds look at side by side: 64 x 1 MiB of text
-  // 5.8 -> 5.0 ms, 8 x 8 MiB 5.3 -> 4.7; 16 x 1 MiB 2.5 <- 3.2, one MiB 1.4 <- 2.4)
-  size_t call_out = 0;
-  for (uint32_t j : alive)
-    if (fc[j].chain_ok && fc[j].n_blocks >= 2) call_out += fc[j].out_len;
-  keep.clear();
-  size_t tok_words = 0;
-  for (uint32_t j : alive) {
-    if (!fc[j].chain_ok || fc[j].n_blocks < 2 || fc[j].out_len == 0) continue;  // (one block: nothing to gain)
-    BlocksJob &J = jobs[j];
-    J.out_len = (uint32_t)fc[j].out_len;
-    J.n_blocks = fc[j].n_blocks;
-    // (... and nothing on data with few matches: 16 MiB of records that deflate to 0.85, resolve 0.13 ms either way)
-    J.follow = follow_env >= 0 ? follow_env : call_out >= ((size_t)32 << 20) && (uint64_t)J.out_len * 2u >= sds[J.stream].src_len * 3u;
-    // the token run: a wave per interval of a block (its checkpoints), or -- follow -- a wave per block
-    J.n = J.follow ? J.n_blocks : fc[j].n_intervals;
-    tok_words += ((size_t)J.out_len * 3 + 63) & ~(size_t)63;
-    keep.push_back(j);
-  }
-  alive.swap(keep);
-  if (alive.empty()) return ZIPC_HIP_OK;
-  if (ctx->ensure(ctx->tok_scratch, tok_words * 4) != hipSuccess) {  // tok[], and two lists of bytes still to resolve
-    (void)hipGetLastError();  // (no room for a word per byte and the lists: the streams' one waves need none)
-    return ZIPC_HIP_OK;
-  }
-  tok_words = 0;
-  for (uint32_t j : alive) {
-    jobs[j].tok = (uint32_t *)ctx->tok_scratch.p + tok_words;
-    tok_words += ((size_t)jobs[j].out_len * 3 + 63) & ~(size_t)63;
-  }
-  if (span_slots(alive) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }  // (no room for the waves' span index: the streams' one waves need 2304 bytes each)
-  HIP_TRY(ctx, hand(alive));
-  na = (unsigned)alive.size();
-  const unsigned out_grid = widest(alive, [](const BlocksJob &J, uint32_t) { return (J.out_len + 255u) / 256u; });
-  ZD_LAUNCH(ctx, "inflate_tok_init", inflate_tok_init_kernel, dim3(out_grid, na), dim3(256), 0, (const BlocksJob *)d_jobs);
-  ZD_LAUNCH(ctx, "inflate_blocks_token", inflate_blocks_token_kernel, dim3(widest(alive, [](const BlocksJob &J, uint32_t) { return J.n; }), na),
-            dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs);
-  // (hops a thread follows in a round: 8 left most bytes of a text for the next round -- 16 MiB: three rounds over nearly
-  // everything, 3.4 ms; 64 and more let nearly every byte arrive in the first: 0.28 ms)
-  const int hops0 = zd::tuning().resolve_hops0, hops1 = zd::tuning().resolve_hops1;
-  const int rounds = hops0 >= 16 && hops1 >= 16 ? 6 : RESOLVE_ROUNDS;  // (16^6 links: more than a stream has bytes)
-  for (int r = 0; r < rounds; r++)
-    ZD_LAUNCH(ctx, "inflate_resolve", inflate_resolve_kernel, dim3(r == 0 || out_grid < 2048u ? out_grid : 2048u, na), dim3(256), 0,
-              (const BlocksJob *)d_jobs, r, r == 0 ? hops0 : hops1);
-  ZD_LAUNCH(ctx, "inflate_gather", inflate_gather_kernel, dim3(out_grid, na), dim3(256), 0, dst, dd, (const BlocksJob *)d_jobs);
-  HIP_TRY(ctx, read_counts());
-  // (12 bytes of scratch per output byte: what a long stream took goes back -- a context lives as long as its thread,
-  // and a 1 GiB member would pin 12 GiB per device; the stream is idle here, the gather has been waited for)
-  if (ctx->tok_scratch.cap > BLOCKS_TOK_BUDGET) free_buf(ctx->tok_scratch);
-  keep.clear();
-  size_t n_chunks = 0;
-  for (uint32_t j : alive) {
-    if (fc[j].token_bad != 0 || fc[j].more[rounds - 1] != 0) continue;  // (the one-wave kernel writes the output again)
-    n_chunks += fc[j].n_chunks;
-    keep.push_back(j);
-  }
-  alive.swap(keep);
-  if (alive.empty()) return ZIPC_HIP_OK;
-  na = (unsigned)alive.size();
-  if (adler) {  // block by block, every block's bytes in chunks of their own (inflate.hip)
-    if (ctx->ensure(ctx->adler_sums, (n_chunks + 1) * 12) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }  // (the one waves write output and checksum again)
-    n_chunks = 0;
-    for (uint32_t j : alive) { jobs[j].sums = (uint32_t *)ctx->adler_sums.p + n_chunks * 3; n_chunks += fc[j].n_chunks; }
-  }
-  HIP_TRY(ctx, hand(alive));
-  ZD_LAUNCH(ctx, "inflate_blocks_result", inflate_blocks_result_kernel, dim3((na + 63u) / 64u), dim3(64), 0, (const BlocksJob *)d_jobs, d_results, na);
-  if (adler) {
-    if (n_chunks)
-      ZD_LAUNCH(ctx, "inflate_adler_chunks", inflate_adler_chunks_kernel, dim3(widest(alive, [&](const BlocksJob &, uint32_t j) { return fc[j].n_chunks; }), na),
-                dim3(64), 0, (const uint8_t *)dst, dd, (const BlocksJob *)d_jobs);
-    ZD_LAUNCH(ctx, "inflate_adler_fold", inflate_adler_fold_kernel, dim3(1, na), dim3(64), 0, (const BlocksJob *)d_jobs,
-              crc_op == ZIPC_HIP_CRC_ADLER32_RFC1950 ? 1 : 0, d_results);
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the lists handed to the copies go with this frame)
-  for (uint32_t j : alive) { handled[jobs[j].stream] = 1; ctx->last_inflate_blocks += jobs[j].n_blocks; }
-  return ZIPC_HIP_OK;
-}
-
-// which of a call's streams go by blocks, group by group; *n_handled: how many did
-// h_descs: the caller's own host copy of the descriptors (the many-stream host forms have one), or null: they are read
-// back from the device, which waits for everything the stream holds -- the host forms feed sub-batch g + 1 while g's
-// kernels run, and a read-back per sub-batch (before the model below had even said whether any stream goes by blocks:
-// for an archive of equal members none does) put the host behind every sub-batch's copies and kernels.
-static int inflate_by_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
-                             zipc_hip_stream_result *d_results, size_t n_streams, int crc_op, std::vector<StreamDesc> &sds,
-                             std::vector<uint8_t> &handled, size_t *n_handled, const StreamDesc *h_descs) {
-  *n_handled = 0;
-  handled.assign(n_streams, 0);
-  if (!zd::tuning().inflate_blocks) return ZIPC_HIP_OK;
-  if (h_descs) {
-    sds.assign(h_descs, h_descs + n_streams);
-  } else {
-    sds.resize(n_streams);
-    HIP_TRY(ctx, hipMemcpyAsync(sds.data(), d_descs, n_streams * sizeof(StreamDesc), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  const std::vector<uint32_t> picked = inflate_blocks_pick(sds.data(), n_streams);
-  size_t begin = 0;
-  for (size_t end : inflate_blocks_groups(sds.data(), picked)) {
-    const int st = inflate_blocks_group(ctx, (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs,
-                                        (StreamResult *)d_results, sds.data(), picked.data() + begin, end - begin, crc_op, handled.data());
-    if (st) return st;
-    begin = end;
-  }
-  for (size_t i = 0; i < n_streams; i++) *n_handled += handled[i];
-  return ZIPC_HIP_OK;
-}
-
-static int inflate_batch_one_wave(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
-                                  zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op, bool marked = false);
-static int inflate_batch_impl(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
-                              zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op, const StreamDesc *h_descs,
-                              bool first_of_call);
-
 int zipc_hip_inflate_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
                            const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
                            size_t n_streams, size_t max_dst_cap, int crc_op) {
-  return inflate_batch_impl(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, max_dst_cap, crc_op, nullptr, true);
-}
-
-// first_of_call: zipc_hip_last_inflate_blocks counts from zero (the host forms' sub-batches add up)
-static int inflate_batch_impl(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
-                              zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op, const StreamDesc *h_descs,
-                              bool first_of_call) {
   if (!ctx || !d_descs || !d_results) return ZIPC_HIP_ERR_INVALID_ARG;
   if (crc_op < 0 || crc_op > 3 || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
-  if (first_of_call) ctx->last_inflate_blocks = 0;  // (also for a call that never reaches the block path: "0 when the stream's one wave decoded it")
-  if (n_streams == 0) return ZIPC_HIP_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (n_streams == 1 && max_dst_cap > MAX_STREAM_LEN)
-    return inflate_huge_stream(ctx, d_src_arena, d_dst_arena, d_descs, d_results, crc_op);
-  if (inflate_blocks_gate(n_streams, max_dst_cap)) {
-    std::vector<StreamDesc> sds;
-    std::vector<uint8_t> handled;
-    size_t n_handled = 0;
-    const int by = inflate_by_blocks(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, crc_op, sds, handled, &n_handled, h_descs);
-    if (by != ZIPC_HIP_OK) return by;
-    if (n_handled == n_streams) {
-      if (crc_op != ZIPC_HIP_CRC_CRC32) return ZIPC_HIP_OK;
-      return crc32_pass(ctx, (const uint8_t *)d_dst_arena, RANGE_INFLATE_OUT, (const StreamDesc *)d_descs, (StreamResult *)d_results,
-                        n_streams, 0, 0, max_dst_cap, nullptr);
-    }
-    if (n_handled) {
-      // the others by their one waves, over a copy of the descriptors that says which streams are through (the CRC
-      // pass behind the kernel takes every stream's output as it finds it in d_results)
-      for (size_t i = 0; i < n_streams; i++)
-        if (handled[i]) sds[i].flags |= STREAM_DONE;
-      HIP_TRY(ctx, ctx->ensure(ctx->descs_marked, n_streams * sizeof(StreamDesc)));
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->descs_marked.p, sds.data(), n_streams * sizeof(StreamDesc), hipMemcpyHostToDevice, ctx->stream));
-      const int st = inflate_batch_one_wave(ctx, d_src_arena, d_dst_arena, (const zipc_hip_stream_desc *)ctx->descs_marked.p, d_results,
-                                            n_streams, max_dst_cap, crc_op, true);
-      const hipError_t e = hipStreamSynchronize(ctx->stream);  // (sds goes with this frame)
-      if (st == ZIPC_HIP_OK) HIP_TRY(ctx, e);
-      return st;
-    }
-  }
-  return inflate_batch_one_wave(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, max_dst_cap, crc_op);
-}
-
-// the batch kernel: one wave per stream
-static int inflate_batch_one_wave(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
-                                  zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op, bool marked) {
-  const int k_crc_op = crc_op | (marked ? CRC_OP_MARKED : 0);  // what the kernels are told (inflate.hip inflate_skips_stream)
-  // one wave per stream (in slices on queues of their own, the CRC pass of one slice beside the inflate kernel of
-  // the next: two by default, forms.h batch_slices)
-  HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_streams * INFLATE_SCRATCH_PER_STREAM));
-  const size_t segs = crc32_segs(max_dst_cap);
-  if (crc_op == ZIPC_HIP_CRC_CRC32) {
-    if (n_streams * segs > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
-    HIP_TRY(ctx, ctx->ensure(ctx->crc_partials, n_streams * segs * sizeof(uint32_t)));
-  }
-  const size_t k = crc_op == ZIPC_HIP_CRC_CRC32 ? batch_slices(n_streams, zd::tuning(), debug_slices_override()) : 1;
-  if (k > 1) HIP_TRY(ctx, ctx->fork(k));
-  int st = ZIPC_HIP_OK;
-  for (size_t i = 0; i < k && st == ZIPC_HIP_OK; i++) {
-    const size_t lo = n_streams * i / k, hi = n_streams * (i + 1) / k;
-    if (k > 1) ctx->use_slice_stream(i);
-    const StreamDesc *dd = (const StreamDesc *)d_descs + lo;
-    StreamResult *dr = (StreamResult *)d_results + lo;
-    if (inflate_few_streams(n_streams))
-      ZD_LAUNCH(ctx, "inflate_batch", inflate_batch_few_kernel, dim3((unsigned)(hi - lo)), dim3(64), 0,
-                (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, dd, dr, (uint32_t)(hi - lo),
-                (uint16_t *)ctx->inflate_scratch.p + lo * (INFLATE_SCRATCH_PER_STREAM / 2), k_crc_op);
-    else
-      ZD_LAUNCH(ctx, "inflate_batch", inflate_batch_kernel, dim3((unsigned)(hi - lo)), dim3(64), 0,
-                (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, dd, dr, (uint32_t)(hi - lo),
-                (uint16_t *)ctx->inflate_scratch.p + lo * (INFLATE_SCRATCH_PER_STREAM / 2), k_crc_op);
-    if (hipGetLastError() != hipSuccess) { ctx->last_error = "inflate_batch launch failed"; st = ZIPC_HIP_ERR_HIP; break; }
-    if (crc_op == ZIPC_HIP_CRC_CRC32)
-      st = crc32_pass(ctx, (const uint8_t *)d_dst_arena, RANGE_INFLATE_OUT, dd, dr, hi - lo, 0, 0, max_dst_cap, nullptr,
-                      lo * segs, true);
-  }
-  if (k > 1) {
-    const hipError_t e = ctx->join(k);
-    if (st == ZIPC_HIP_OK) HIP_TRY(ctx, e);
-  }
-  return st;
+  return launch_inflate(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, max_dst_cap, crc_op, nullptr, true);
 }
 
 int zipc_hip_deflate_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
@@ -1342,7 +876,7 @@ static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void
       for (size_t i = lo; i < hi; i++) total_g += src_len[i];
       int st;
       if (is_inflate)  // (with the descriptors it has on the host: no read-back, nothing waited for unless a stream goes by blocks)
-        st = inflate_batch_impl(ctx, ctx->io_src.p, ctx->io_dst.p, dd, dr, hi - lo, max_cap, crc_op, descs.data() + lo, first_batch);
+        st = launch_inflate(ctx, ctx->io_src.p, ctx->io_dst.p, dd, dr, hi - lo, max_cap, crc_op, descs.data() + lo, first_batch);
       else
         st = zipc_hip_deflate_batch(ctx, ctx->io_src.p, ctx->io_dst.p, dd, dr, hi - lo, max_src, total_g, level, crc_op);
       first_batch = false;
@@ -1473,7 +1007,7 @@ int zipc_hip_zlib_decompress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, v
                                    zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap) {
   if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
   if (n_streams == 0) return ZIPC_HIP_OK;
-  if (n_streams == 1 && max_dst_cap > MAX_STREAM_LEN) return ZIPC_HIP_ERR_INVALID_ARG;  // (that path has no Adler-32: inflate_huge_stream)
+  if (n_streams == 1 && max_dst_cap > MAX_STREAM_LEN) return ZIPC_HIP_ERR_INVALID_ARG;  // (that path has no Adler-32: inflate.hip inflate_huge_stream)
   int st = zlib_open(ctx, d_src_arena, d_descs, n_streams, 0);
   if (st) return st;
   st = zipc_hip_inflate_batch(ctx, d_src_arena, d_dst_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, d_results, n_streams,

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/zipc_hip.h"
 #include "kernels.h"
 
 struct zipc_hip_ctx {
@@ -82,7 +83,19 @@ struct zipc_hip_ctx {
     if ((ctx)->profiling) (ctx)->end(name, _zd_start);                            \
   } while (0)
 
+// a HIP call of a function that returns a ZIPC_HIP_* status: a failure is written down and ends it
+#define HIP_TRY(ctx, expr)                                                             \
+  do {                                                                                 \
+    hipError_t _e = (expr);                                                            \
+    if (_e != hipSuccess) {                                                            \
+      (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);           \
+      return ZIPC_HIP_ERR_HIP;                                                         \
+    }                                                                                  \
+  } while (0)
+
 namespace zd {
+// api.hip: a buffer of the context's scratch goes back to the device (the stream must be idle)
+void free_buf(zipc_hip_ctx::Buf &b);
 // api.hip: zipc_hip_debug_set_slices' number of slices for forms.h batch_slices (0: none set)
 long debug_slices_override();
 // api.hip: the two halves of the CRC-32 pass over n_ranges ranges of up to max_len bytes, on ctx->cur.
@@ -94,6 +107,10 @@ hipError_t crc32_segments_launch(zipc_hip_ctx *ctx, const uint8_t *base, int mod
 hipError_t crc32_finish_launch(zipc_hip_ctx *ctx, int mode, const StreamDesc *d_descs, StreamResult *d_results,
                                size_t n_ranges, uint64_t single_len, size_t max_len, const uint32_t *partials,
                                uint32_t *d_single_out);
+// ... and the whole pass (a ZIPC_HIP_* status); partials: the context's buffer from word `partials_at` on, grown here unless `ensured`
+int crc32_pass(zipc_hip_ctx *ctx, const uint8_t *base, int mode, const StreamDesc *d_descs, StreamResult *d_results,
+               size_t n_ranges, uint64_t single_off, uint64_t single_len, size_t max_len, uint32_t *d_single_out,
+               size_t partials_at = 0, bool ensured = false);
 // deflate.hip: the probe behind ctx->xchg_ordered
 bool xchg_order_probe(zipc_hip_ctx *ctx);
 // deflate.hip (tests): the links one of the two chain kernels makes of a batch, and how many link slots that takes
@@ -104,4 +121,10 @@ size_t debug_chain_positions(size_t n, size_t total_src_len);
 hipError_t launch_deflate(zipc_hip_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst,
                           const StreamDesc *d_descs, StreamResult *d_results, size_t n_streams,
                           size_t max_src_len, size_t total_src_len, int level, int crc_op);
+// inflate.hip: zipc_hip_inflate_batch behind its argument checks (a ZIPC_HIP_* status).  h_descs: the caller's own host copy
+// of the descriptors, or null: the block path reads them back; first_of_call: zipc_hip_last_inflate_blocks counts from zero
+// (the many-stream host forms' sub-batches add up)
+int launch_inflate(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                   zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op, const StreamDesc *h_descs,
+                   bool first_of_call);
 }  // namespace zd

@@ -2,7 +2,7 @@
 //
 // Every rule the launch code follows between its ZD_LAUNCH lines is a pure function of plain numbers here (no context,
 // no environment: the switches come in as a Tuning), so that the same code is compiled twice:
-//   * into libzipc_hip.so (deflate.hip launch_deflate_group, api.hip inflate_batch_impl: they compute the forms, then launch);
+//   * into libzipc_hip.so (deflate.hip launch_deflate_group, inflate.hip launch_inflate: they compute the forms, then launch);
 //   * into tests/host_sim/sim_forms.cpp with g++, where tests/test_host_sim.py pins both sides of every threshold.
 // The constants the rules share with the kernels live here too.  DESIGN.md section 4.0 is a summary of this file.
 #pragma once
@@ -266,7 +266,8 @@ inline DeflateSliceForms deflate_slice_forms(const DeflateForms &f, size_t m) {
 }
 
 // ---------------------------------------------------------------------------------
-// inflate: streams of at least BLOCKS_MIN_SRC bytes by a wave per block (api.hip inflate_by_blocks)
+// inflate: streams of at least BLOCKS_MIN_SRC bytes by a wave per block (inflate.hip inflate_by_blocks; the rules between
+// that path's launches: inflate_blocks.h)
 constexpr size_t BLOCKS_MIN_SRC = 40u << 10, BLOCKS_MAX_SRC = 0x1FFFFFFFull;  // (bit offsets are 32-bit words here)
 constexpr uint32_t BLOCKS_CAND_CAP = 65536, BLOCKS_REC_CAP = 262144;
 // (a call whose descriptors are worth reading back: its longest stream alone is 4 ms of one wave.  Round 4 began with

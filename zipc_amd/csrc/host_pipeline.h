@@ -341,7 +341,7 @@ int many_pipeline(const ManyJob<Desc> &job, Device &dev, Pools &pools, std::stri
         if (times) times->gathered[g] = since(t_begin);
         return lo < hi ? dev.sent(g) : ZIPC_HIP_OK;
       };
-      // Long members' inflate may go by blocks inside inflate_batch, which waits for the device on the way (api.hip
+      // Long members' inflate may go by blocks inside inflate_batch, which waits for the device on the way (inflate.hip
       // inflate_by_blocks): the NEXT sub-batch's sources are gathered and sent before this one's kernels are asked for, or
       // they would not leave the host before those kernels are through (256 x 1 MiB: 22.0 -> 21.4 ms: what is left is the
       // blocks' kernels, 7-8 ms a sub-batch of 128 MiB).  Everywhere else the kernels of a sub-batch are enqueued the

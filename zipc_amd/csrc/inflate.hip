@@ -43,15 +43,19 @@
 // the same wave code in two more modes -- IM_DRY walks a block for its end and size, IM_TOKEN stores its literals
 // and writes down what its matches copy -- around a search for block headers, a chain of the blocks and pointer
 // jumping over the copies.
+// The launch code is the last section (zd::launch_inflate); its rules between two launches: forms.h, inflate_blocks.h.
+#include <deque>
+
+#include "ctx.h"
+#include "inflate_blocks.h"
+#include "inflate_find.h"
 #include "inflate_lane.h"
 #include "inflate_span.h"
-#include "inflate_find.h"
-#include "kernels.h"
+#include "tuning.h"
 #include "wave_ops.h"
 
 namespace zd {
 
-static_assert(LDS_BYTES_PER_LANE == INFLATE_LDS_BYTES_PER_LANE, "kernels.h");
 static_assert(SPEC_WINDOW == 64 && QUEUE_ENTRIES <= 64, "one lane per offset / per queue entry");
 constexpr int ROUND_TURNS = 24;  // wide turns between two service points
 
@@ -622,7 +626,7 @@ struct Explore {
   // block before does for a stream's wave (prev_block_bits)
   uint32_t est_bits;
 };
-static_assert(CK_MAX == BLOCK_CK_MAX, "kernels.h");
+static_assert(CK_MAX == BLOCK_CK_MAX, "inflate_blocks.h");
 constexpr uint64_t NO_BIT = ~0ull;
 __device__ __forceinline__ Explore no_explore() {
   Explore X;
@@ -961,7 +965,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
 }
 
 // A descriptor's flags before its wave starts.  STREAM_DONE is the library's own mark, in its own copy of a call's
-// descriptors (api.hip: the stream went by blocks, its result stands) -- such launches say so in crc_op (CRC_OP_MARKED).
+// descriptors (launch_inflate: the stream went by blocks, its result stands) -- such launches say so in crc_op (CRC_OP_MARKED).
 // In a caller's descriptors that bit, like every bit but STREAM_HAS_LIMIT, is an invalid argument and is reported as one
 // (it used to skip the stream silently and leave whatever its result slot held).
 __device__ __forceinline__ bool inflate_skips_stream(uint32_t flags, int &crc_op, StreamResult *result) {
@@ -992,7 +996,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   inflate_wave<IM_REAL>(lds_raw, src_arena, dst_arena, descs[stream], at, results + stream,
                         span_scratch + (size_t)stream * SPAN_IDX_ENTRIES, nullptr, crc_op);
 }
-// the same for calls of a few streams (api.hip: up to 256), where a wave has more to itself than its share of a full
+// the same for calls of a few streams (forms.h inflate_few_streams: up to 256), where a wave has more to itself than its share of a full
 // GPU and a stream of runs -- blocks of a few hundred matches with one and the same header -- is not lost in a batch:
 // REUSE (inflate_wave)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void inflate_batch_few_kernel(const uint8_t *__restrict__ src_arena,
@@ -1466,7 +1470,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   }
 }
 
-// Pointer jumping, up to `hops` hops a thread and round (api.hip: 256): a pointer only ever moves to an earlier byte of the
+// Pointer jumping, up to `hops` hops a thread and round (tuning.h: 256): a pointer only ever moves to an earlier byte of the
 // same chain of copies, so reading one that another thread has already moved is as good.  Round 0 looks at every
 // byte; a thread that did not arrive at a literal lists its byte (more[round] counts them), and the rounds behind
 // look at the listed bytes only (all rounds are launched; one whose list is empty returns at once).
@@ -1597,7 +1601,13 @@ __global__ __launch_bounds__(256) void inflate_gather_kernel(uint8_t *__restrict
 // and all candidates are checked at once: the chain holds as far as every candidate is a stored
 // header (BTYPE 00 on a byte boundary, LEN = ~NLEN) of that length.  The blocks of that prefix
 // are copied with 64-bit offsets, one workgroup each; whatever follows -- a shorter last block,
-// a block of another kind -- is an ordinary stream for the kernel above (api.hip).
+// a block of another kind -- is an ordinary stream for the kernel above (inflate_huge_stream, below).
+struct StoredChain {
+  uint32_t len0;        // LEN of the first block (0: the stream does not start with a stored block)
+  uint32_t candidates;  // header positions j * (5 + len0) inside the input
+  uint32_t first_bad;   // first candidate that is not a stored header of that length
+  uint32_t final_at;    // first candidate with BFINAL set (0xFFFFFFFF: none)
+};
 __global__ void stored_chain_probe_kernel(const uint8_t *__restrict__ src_arena, const StreamDesc *__restrict__ descs,
                                           StoredChain *__restrict__ st) {
   const StreamDesc sd = descs[0];
@@ -1641,6 +1651,16 @@ __global__ __launch_bounds__(256) void stored_chain_copy_kernel(const uint8_t *_
   if (threadIdx.x < (len0 & 15u)) o[body + threadIdx.x] = s[body + threadIdx.x];
 }
 
+struct StoredBlock { uint64_t src, dst; uint32_t len, pad; };  // offsets inside the stream's source / destination
+enum : uint32_t { WALK_MORE = 0, WALK_FINAL = 1, WALK_OTHER = 2, WALK_CORRUPT = 3, WALK_ROOM = 4 };
+struct StoredWalk {
+  uint64_t src_pos, dst_pos;  // in: where the walk starts; out: where it stopped (a header's first byte)
+  uint64_t room;              // output bytes the walk may still list
+  uint32_t n_blocks;          // out: blocks listed
+  uint32_t stop;              // out: WALK_* -- the list is full / the final block is listed / the next block is not a
+                              // stored one / its header is damaged or cut short (the reference's "Corrupted data
+                              // stream", zd.ml:672-677) / the next block does not fit the room
+};
 // The same for stored blocks of any lengths (a stream some other encoder made, or the reference's own
 // behind a run of shorter blocks).  A block's length says where the next header is, so the headers are a
 // chain of dependent loads; but runs of equal blocks are the rule, so the wave guesses that the next 64
@@ -1716,6 +1736,370 @@ __global__ __launch_bounds__(256) void stored_list_copy_kernel(const uint8_t *__
     for (uint32_t i = threadIdx.x * 16u; i < body; i += 256u * 16u) store16_unaligned(o + i, load16_unaligned(s + i));
     if (threadIdx.x < (b.len & 15u)) o[body + threadIdx.x] = s[body + threadIdx.x];
   }
+}
+
+
+// ---- the launches (host side): zd::launch_inflate is what zipc_hip_inflate_batch and the many-stream host forms call (api.hip)
+
+// One stream beyond ZIPC_HIP_MAX_STREAM_LEN: the stored blocks it has to start with (inflate.hip) are found
+// and copied with 64-bit offsets -- a chain of equal blocks all at once, blocks of other lengths by a walk over
+// their headers -- and what follows, if anything, goes through the batch kernel as a stream of its own; the
+// results are put together.  A damaged or cut-short stored header, and a block that does not fit the limit,
+// get the reference's messages.  This path copies a few words to the host between its steps: it SYNCHRONISES
+// the context's stream, unlike the rest of launch_inflate.
+static int inflate_huge_stream(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                               const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results, int crc_op) {
+  if (crc_op == ZIPC_HIP_CRC_ADLER32 || crc_op == ZIPC_HIP_CRC_ADLER32_RFC1950) return ZIPC_HIP_ERR_INVALID_ARG;
+  HIP_TRY(ctx, ctx->ensure(ctx->io_small, 256));
+  StoredChain *d_st = (StoredChain *)ctx->io_small.p;
+  StreamDesc sd;
+  HIP_TRY(ctx, hipMemcpyAsync(&sd, d_descs, sizeof sd, hipMemcpyDeviceToHost, ctx->stream));
+  ZD_LAUNCH(ctx, "stored_chain_probe", stored_chain_probe_kernel, dim3(1), dim3(1), 0, (const uint8_t *)d_src_arena,
+            (const StreamDesc *)d_descs, d_st);
+  StoredChain st;
+  HIP_TRY(ctx, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  StreamResult res;
+  res.status = ZIPC_HIP_ERR_INVALID_ARG; res.checksum = 0; res.out_len = 0;
+  uint64_t blocks = 0;
+  bool done = false;
+  if (st.len0 != 0 && st.candidates != 0) {
+    ZD_LAUNCH(ctx, "stored_chain_scan", stored_chain_scan_kernel, dim3((unsigned)(((uint64_t)st.candidates + 255) / 256)), dim3(256), 0,
+              (const uint8_t *)d_src_arena, (const StreamDesc *)d_descs, d_st);
+    HIP_TRY(ctx, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    blocks = st.first_bad;
+    if (st.final_at < blocks) { blocks = (uint64_t)st.final_at + 1; done = true; }  // the final block is one of the chain
+    // blocks that would overrun the destination are left to the walk below: it reports the reference's error
+    {
+      const uint64_t lim = (sd.flags & STREAM_HAS_LIMIT) ? sd.limit : ~0ull;
+      const uint64_t room = lim < sd.dst_cap ? lim : sd.dst_cap;
+      if (blocks * st.len0 > room) { blocks = room / st.len0; done = false; }
+    }
+    if (blocks)
+      ZD_LAUNCH(ctx, "stored_chain_copy", stored_chain_copy_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs, st.len0);
+  }
+  uint64_t used_src = blocks * (5ull + st.len0), made = blocks * (uint64_t)st.len0;
+  const uint64_t limit = (sd.flags & STREAM_HAS_LIMIT) ? sd.limit : ~0ull;
+  const uint64_t room_all = limit < sd.dst_cap ? limit : sd.dst_cap;
+  bool settled = done;  // the result is known without the batch kernel
+  if (done) {
+    res.status = ZIPC_HIP_OK;
+    res.out_len = made;
+  }
+  if (!settled) {
+    // stored blocks of other lengths: walked header by header (64 at a time while the length stays), listed and
+    // copied, a list at a time
+    constexpr uint32_t LIST_CAP = 1u << 20;
+    HIP_TRY(ctx, ctx->ensure(ctx->stored_list, (size_t)LIST_CAP * sizeof(StoredBlock)));
+    StoredWalk *d_walk = (StoredWalk *)((uint8_t *)ctx->io_small.p + 192);
+    static_assert(192 + sizeof(StoredWalk) <= 256, "io_small layout");
+    for (;;) {
+      StoredWalk w;
+      w.src_pos = used_src; w.dst_pos = made; w.room = room_all - made; w.n_blocks = 0; w.stop = WALK_MORE;
+      HIP_TRY(ctx, hipMemcpyAsync(d_walk, &w, sizeof w, hipMemcpyHostToDevice, ctx->stream));
+      ZD_LAUNCH(ctx, "stored_walk", stored_walk_kernel, dim3(1), dim3(64), 0, (const uint8_t *)d_src_arena,
+                (const StreamDesc *)d_descs, d_walk, (StoredBlock *)ctx->stored_list.p, LIST_CAP);
+      HIP_TRY(ctx, hipMemcpyAsync(&w, d_walk, sizeof w, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      if (w.n_blocks)
+        ZD_LAUNCH(ctx, "stored_list_copy", stored_list_copy_kernel, dim3(w.n_blocks < 65536u ? w.n_blocks : 65536u), dim3(256), 0,
+                  (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs,
+                  (const StoredBlock *)ctx->stored_list.p, w.n_blocks);
+      used_src = w.src_pos;
+      made = w.dst_pos;
+      if (w.stop == WALK_MORE && w.n_blocks) continue;  // the list was full
+      if (w.stop == WALK_FINAL) { res.status = ZIPC_HIP_OK; res.out_len = made; settled = true; }
+      else if (w.stop == WALK_CORRUPT) { res.status = ZIPC_HIP_ERR_CORRUPTED; settled = true; }  // zd.ml:672-677
+      else if (w.stop == WALK_ROOM) {  // Buf.add_string past the fixed size (zd.ml:29), or the caller's buffer is full
+        res.status = (sd.flags & STREAM_HAS_LIMIT) && limit <= sd.dst_cap ? ZIPC_HIP_ERR_SIZE_EXCEEDED : ZIPC_HIP_ERR_DST_TOO_SMALL;
+        settled = true;
+      }
+      break;  // WALK_OTHER: a block of another kind follows
+    }
+  }
+  if (!settled) {
+    StreamDesc rest = sd;
+    rest.src_off += used_src; rest.src_len -= used_src;
+    rest.dst_off += made; rest.dst_cap -= made;
+    if (rest.flags & STREAM_HAS_LIMIT) rest.limit -= made;
+    if (rest.src_len <= MAX_STREAM_LEN) {
+      if (rest.dst_cap > MAX_STREAM_LEN) rest.dst_cap = MAX_STREAM_LEN;  // (the rest is an ordinary stream: it may produce up to that much)
+      // the remainder's descriptor and result live in io_small, behind the StoredChain: the host forms hand
+      // THEIR descriptors in io_desc / io_res to this function (d_descs, d_results), which must stay as they are
+      // for the CRC pass below
+      zipc_hip_stream_desc *d_rest = (zipc_hip_stream_desc *)((uint8_t *)ctx->io_small.p + 64);
+      zipc_hip_stream_result *d_rest_res = (zipc_hip_stream_result *)((uint8_t *)ctx->io_small.p + 128);
+      static_assert(sizeof(StoredChain) <= 64 && sizeof(StreamDesc) <= 64 && 128 + sizeof(StreamResult) <= 192, "io_small layout");
+      HIP_TRY(ctx, hipMemcpyAsync(d_rest, &rest, sizeof rest, hipMemcpyHostToDevice, ctx->stream));
+      const int stb = launch_inflate(ctx, d_src_arena, d_dst_arena, d_rest, d_rest_res, 1, (size_t)rest.dst_cap, ZIPC_HIP_CRC_NOP,
+                                     nullptr, true);
+      if (stb) return stb;
+      HIP_TRY(ctx, hipMemcpyAsync(&res, d_rest_res, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      if (res.status == ZIPC_HIP_OK) res.out_len += made;
+      else res.out_len = 0;
+    }  // else: compressed blocks begin too early for the rest to be one ordinary stream (32-bit positions): INVALID_ARG stands
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(d_results, &res, sizeof res, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (crc_op == ZIPC_HIP_CRC_CRC32 && res.status == ZIPC_HIP_OK)
+    return crc32_pass(ctx, (const uint8_t *)d_dst_arena, RANGE_INFLATE_OUT, (const StreamDesc *)d_descs,
+                      (StreamResult *)d_results, 1, 0, 0, (size_t)res.out_len, nullptr);
+  return ZIPC_HIP_OK;
+}
+
+// Streams of at least BLOCKS_MIN_SRC bytes by a wave per block (inflate.hip: find, dry, explore, chain, token, resolve;
+// Adler-32 block by block as the reference updates it; CRC-32 is the caller's pass over the output).  The streams of
+// a call go through every step side by side -- the kernels' grids have them as their second dimension -- and the
+// host reads the counts of all of them back at once between the steps (three or four times a group, not per stream).
+// handled[i]: stream i went that way (its result is in d_results); else it is left to inflate_batch_kernel -- a stream
+// that is not a chain of dynamic blocks behind its first block, anything the dry run or the chain did not like: the
+// one-wave kernel owns the reference's messages.  It SYNCHRONISES the context's stream.  ZIPC_HIP_INFLATE_BLOCKS=0
+// turns it off.
+// (the BLOCKS_* limits, which streams go that way and in which groups: forms.h; every length, threshold and offset below: inflate_blocks.h)
+static int inflate_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, uint8_t *dst, const StreamDesc *dd, StreamResult *d_results,
+                                const StreamDesc *sds, const uint32_t *streams, size_t nj, int crc_op, uint8_t *handled) {
+  const uint64_t stride = tuning().explore_stride;  // bytes of input between two explorers
+  const bool adler = crc_op == ZIPC_HIP_CRC_ADLER32 || crc_op == ZIPC_HIP_CRC_ADLER32_RFC1950;
+  std::vector<BlocksJob> jobs(nj);
+  for (size_t j = 0; j < nj; j++) jobs[j] = blocks_job(streams[j], sds[streams[j]].src_len, stride);
+  FindCounts *d_counts;
+  BlocksJob *d_jobs;
+  if (ctx->ensure(ctx->blocks_scratch, carve_blocks_scratch(0, jobs, d_counts, d_jobs)) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }  // (no room for the lists: the streams' one waves need none)
+  carve_blocks_scratch((uintptr_t)ctx->blocks_scratch.p, jobs, d_counts, d_jobs);
+  std::vector<FindCounts> fc(nj);
+  auto read_counts = [&]() -> hipError_t {
+    const hipError_t e = hipMemcpyAsync(fc.data(), d_counts, nj * sizeof(FindCounts), hipMemcpyDeviceToHost, ctx->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
+  };
+  // a launch's streams: the jobs still on their way, as the kernels index them by blockIdx.y (the lists handed to
+  // the copies stay until the group is through)
+  std::deque<std::vector<BlocksJob>> handed;
+  auto hand = [&](const std::vector<uint32_t> &which) -> hipError_t {
+    std::vector<BlocksJob> &v = handed.emplace_back();
+    for (uint32_t j : which) v.push_back(jobs[j]);
+    return hipMemcpyAsync(d_jobs, v.data(), v.size() * sizeof(BlocksJob), hipMemcpyHostToDevice, ctx->stream);
+  };
+  // the span decoder's index, a slot per wave of a launch: every stream's waves behind those of the one before
+  // (false: no room for it -- the streams are left to their one waves, which need 2304 bytes each)
+  std::vector<size_t> at;
+  auto span_slots = [&](const std::vector<uint32_t> &which) {
+    if (ctx->ensure(ctx->inflate_scratch, blocks_span_slots(jobs, which, at)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    for (size_t k = 0; k < which.size(); k++) jobs[which[k]].span = (uint16_t *)((uint8_t *)ctx->inflate_scratch.p + at[k]);
+    return true;
+  };
+  auto widest = [&](const std::vector<uint32_t> &which, auto need) {
+    unsigned w = 1;
+    for (uint32_t j : which) { const unsigned x = (unsigned)need(jobs[j], j); if (x > w) w = x; }
+    return w;
+  };
+  std::vector<uint32_t> alive(nj), keep;
+  for (size_t j = 0; j < nj; j++) alive[j] = (uint32_t)j;
+  const unsigned ny = (unsigned)nj;
+
+  HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, nj * sizeof(FindCounts), ctx->stream));
+  HIP_TRY(ctx, hand(alive));
+  ZD_LAUNCH(ctx, "inflate_find_headers", inflate_find_headers_kernel,
+            dim3(widest(alive, [&](const BlocksJob &J, uint32_t) { return (sds[J.stream].src_len + 1023) / 1024; }), ny), dim3(256), 0, src, dd,
+            (const BlocksJob *)d_jobs);
+  ZD_LAUNCH(ctx, "inflate_find_lengths", inflate_find_lengths_kernel,
+            dim3(widest(alive, [](const BlocksJob &J, uint32_t) { return (J.first_cap + 63u) / 64u; }), ny), dim3(64), 0, src, dd,
+            (const BlocksJob *)d_jobs);
+  if (blocks_read_candidates(nj, jobs[0].cand_cap)) {
+    HIP_TRY(ctx, read_counts());
+    keep.clear();
+    for (uint32_t j : alive)
+      if (blocks_found(fc[j], jobs[j])) { jobs[j].n = fc[j].n_cand; keep.push_back(j); }
+    alive.swap(keep);
+    if (alive.empty()) return ZIPC_HIP_OK;
+  } else {
+    jobs[0].n = jobs[0].cand_cap;
+  }
+  if (!span_slots(alive)) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, hand(alive));
+  unsigned na = (unsigned)alive.size();
+  const unsigned dry_waves = widest(alive, [](const BlocksJob &J, uint32_t) { return J.n; });
+  ZD_LAUNCH(ctx, "inflate_blocks_dry", inflate_blocks_dry_kernel, dim3(dry_waves, na), dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs);
+  ZD_LAUNCH(ctx, "inflate_sort_blocks", inflate_sort_blocks_kernel, dim3((dry_waves + 255u) / 256u, na), dim3(256), 0, (const BlocksJob *)d_jobs);
+  ZD_LAUNCH(ctx, "inflate_chain", inflate_chain_kernel, dim3(1, na), dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs, 0);
+  HIP_TRY(ctx, read_counts());
+  keep.clear();
+  std::vector<uint32_t> lost;  // streams whose chain came to a block nobody listed
+  for (uint32_t j : alive) {
+    const BlocksChained v = blocks_chained(fc[j], jobs[j]);
+    if (v == BLOCKS_LOST) lost.push_back(j);
+    if (v != BLOCKS_DROPPED) keep.push_back(j);
+  }
+  alive.swap(keep);
+  if (!lost.empty()) {
+    // explorers from there on, then the chain again (which now walks what is still missing itself)
+    for (uint32_t j : lost) blocks_explore_waves(fc[j], jobs[j], sds[jobs[j].stream].src_len, stride);
+    if (!span_slots(lost)) return ZIPC_HIP_OK;
+    HIP_TRY(ctx, hand(lost));
+    const unsigned nl = (unsigned)lost.size();
+    ZD_LAUNCH(ctx, "inflate_explore", inflate_explore_kernel, dim3(widest(lost, [](const BlocksJob &J, uint32_t) { return J.n; }), nl), dim3(64), 0,
+              src, dst, dd, (const BlocksJob *)d_jobs, (uint32_t)(stride * 8u));
+    ZD_LAUNCH(ctx, "inflate_sort_blocks", inflate_sort_blocks_kernel,
+              dim3(widest(lost, [](const BlocksJob &J, uint32_t) { return (J.rec_cap + 255u) / 256u; }), nl), dim3(256), 0, (const BlocksJob *)d_jobs);
+    ZD_LAUNCH(ctx, "inflate_chain", inflate_chain_kernel, dim3(1, nl), dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs, 1);
+    HIP_TRY(ctx, read_counts());
+  }
+  const TokenPlan plan = blocks_token_plan(jobs, fc, alive, sds, tuning().inflate_follow);
+  alive = plan.taken;
+  if (alive.empty()) return ZIPC_HIP_OK;
+  if (ctx->ensure(ctx->tok_scratch, plan.tok_bytes) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }  // (no room for a word per byte and the lists: the streams' one waves need none)
+  for (size_t k = 0; k < alive.size(); k++) jobs[alive[k]].tok = (uint32_t *)((uint8_t *)ctx->tok_scratch.p + plan.tok_at[k]);
+  if (!span_slots(alive)) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, hand(alive));
+  na = (unsigned)alive.size();
+  const unsigned out_grid = widest(alive, [](const BlocksJob &J, uint32_t) { return (J.out_len + 255u) / 256u; });
+  ZD_LAUNCH(ctx, "inflate_tok_init", inflate_tok_init_kernel, dim3(out_grid, na), dim3(256), 0, (const BlocksJob *)d_jobs);
+  ZD_LAUNCH(ctx, "inflate_blocks_token", inflate_blocks_token_kernel, dim3(widest(alive, [](const BlocksJob &J, uint32_t) { return J.n; }), na),
+            dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs);
+  const int hops0 = tuning().resolve_hops0, hops1 = tuning().resolve_hops1;
+  const int rounds = resolve_rounds(hops0, hops1);
+  for (int r = 0; r < rounds; r++)
+    ZD_LAUNCH(ctx, "inflate_resolve", inflate_resolve_kernel, dim3(resolve_grid(r, out_grid), na), dim3(256), 0, (const BlocksJob *)d_jobs, r, r == 0 ? hops0 : hops1);
+  ZD_LAUNCH(ctx, "inflate_gather", inflate_gather_kernel, dim3(out_grid, na), dim3(256), 0, dst, dd, (const BlocksJob *)d_jobs);
+  HIP_TRY(ctx, read_counts());
+  // (12 bytes of scratch per output byte: what a long stream took goes back -- a context lives as long as its thread,
+  // and a 1 GiB member would pin 12 GiB per device; the stream is idle here, the gather has been waited for)
+  if (ctx->tok_scratch.cap > BLOCKS_TOK_BUDGET) free_buf(ctx->tok_scratch);
+  keep.clear();
+  size_t n_chunks = 0;
+  for (uint32_t j : alive) {
+    if (!blocks_done(fc[j], rounds)) continue;  // (the one-wave kernel writes the output again)
+    n_chunks += fc[j].n_chunks;
+    keep.push_back(j);
+  }
+  alive.swap(keep);
+  if (alive.empty()) return ZIPC_HIP_OK;
+  na = (unsigned)alive.size();
+  if (adler) {  // block by block, every block's bytes in chunks of their own
+    if (ctx->ensure(ctx->adler_sums, blocks_adler_sums(fc, alive, at)) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }  // (the one waves write output and checksum again)
+    for (size_t k = 0; k < alive.size(); k++) jobs[alive[k]].sums = (uint32_t *)((uint8_t *)ctx->adler_sums.p + at[k]);
+  }
+  HIP_TRY(ctx, hand(alive));
+  ZD_LAUNCH(ctx, "inflate_blocks_result", inflate_blocks_result_kernel, dim3((na + 63u) / 64u), dim3(64), 0, (const BlocksJob *)d_jobs, d_results, na);
+  if (adler) {
+    if (n_chunks)
+      ZD_LAUNCH(ctx, "inflate_adler_chunks", inflate_adler_chunks_kernel, dim3(widest(alive, [&](const BlocksJob &, uint32_t j) { return fc[j].n_chunks; }), na),
+                dim3(64), 0, (const uint8_t *)dst, dd, (const BlocksJob *)d_jobs);
+    ZD_LAUNCH(ctx, "inflate_adler_fold", inflate_adler_fold_kernel, dim3(1, na), dim3(64), 0, (const BlocksJob *)d_jobs,
+              crc_op == ZIPC_HIP_CRC_ADLER32_RFC1950 ? 1 : 0, d_results);
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the lists handed to the copies go with this frame)
+  for (uint32_t j : alive) { handled[jobs[j].stream] = 1; ctx->last_inflate_blocks += jobs[j].n_blocks; }
+  return ZIPC_HIP_OK;
+}
+
+// which of a call's streams go by blocks, group by group; *n_handled: how many did
+// h_descs: the caller's own host copy of the descriptors (the many-stream host forms have one), or null: they are read
+// back from the device, which waits for everything the stream holds -- the host forms feed sub-batch g + 1 while g's
+// kernels run, and a read-back per sub-batch (before the model below had even said whether any stream goes by blocks:
+// for an archive of equal members none does) put the host behind every sub-batch's copies and kernels.
+static int inflate_by_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                             zipc_hip_stream_result *d_results, size_t n_streams, int crc_op, std::vector<StreamDesc> &sds,
+                             std::vector<uint8_t> &handled, size_t *n_handled, const StreamDesc *h_descs) {
+  *n_handled = 0;
+  handled.assign(n_streams, 0);
+  if (!zd::tuning().inflate_blocks) return ZIPC_HIP_OK;
+  if (h_descs) {
+    sds.assign(h_descs, h_descs + n_streams);
+  } else {
+    sds.resize(n_streams);
+    HIP_TRY(ctx, hipMemcpyAsync(sds.data(), d_descs, n_streams * sizeof(StreamDesc), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  const std::vector<uint32_t> picked = inflate_blocks_pick(sds.data(), n_streams);
+  size_t begin = 0;
+  for (size_t end : inflate_blocks_groups(sds.data(), picked)) {
+    const int st = inflate_blocks_group(ctx, (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs,
+                                        (StreamResult *)d_results, sds.data(), picked.data() + begin, end - begin, crc_op, handled.data());
+    if (st) return st;
+    begin = end;
+  }
+  for (size_t i = 0; i < n_streams; i++) *n_handled += handled[i];
+  return ZIPC_HIP_OK;
+}
+
+// the batch kernel: one wave per stream
+static int inflate_batch_one_wave(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                  zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op, bool marked = false) {
+  const int k_crc_op = crc_op | (marked ? CRC_OP_MARKED : 0);  // what the kernels are told (inflate.hip inflate_skips_stream)
+  // one wave per stream (in slices on queues of their own, the CRC pass of one slice beside the inflate kernel of
+  // the next: two by default, forms.h batch_slices)
+  HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_streams * INFLATE_SCRATCH_PER_STREAM));
+  const size_t segs = crc32_segs(max_dst_cap);
+  if (crc_op == ZIPC_HIP_CRC_CRC32) {
+    if (n_streams * segs > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+    HIP_TRY(ctx, ctx->ensure(ctx->crc_partials, n_streams * segs * sizeof(uint32_t)));
+  }
+  const size_t k = crc_op == ZIPC_HIP_CRC_CRC32 ? batch_slices(n_streams, zd::tuning(), debug_slices_override()) : 1;
+  if (k > 1) HIP_TRY(ctx, ctx->fork(k));
+  int st = ZIPC_HIP_OK;
+  for (size_t i = 0; i < k && st == ZIPC_HIP_OK; i++) {
+    const size_t lo = n_streams * i / k, hi = n_streams * (i + 1) / k;
+    if (k > 1) ctx->use_slice_stream(i);
+    const StreamDesc *dd = (const StreamDesc *)d_descs + lo;
+    StreamResult *dr = (StreamResult *)d_results + lo;
+    if (inflate_few_streams(n_streams))
+      ZD_LAUNCH(ctx, "inflate_batch", inflate_batch_few_kernel, dim3((unsigned)(hi - lo)), dim3(64), 0,
+                (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, dd, dr, (uint32_t)(hi - lo),
+                (uint16_t *)ctx->inflate_scratch.p + lo * (INFLATE_SCRATCH_PER_STREAM / 2), k_crc_op);
+    else
+      ZD_LAUNCH(ctx, "inflate_batch", inflate_batch_kernel, dim3((unsigned)(hi - lo)), dim3(64), 0,
+                (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, dd, dr, (uint32_t)(hi - lo),
+                (uint16_t *)ctx->inflate_scratch.p + lo * (INFLATE_SCRATCH_PER_STREAM / 2), k_crc_op);
+    if (hipGetLastError() != hipSuccess) { ctx->last_error = "inflate_batch launch failed"; st = ZIPC_HIP_ERR_HIP; break; }
+    if (crc_op == ZIPC_HIP_CRC_CRC32)
+      st = crc32_pass(ctx, (const uint8_t *)d_dst_arena, RANGE_INFLATE_OUT, dd, dr, hi - lo, 0, 0, max_dst_cap, nullptr,
+                      lo * segs, true);
+  }
+  if (k > 1) {
+    const hipError_t e = ctx->join(k);
+    if (st == ZIPC_HIP_OK) HIP_TRY(ctx, e);
+  }
+  return st;
+}
+
+// zipc_hip_inflate_batch behind its argument checks (ctx.h)
+int launch_inflate(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                   zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op, const StreamDesc *h_descs,
+                   bool first_of_call) {
+  if (first_of_call) ctx->last_inflate_blocks = 0;  // (also for a call that never reaches the block path: "0 when the stream's one wave decoded it")
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (n_streams == 1 && max_dst_cap > MAX_STREAM_LEN)
+    return inflate_huge_stream(ctx, d_src_arena, d_dst_arena, d_descs, d_results, crc_op);
+  if (inflate_blocks_gate(n_streams, max_dst_cap)) {
+    std::vector<StreamDesc> sds;
+    std::vector<uint8_t> handled;
+    size_t n_handled = 0;
+    const int by = inflate_by_blocks(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, crc_op, sds, handled, &n_handled, h_descs);
+    if (by != ZIPC_HIP_OK) return by;
+    if (n_handled == n_streams) {
+      if (crc_op != ZIPC_HIP_CRC_CRC32) return ZIPC_HIP_OK;
+      return crc32_pass(ctx, (const uint8_t *)d_dst_arena, RANGE_INFLATE_OUT, (const StreamDesc *)d_descs, (StreamResult *)d_results,
+                        n_streams, 0, 0, max_dst_cap, nullptr);
+    }
+    if (n_handled) {
+      // the others by their one waves, over a copy of the descriptors that says which streams are through (the CRC
+      // pass behind the kernel takes every stream's output as it finds it in d_results)
+      for (size_t i = 0; i < n_streams; i++)
+        if (handled[i]) sds[i].flags |= STREAM_DONE;
+      HIP_TRY(ctx, ctx->ensure(ctx->descs_marked, n_streams * sizeof(StreamDesc)));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->descs_marked.p, sds.data(), n_streams * sizeof(StreamDesc), hipMemcpyHostToDevice, ctx->stream));
+      const int st = inflate_batch_one_wave(ctx, d_src_arena, d_dst_arena, (const zipc_hip_stream_desc *)ctx->descs_marked.p, d_results,
+                                            n_streams, max_dst_cap, crc_op, true);
+      const hipError_t e = hipStreamSynchronize(ctx->stream);  // (sds goes with this frame)
+      if (st == ZIPC_HIP_OK) HIP_TRY(ctx, e);
+      return st;
+    }
+  }
+  return inflate_batch_one_wave(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, max_dst_cap, crc_op);
 }
 
 }  // namespace zd

@@ -31,7 +31,7 @@ struct Tuning {
   long slices, slice_min;      // ZIPC_HIP_SLICES, ZIPC_HIP_SLICE_MIN  a batch cut into slices on side queues (default 0: two slices of at
                                //                          least 2048 streams each, forms.h batch_slices; the tests force more and smaller
                                //                          ones).  test_gpu_fuzz
-  // ---- inflate of one long stream by blocks (api.hip inflate_by_blocks)
+  // ---- inflate of one long stream by blocks (inflate.hip inflate_by_blocks, inflate_blocks.h)
   bool inflate_blocks;         // ZIPC_HIP_INFLATE_BLOCKS=0  the stream's one wave instead.  tools/measure_round.sh
   int inflate_follow;          // ZIPC_HIP_INFLATE_FOLLOW  -1 (default): sources followed inside the token run in calls of 32 MiB of
                                //                          output and more; 0 / 1 never / always.  test_gpu_fuzz

@@ -74,7 +74,7 @@ struct StreamResult {
   uint64_t out_len;
 };
 constexpr uint32_t STREAM_HAS_LIMIT = 1u;
-// (never a caller's: the library's own copy of a call's descriptors, for streams that went by blocks -- api.hip)
+// (never a caller's: the library's own copy of a call's descriptors, for streams that went by blocks -- inflate.hip launch_inflate)
 constexpr uint32_t STREAM_DONE = 1u << 31;
 constexpr int CRC_OP_MARKED = 0x100;  // in a kernel's crc_op argument: the descriptors are the library's marked copy (inflate.hip)
 
