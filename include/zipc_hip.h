@@ -330,6 +330,66 @@ int zipc_hip_zlib_compress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, voi
                                  const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
                                  size_t n_streams, size_t max_src_len, size_t total_src_len, int level);
 
+/* Recode on the device: every stream of the source arena -- a raw deflate stream, a ZIP member's bytes -- is inflated
+ * into its room in a MIDDLE arena, its CRC-32 taken there and compared where the descriptor expects one, and what it
+ * inflated to is deflated at `level` into its destination slot: Zipc_deflate.inflate_and_crc_32, Crc_32.check and
+ * Zipc_deflate.deflate of every member (the reference's `recode`, test/zipc_tool.ml:437-545) in one call, with nothing
+ * read back in between and the decompressed bytes never leaving the device.  The codec's kernels are the ones of the
+ * two batch forms above, between three small ones, a lane per stream (csrc/recode.hip, rules: csrc/recode_rules.h):
+ *   open: a flag bit other than ZIPC_HIP_STREAM_HAS_LIMIT and ZIPC_HIP_STREAM_EXPECT_CRC32, or mid_cap above the call's
+ *     max_mid_cap, is ZIPC_HIP_ERR_INVALID_ARG at stage 0 and nothing of the stream is read or written;
+ *   link: a stream inflate refused stops with inflate's status at stage 1; one whose CRC-32 is not expect_crc32 stops
+ *     with ZIPC_HIP_ERR_CHECKSUM at stage 2, checksum = the value FOUND;
+ *   close: deflate's status (ZIPC_HIP_ERR_DST_TOO_SMALL, or the batch-wide ZIPC_HIP_ERR_INVALID_ARG of its declared
+ *     sizes) at stage 3, or ZIPC_HIP_OK with the recoded length.
+ * The CRC-32 is taken once, over inflate's output; it is the CRC-32 the recoded member has. */
+#define ZIPC_HIP_STREAM_EXPECT_CRC32 2u
+typedef struct {            /* 64 bytes */
+  uint64_t src_off, src_len;   /* the deflate stream, in the source arena */
+  uint64_t mid_off, mid_cap;   /* room for its decompressed bytes, in the middle arena */
+  uint64_t dst_off, dst_cap;   /* room for the recoded stream, in the destination arena */
+  uint64_t limit;              /* ?decompressed_size when flags & ZIPC_HIP_STREAM_HAS_LIMIT */
+  uint32_t flags;
+  uint32_t expect_crc32;       /* compared when flags & ZIPC_HIP_STREAM_EXPECT_CRC32 */
+} zipc_hip_recode_desc;
+typedef struct {            /* 32 bytes */
+  uint32_t status;    /* ZIPC_HIP_OK or the failing step's status */
+  uint32_t checksum;  /* CRC-32 of the decompressed bytes (stage 2, 3 and OK); else 0 */
+  uint64_t out_len;   /* bytes of the recoded stream at dst_off; 0 unless OK */
+  uint64_t mid_len;   /* decompressed length; 0 at stage 0 and 1 */
+  uint32_t stage;     /* 0 OK or refused before any work, 1 inflate, 2 CRC check, 3 deflate */
+  uint32_t reserved;  /* 0 */
+} zipc_hip_recode_result;
+/* All pointers are DEVICE pointers.  The work is enqueued on the context's stream and not synchronised, except where
+ * zipc_hip_inflate_batch itself synchronises (max_mid_cap of 256 KiB and more).  max_mid_cap: upper bound of mid_cap
+ * over the batch; total_mid_cap: their sum -- inflate's max_dst_cap and deflate's max_src_len / total_src_len, whose
+ * device-side check of the declared sizes applies unchanged (if it trips, the streams that got as far as deflate report
+ * its ZIPC_HIP_ERR_INVALID_ARG at stage 3).  level outside 0..3, or max_mid_cap above ZIPC_HIP_MAX_STREAM_LEN (one
+ * stream's included: inflate's path for stored streams beyond 4 GiB has nothing deflate could take), fails the call
+ * with ZIPC_HIP_ERR_INVALID_ARG.  Nothing is written behind any stream's dst_cap or mid_cap, and nothing to the
+ * destination slot of a stream that stops at stage 0, 1 or 2; one that stops at stage 3 has what zipc_hip_deflate_batch
+ * leaves of a stream that does not fit: nothing of the block that did not fit nor of those behind it (of a stream of one
+ * block: nothing).
+ * The defining property: for every stream, the result and the destination bytes are what the caller gets from
+ * zipc_hip_inflate_batch (ZIPC_HIP_CRC_CRC32) into the middle arena, the link rule above applied on the host, and
+ * zipc_hip_deflate_batch (level, ZIPC_HIP_CRC_NOP) of the streams that go on. */
+int zipc_hip_recode_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_mid_arena, void *d_dst_arena,
+                          const zipc_hip_recode_desc *d_descs, zipc_hip_recode_result *d_results,
+                          size_t n_streams, size_t max_mid_cap, size_t total_mid_cap, int level);
+/* The same for streams held in HOST memory, through the pipeline of zipc_hip_inflate_many / _deflate_many (gather, copy
+ * in, kernels, copy back end to end, scatter): stream i is src[i][0 .. src_len[i]), recoded into dst[i] (capacity
+ * dst_cap[i]; zipc_hip_deflate_bound(mid_cap[i]) always fits), with mid_cap[i] bytes of room for its decompressed bytes
+ * in a middle arena the context keeps on the device, sized to the largest sub-batch.  What crosses the bus is the old
+ * stream on the way in and the new one on the way back.  limit may be NULL (no ?decompressed_size for any stream: a
+ * stream that inflates to more than mid_cap[i] reports ZIPC_HIP_ERR_DST_TOO_SMALL at stage 1), expect_crc32 may be NULL
+ * (no stream's CRC-32 is compared).  Like the other _many forms: results[] (host memory) is defined on every return,
+ * bad arguments included -- the streams of sub-batches that had come back keep their results, every other one carries
+ * the call's status at stage 0 -- and no C++ exception crosses the boundary. */
+int zipc_hip_recode_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len,
+                         const size_t *limit /* may be NULL */, const uint32_t *expect_crc32 /* may be NULL */,
+                         const size_t *mid_cap, int level, void *const *dst, const size_t *dst_cap,
+                         zipc_hip_recode_result *results);
+
 /* CRC-32 and Adler-32 of one device buffer (Crc_32.string + Adler_32.string).  Both asked for: ONE pass over the bytes
  * leaves the CRC-32 partials and the Adler-32 chunk sums (len bytes of traffic), then the two short finishes.  d_out receives {crc32, adler32}.  Either selector may be 0 to
  * skip that checksum. */

@@ -83,6 +83,12 @@ int zipc_host_add_file_deflate(zipc_host_archive *a, const char *path, size_t pa
 int zipc_host_add_files_deflate(zipc_host_archive *a, size_t n, const char *const *paths, const size_t *path_lens,
                                 const void *const *datas, const size_t *lens, int level, char *err, size_t errcap);
 
+/* File.to_binary_string |> File.deflate_of_binary_string ?level of every deflated, non-encrypted file member, as ONE
+ * batch that stays on the GPU (Archive::recode_deflated: inflate, the CRC-32 against the directory's, deflate, with the
+ * decompressed bytes never crossing the bus); path, mtime and mode are kept.  ZIPC_HOST_ERROR: err is "<path>: " and
+ * to_binary_string's message for the first member in path order that failed, and the archive is as it was. */
+int zipc_host_recode_deflated(zipc_host_archive *a, int level, char *err, size_t errcap);
+
 /* encoding_size / to_binary_string ?first (zipc.mli:353-356).  first = NULL: "mimetype". */
 size_t zipc_host_encoding_size(const zipc_host_archive *a);
 int zipc_host_to_binary_string(const zipc_host_archive *a, const char *first, size_t first_len, void *dst, size_t cap,

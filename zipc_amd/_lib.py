@@ -29,6 +29,7 @@ ERR_NOMEM = 20
 CRC_NOP, CRC_CRC32, CRC_ADLER32, CRC_ADLER32_RFC1950 = 0, 1, 2, 3
 LEVEL_NONE, LEVEL_FAST, LEVEL_DEFAULT, LEVEL_BEST = 0, 1, 2, 3
 STREAM_HAS_LIMIT = 1
+STREAM_EXPECT_CRC32 = 2
 
 
 class StreamDesc(C.Structure):
@@ -39,6 +40,17 @@ class StreamDesc(C.Structure):
 
 class StreamResult(C.Structure):
     _fields_ = [("status", C.c_uint32), ("checksum", C.c_uint32), ("out_len", C.c_uint64)]
+
+
+class RecodeDesc(C.Structure):
+    _fields_ = [("src_off", C.c_uint64), ("src_len", C.c_uint64), ("mid_off", C.c_uint64), ("mid_cap", C.c_uint64),
+                ("dst_off", C.c_uint64), ("dst_cap", C.c_uint64), ("limit", C.c_uint64), ("flags", C.c_uint32),
+                ("expect_crc32", C.c_uint32)]
+
+
+class RecodeResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("checksum", C.c_uint32), ("out_len", C.c_uint64), ("mid_len", C.c_uint64),
+                ("stage", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class KernelTime(C.Structure):
@@ -87,6 +99,8 @@ SYMBOLS = [
     ("zipc_hip_deflate_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int, C.c_int]),
     ("zipc_hip_zlib_decompress_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ]),
     ("zipc_hip_zlib_compress_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int]),
+    ("zipc_hip_recode_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int]),
+    ("zipc_hip_recode_many", C.c_int, [_P, _SZ, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("zipc_hip_checksum_device", C.c_int, [_P, _P, _SZ, C.c_int, C.c_int, _P]),
     ("zipc_hip_reserve", C.c_int, [_P, _SZ, _SZ, _SZ]),
 ]

@@ -9,13 +9,20 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import CRC_NOP, OK, STREAM_HAS_LIMIT, Context, lib
+from ._lib import CRC_NOP, OK, STREAM_EXPECT_CRC32, STREAM_HAS_LIMIT, Context, lib
 
 DESC_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("dst_off", "<u8"),
                        ("dst_cap", "<u8"), ("limit", "<u8"), ("flags", "<u4"),
                        ("reserved", "<u4")])
 RESULT_DTYPE = np.dtype([("status", "<u4"), ("checksum", "<u4"), ("out_len", "<u8")])
 assert DESC_DTYPE.itemsize == 48 and RESULT_DTYPE.itemsize == 16
+# zipc_hip_recode_desc / zipc_hip_recode_result
+RECODE_DESC_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("mid_off", "<u8"), ("mid_cap", "<u8"),
+                              ("dst_off", "<u8"), ("dst_cap", "<u8"), ("limit", "<u8"), ("flags", "<u4"),
+                              ("expect_crc32", "<u4")])
+RECODE_RESULT_DTYPE = np.dtype([("status", "<u4"), ("checksum", "<u4"), ("out_len", "<u8"), ("mid_len", "<u8"),
+                                ("stage", "<u4"), ("reserved", "<u4")])
+assert RECODE_DESC_DTYPE.itemsize == 64 and RECODE_RESULT_DTYPE.itemsize == 32
 
 
 def make_descs(src_off, src_len, dst_off, dst_cap, limit=None) -> np.ndarray:
@@ -25,6 +32,20 @@ def make_descs(src_off, src_len, dst_off, dst_cap, limit=None) -> np.ndarray:
     if limit is not None:
         d["limit"] = limit
         d["flags"] = STREAM_HAS_LIMIT
+    return d
+
+
+def make_recode_descs(src_off, src_len, mid_off, mid_cap, dst_off, dst_cap, limit=None, expect_crc32=None) -> np.ndarray:
+    """descriptors of zipc_hip_recode_batch; limit / expect_crc32: None, or one value per stream (the flag bits follow)"""
+    d = np.zeros(len(src_off), dtype=RECODE_DESC_DTYPE)
+    d["src_off"], d["src_len"], d["mid_off"], d["mid_cap"] = src_off, src_len, mid_off, mid_cap
+    d["dst_off"], d["dst_cap"] = dst_off, dst_cap
+    if limit is not None:
+        d["limit"] = limit
+        d["flags"] |= STREAM_HAS_LIMIT
+    if expect_crc32 is not None:
+        d["expect_crc32"] = expect_crc32
+        d["flags"] |= STREAM_EXPECT_CRC32
     return d
 
 
@@ -88,6 +109,24 @@ def zlib_compress_batch(ctx: Context, src, dst, descs_dev, results_dev, n_stream
         _sync_torch(src)
     st = lib().zipc_hip_zlib_compress_batch(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(),
                                             results_dev.data_ptr(), n_streams, max_src_len, total_src_len, level)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def recode_results_from_device(t) -> np.ndarray:
+    return t.cpu().numpy().view(RECODE_RESULT_DTYPE).copy()
+
+
+def recode_batch(ctx: Context, src, mid, dst, descs_dev, results_dev, n_streams: int, max_mid_cap: int, total_mid_cap: int,
+                 level: int, sync: bool = True):
+    """zipc_hip_recode_batch: stream i of `src` (a raw deflate stream) is inflated into its room in `mid`, its CRC-32
+    taken and compared where the descriptor expects one, and deflated at `level` into its slot of `dst`, all on the
+    device; descs_dev / results_dev: uint8 cuda tensors of RECODE_DESC_DTYPE / RECODE_RESULT_DTYPE records."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_recode_batch(ctx.handle, src.data_ptr(), mid.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(),
+                                     results_dev.data_ptr(), n_streams, max_mid_cap, total_mid_cap, level)
     ctx.check(st)
     if sync:
         ctx.synchronize()
@@ -158,7 +197,8 @@ def compact_descs(results: np.ndarray, descs: np.ndarray, dst_cap_of_out, limit_
     return d
 
 
-__all__ = ["DESC_DTYPE", "RESULT_DTYPE", "make_descs", "to_device", "results_from_device",
+__all__ = ["DESC_DTYPE", "RESULT_DTYPE", "RECODE_DESC_DTYPE", "RECODE_RESULT_DTYPE", "make_descs", "make_recode_descs", "to_device",
+           "results_from_device", "recode_results_from_device", "recode_batch",
            "inflate_batch", "deflate_batch", "zlib_decompress_batch", "zlib_compress_batch", "checksum_device", "reserve",
            "deflate_bound", "zlib_bound",
            "uniform_layout", "compact_descs", "OK"]

@@ -1,6 +1,6 @@
 // api.hip -- the C ABI of include/zipc_hip.h: the context and its scratch, tuning(), the CRC-32 pass and the checksum
 // launches, the batch forms as argument checks around launch_deflate / launch_inflate (deflate.hip, inflate.hip), the
-// host forms, the many-stream pipeline's device half and the zlib forms.
+// host forms, the many-stream pipeline's device half, the zlib forms and the recode forms.
 //
 // Host forms stage one stream through device scratch and run the same kernels as
 // the batch forms (a batch of one).  Nothing here computes on the CPU: with no
@@ -22,6 +22,7 @@
 #include "deflate_scratch.h"
 #include "host_pipeline.h"
 #include "inflate_blocks.h"
+#include "recode_rules.h"
 #include "tuning.h"
 #include "zlib_container.h"
 
@@ -29,6 +30,9 @@ using namespace zd;
 
 static_assert(sizeof(zipc_hip_stream_desc) == sizeof(StreamDesc), "desc layout");
 static_assert(sizeof(zipc_hip_stream_result) == sizeof(StreamResult), "result layout");
+static_assert(sizeof(zipc_hip_recode_desc) == sizeof(RecodeDesc) && sizeof(RecodeDesc) == 64, "recode desc layout");
+static_assert(sizeof(zipc_hip_recode_result) == sizeof(RecodeResult) && sizeof(RecodeResult) == 32, "recode result layout");
+static_assert(ZIPC_HIP_STREAM_EXPECT_CRC32 == STREAM_EXPECT_CRC32 && ZIPC_HIP_ERR_CHECKSUM == ST_CHECKSUM, "recode constants");
 
 // ---- context internals -------------------------------------------------------
 
@@ -353,12 +357,15 @@ void zipc_hip_destroy(zipc_hip_ctx *ctx) {
   free_buf(ctx->tok_scratch);
   free_buf(ctx->descs_marked);
   free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre);
+  free_buf(ctx->recode_descs); free_buf(ctx->recode_res); free_buf(ctx->recode_verdicts);
+  free_buf(ctx->io_mid); free_buf(ctx->io_rdesc); free_buf(ctx->io_rres);
   free_buf(ctx->stored_list);
   free_buf(ctx->chain_check_links);
   if (ctx->chain_check_host) (void)hipHostFree(ctx->chain_check_host);
   if (ctx->pin_src.p) (void)hipHostFree(ctx->pin_src.p);
   if (ctx->pin_dst.p) (void)hipHostFree(ctx->pin_dst.p);
   if (ctx->pin_res.p) (void)hipHostFree(ctx->pin_res.p);
+  if (ctx->pin_rres.p) (void)hipHostFree(ctx->pin_rres.p);
   if (ctx->copy_in) (void)hipStreamDestroy(ctx->copy_in);
   if (ctx->copy_out) (void)hipStreamDestroy(ctx->copy_out);
   for (auto s : ctx->side) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
@@ -654,6 +661,54 @@ int zipc_hip_deflate(zipc_hip_ctx *ctx, const void *src, size_t len, int level, 
   return one_stream(ctx, false, src, len, 0, 0, level, crc_op, dst, dst_cap, out_len, checksum);
 }
 
+// ---- recode on the device (recode_rules.h has the rules; recode.hip the three kernels) ------------------------------
+
+// The context's scratch of a recode of n streams: the descriptors the codec runs with, its results, the verdicts.
+static int recode_reserve(zipc_hip_ctx *ctx, size_t n) {
+  HIP_TRY(ctx, ctx->ensure(ctx->recode_descs, n * sizeof(StreamDesc)));
+  HIP_TRY(ctx, ctx->ensure(ctx->recode_res, n * sizeof(StreamResult)));
+  HIP_TRY(ctx, ctx->ensure(ctx->recode_verdicts, n * sizeof(RecodeVerdict)));
+  return ZIPC_HIP_OK;
+}
+// open -> inflate with its CRC-32 pass -> link -> deflate out of the middle arena -> close, all on the context's stream.
+// d_plain: null, or n StreamResults for the many-stream pipeline; h_inflate_descs: null, or the host's own copy of what
+// recode_open makes of the descriptors (launch_inflate's h_descs); first_of_call: launch_inflate's.
+static int recode_sequence(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_mid_arena, void *d_dst_arena, const RecodeDesc *d_descs,
+                           RecodeResult *d_results, StreamResult *d_plain, size_t n, size_t max_mid_cap, size_t total_mid_cap, int level,
+                           const StreamDesc *h_inflate_descs, bool first_of_call) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int st = recode_reserve(ctx, n);
+  if (st) return st;
+  StreamDesc *inner = (StreamDesc *)ctx->recode_descs.p;
+  StreamResult *inner_res = (StreamResult *)ctx->recode_res.p;
+  RecodeVerdict *verdicts = (RecodeVerdict *)ctx->recode_verdicts.p;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  ZD_LAUNCH(ctx, "recode_open", recode_open_kernel, grid, block, 0, d_descs, (uint32_t)n, (uint64_t)max_mid_cap, inner, verdicts);
+  HIP_TRY(ctx, hipGetLastError());
+  st = launch_inflate(ctx, d_src_arena, d_mid_arena, (const zipc_hip_stream_desc *)inner, (zipc_hip_stream_result *)inner_res, n, max_mid_cap,
+                      ZIPC_HIP_CRC_CRC32, h_inflate_descs, first_of_call);
+  if (st) return st;
+  ZD_LAUNCH(ctx, "recode_link", recode_link_kernel, grid, block, 0, d_descs, (uint32_t)n, (const StreamResult *)inner_res, inner, verdicts);
+  HIP_TRY(ctx, hipGetLastError());
+  st = zipc_hip_deflate_batch(ctx, d_mid_arena, d_dst_arena, (const zipc_hip_stream_desc *)inner, (zipc_hip_stream_result *)inner_res, n,
+                              max_mid_cap, total_mid_cap, level, ZIPC_HIP_CRC_NOP);
+  if (st) return st;
+  ZD_LAUNCH(ctx, "recode_close", recode_close_kernel, grid, block, 0, (uint32_t)n, (const RecodeVerdict *)verdicts,
+            (const StreamResult *)inner_res, d_results, d_plain);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+
+int zipc_hip_recode_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_mid_arena, void *d_dst_arena,
+                          const zipc_hip_recode_desc *d_descs, zipc_hip_recode_result *d_results, size_t n_streams,
+                          size_t max_mid_cap, size_t total_mid_cap, int level) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull || level < 0 || level > 3) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (max_mid_cap > MAX_STREAM_LEN) return ZIPC_HIP_ERR_INVALID_ARG;  // (deflate takes no longer source; inflate_huge_stream's output is none)
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  return recode_sequence(ctx, d_src_arena, d_mid_arena, d_dst_arena, (const RecodeDesc *)d_descs, (RecodeResult *)d_results, nullptr,
+                         n_streams, max_mid_cap, total_mid_cap, level, nullptr, true);
+}
+
 // ---- the many-stream forms' way back: a sub-batch's outputs end to end, written by a kernel ----------------
 // What a sub-batch made goes into the pinned host buffer by a KERNEL's stores, one output behind the other on 16-byte
 // boundaries, not by the copy engine:
@@ -728,12 +783,24 @@ __global__ __launch_bounds__(256) void pack_copy_kernel(const uint8_t *dst_arena
   }
 }
 
+// what the kernels' step of a many-stream call is.  MANY_RECODE: the recode sequence above (crc_op: CRC-32); its middle
+// arena is one more buffer of the context, as large as the largest sub-batch needs, and beside the plain results the
+// pipeline works with, the call's zipc_hip_recode_results come back into pinned memory of their own (ctx->pin_rres).
+enum ManyOp { MANY_DEFLATE = 0, MANY_INFLATE = 1, MANY_RECODE = 2 };
+struct RecodeMany {
+  const size_t *mid_cap;
+  const uint32_t *expect_crc32;  // may be null
+};
+constexpr uint32_t MANY_RESULT_UNSET = 0xFFFFFFFFu;  // a status no call gives: an entry nothing has written yet
+
 // n host-resident streams through the batch kernels: arenas are the context's
 // staging buffers, streams packed at 256-byte aligned offsets
-static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void *const *src, const size_t *src_len,
+static int many_streams(zipc_hip_ctx *ctx, ManyOp op, size_t n, const void *const *src, const size_t *src_len,
                         const size_t *limit, int level, int crc_op, void *const *dst, const size_t *dst_cap,
-                        zipc_hip_stream_result *results, bool want_bytes = true) {
+                        zipc_hip_stream_result *results, bool want_bytes = true, const RecodeMany *rc = nullptr) {
+  const bool is_inflate = op == MANY_INFLATE, recode = op == MANY_RECODE;
   if (!ctx || (n && (!src || !src_len || (!dst && want_bytes) || !dst_cap || !results))) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (recode && (!rc || (n && !rc->mid_cap))) return ZIPC_HIP_ERR_INVALID_ARG;
   if (crc_op < 0 || crc_op > 3 || level < 0 || level > 3 || n > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
   if (n == 0) return ZIPC_HIP_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -744,7 +811,7 @@ static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void
   };
   std::vector<StreamDesc> descs(n);
   uint64_t so = 0, dof = 0;
-  size_t max_src = 0, max_cap = 0;
+  size_t max_src = 0, max_cap = 0, max_mid = 0;
   for (size_t i = 0; i < n; i++) {
     if ((!src[i] && src_len[i]) || (want_bytes && !dst[i] && dst_cap[i])) return ZIPC_HIP_ERR_INVALID_ARG;
     StreamDesc &d = descs[i];
@@ -755,8 +822,10 @@ static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void
     dof += (dst_cap[i] + 255) / 256 * 256 + 256;
     max_src = src_len[i] > max_src ? src_len[i] : max_src;
     max_cap = dst_cap[i] > max_cap ? dst_cap[i] : max_cap;
+    if (recode) max_mid = rc->mid_cap[i] > max_mid ? rc->mid_cap[i] : max_mid;
   }
-  if (!is_inflate && max_src > MAX_STREAM_LEN) return ZIPC_HIP_ERR_INVALID_ARG;  // (inflate reports it per stream)
+  if (op == MANY_DEFLATE && max_src > MAX_STREAM_LEN) return ZIPC_HIP_ERR_INVALID_ARG;  // (inflate reports it per stream)
+  if (recode && max_mid > MAX_STREAM_LEN) return ZIPC_HIP_ERR_INVALID_ARG;              // (zipc_hip_recode_batch's rule)
   // The batch is cut into K sub-batches, and sub-batch g goes through
   //   gather (host threads, into pinned memory) -> copy in (the engine, queue copy_in, in runs of 16 MiB as they are
   //   gathered) -> kernels (the context's queue) -> the way back (the kernel above, queue copy_out) -> scatter (host threads)
@@ -792,6 +861,33 @@ static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void
     total_max = t > total_max ? t : total_max;
   }
   const bool packed = zd::tuning().host_pack && want_bytes;  // (false: whole destination slots by the copy engine)
+  // recode: every sub-batch's streams get their room in the middle arena from its beginning on; what inflate is handed
+  // is known here (recode_open is the kernel's rule), so the block path has nothing to read back
+  std::vector<RecodeDesc> rdescs;
+  std::vector<StreamDesc> h_inflate;
+  uint64_t mid_arena = 0;
+  size_t mid_total_max = 0;
+  if (recode) {
+    rdescs.resize(n);
+    h_inflate.resize(n);
+    for (size_t g = 0; g < K; g++) {
+      uint64_t mo = 0;
+      size_t t = 0;
+      for (size_t i = cut[g]; i < cut[g + 1]; i++) {
+        RecodeDesc &r = rdescs[i];
+        memset(&r, 0, sizeof r);
+        r.src_off = descs[i].src_off; r.src_len = descs[i].src_len; r.dst_off = descs[i].dst_off; r.dst_cap = descs[i].dst_cap;
+        r.mid_off = mo; r.mid_cap = rc->mid_cap[i];
+        r.limit = descs[i].limit; r.flags = descs[i].flags;
+        if (rc->expect_crc32) { r.expect_crc32 = rc->expect_crc32[i]; r.flags |= STREAM_EXPECT_CRC32; }
+        (void)recode_open(r, max_mid, &h_inflate[i]);
+        mo += (rc->mid_cap[i] + 255) / 256 * 256 + 256;
+        t += rc->mid_cap[i];
+      }
+      mid_arena = mo > mid_arena ? mo : mid_arena;
+      mid_total_max = t > mid_total_max ? t : mid_total_max;
+    }
+  }
   // everything is allocated before the first sub-batch is under way (growing a buffer
   // synchronises the stream)
   HIP_TRY(ctx, ctx->ensure(ctx->io_src, so + 64));
@@ -802,14 +898,25 @@ static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void
   HIP_TRY(ctx, ctx->ensure_pinned(ctx->pin_src, so + 64));
   if (want_bytes) HIP_TRY(ctx, ctx->ensure_pinned(ctx->pin_dst, dof + 64));
   HIP_TRY(ctx, ctx->ensure_pinned(ctx->pin_res, n * sizeof(StreamResult)));
-  if (!is_inflate) {
+  if (recode) {
+    HIP_TRY(ctx, ctx->ensure(ctx->io_mid, mid_arena + 64));
+    HIP_TRY(ctx, ctx->ensure(ctx->io_rdesc, n * sizeof(RecodeDesc)));
+    HIP_TRY(ctx, ctx->ensure(ctx->io_rres, n * sizeof(RecodeResult)));
+    HIP_TRY(ctx, ctx->ensure_pinned(ctx->pin_rres, n * sizeof(RecodeResult)));
+    memset(ctx->pin_rres.p, 0xFF, n * sizeof(RecodeResult));  // (MANY_RESULT_UNSET: what has not come back says so)
+    int st = recode_reserve(ctx, n_max);
+    if (st) return st;
+    st = zipc_hip_reserve(ctx, n_max, max_mid, mid_total_max);
+    if (st) return st;
+  }
+  if (op == MANY_DEFLATE) {
     const int st = zipc_hip_reserve(ctx, n_max, max_src, total_max);
     if (st) return st;
   } else {
     HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_max * INFLATE_SCRATCH_PER_STREAM));
   }
   if (crc_op == ZIPC_HIP_CRC_CRC32) {
-    const size_t longest = is_inflate ? max_cap : max_src;
+    const size_t longest = recode ? max_mid : is_inflate ? max_cap : max_src;
     size_t segs = (longest + CRC_SEG_BYTES - 1) / CRC_SEG_BYTES;
     HIP_TRY(ctx, ctx->ensure(ctx->crc_partials, n_max * (segs ? segs : 1) * sizeof(uint32_t)));
   }
@@ -844,6 +951,11 @@ static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void
     EventSet &ev_in, &ev_k, &ev_out, &ev_t;
     decltype(dst_end) &dst_end_of;
     std::string error;
+    // MANY_RECODE: the call's recode descriptors, what inflate is handed of them, the streams' room and the largest
+    const RecodeDesc *rdescs = nullptr;
+    const StreamDesc *h_inflate = nullptr;
+    const size_t *mid_cap = nullptr;
+    size_t max_mid = 0;
 #define PIPE_TRY(expr)                                                                   \
   do {                                                                                   \
     hipError_t _e = (expr);                                                              \
@@ -855,6 +967,7 @@ static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void
     int begin() {
       if (timing) PIPE_TRY(hipEventRecord(ev_t.ev[0], ctx->copy_in));
       PIPE_TRY(hipMemcpyAsync(ctx->io_desc.p, descs.data(), n * sizeof(StreamDesc), hipMemcpyHostToDevice, ctx->copy_in));
+      if (rdescs) PIPE_TRY(hipMemcpyAsync(ctx->io_rdesc.p, rdescs, n * sizeof(RecodeDesc), hipMemcpyHostToDevice, ctx->copy_in));
       return ZIPC_HIP_OK;
     }
     int send(size_t g, bool first, uint64_t from, uint64_t to) {
@@ -875,7 +988,16 @@ static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void
       size_t total_g = 0;
       for (size_t i = lo; i < hi; i++) total_g += src_len[i];
       int st;
-      if (is_inflate)  // (with the descriptors it has on the host: no read-back, nothing waited for unless a stream goes by blocks)
+      if (rdescs) {  // (the plain results the way back works with are recode_close_kernel's second output)
+        size_t total_mid = 0;
+        for (size_t i = lo; i < hi; i++) total_mid += mid_cap[i];
+        st = recode_sequence(ctx, ctx->io_src.p, ctx->io_mid.p, ctx->io_dst.p, (const RecodeDesc *)ctx->io_rdesc.p + lo,
+                             (RecodeResult *)ctx->io_rres.p + lo, (StreamResult *)dr, hi - lo, max_mid, total_mid, level, h_inflate + lo,
+                             first_batch);
+        if (st == ZIPC_HIP_OK)
+          PIPE_TRY(hipMemcpyAsync((RecodeResult *)ctx->pin_rres.p + lo, (const RecodeResult *)ctx->io_rres.p + lo,
+                                  (hi - lo) * sizeof(RecodeResult), hipMemcpyDeviceToHost, ctx->stream));
+      } else if (is_inflate)  // (with the descriptors it has on the host: no read-back, nothing waited for unless a stream goes by blocks)
         st = launch_inflate(ctx, ctx->io_src.p, ctx->io_dst.p, dd, dr, hi - lo, max_cap, crc_op, descs.data() + lo, first_batch);
       else
         st = zipc_hip_deflate_batch(ctx, ctx->io_src.p, ctx->io_dst.p, dd, dr, hi - lo, max_src, total_g, level, crc_op);
@@ -919,7 +1041,8 @@ static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void
   job.n = n; job.src = src; job.src_len = src_len; job.dst = dst; job.dst_cap = dst_cap; job.results = results;
   job.descs = descs.data(); job.src_arena_end = so; job.dst_arena_end = dof;
   job.cut = cut; job.n_max = n_max; job.packed = packed; job.want_bytes = want_bytes;
-  job.ahead = is_inflate && max_cap >= BLOCKS_BATCH_MIN_DST;
+  if (recode) { dev.rdescs = rdescs.data(); dev.h_inflate = h_inflate.data(); dev.mid_cap = rc->mid_cap; dev.max_mid = max_mid; }
+  job.ahead = (is_inflate && max_cap >= BLOCKS_BATCH_MIN_DST) || (recode && max_mid >= BLOCKS_BATCH_MIN_DST);
   job.h2d_bytes = (uint64_t)16 << 20;  // (sources sent in runs of about 16 MiB as they are gathered)
   job.pin_src = (uint8_t *)ctx->pin_src.p; job.pin_dst = want_bytes ? (const uint8_t *)ctx->pin_dst.p : nullptr;
   job.pin_res = (const zipc_hip_stream_result *)ctx->pin_res.p;
@@ -938,7 +1061,7 @@ static int many_streams(zipc_hip_ctx *ctx, bool is_inflate, size_t n, const void
   if (timing) {  // where each sub-batch was when: host clock from the call's begin, device clock from the first copy's begin
     fprintf(stderr, "zipc_hip %s_many n=%zu src_arena=%llu dst_arena=%llu ms: setup %.2f feed %.2f (of it gather %.2f) "
                     "scatter %.2f whole %.2f (threads %zu sub-batches %zu)\n",
-            is_inflate ? "inflate" : "deflate", n, (unsigned long long)so, (unsigned long long)dof, ms_setup, times.ms_feed,
+            recode ? "recode" : is_inflate ? "inflate" : "deflate", n, (unsigned long long)so, (unsigned long long)dof, ms_setup, times.ms_feed,
             times.ms_gather, times.ms_scatter, since(t_begin), host_threads(), K);
     for (size_t g = 0; g < K; g++) {
       if (cut[g] == cut[g + 1]) continue;
@@ -966,19 +1089,67 @@ static int many_threw(zipc_hip_ctx *ctx, size_t n, zipc_hip_stream_result *resul
 }
 int zipc_hip_deflate_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len, int level,
                           int crc_op, void *const *dst, const size_t *dst_cap, zipc_hip_stream_result *results) {
-  try { return many_streams(ctx, false, n, src, src_len, nullptr, level, crc_op, dst, dst_cap, results); }
+  try { return many_streams(ctx, MANY_DEFLATE, n, src, src_len, nullptr, level, crc_op, dst, dst_cap, results); }
   catch (...) { return many_threw(ctx, n, results); }
 }
 int zipc_hip_inflate_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len,
                           const size_t *limit, int crc_op, void *const *dst, const size_t *dst_cap,
                           zipc_hip_stream_result *results) {
-  try { return many_streams(ctx, true, n, src, src_len, limit, 0, crc_op, dst, dst_cap, results); }
+  try { return many_streams(ctx, MANY_INFLATE, n, src, src_len, limit, 0, crc_op, dst, dst_cap, results); }
   catch (...) { return many_threw(ctx, n, results); }
 }
 int zipc_hip_inflate_many_check(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len,
                                 const size_t *limit, int crc_op, const size_t *dst_cap, zipc_hip_stream_result *results) {
-  try { return many_streams(ctx, true, n, src, src_len, limit, 0, crc_op, nullptr, dst_cap, results, false); }
+  try { return many_streams(ctx, MANY_INFLATE, n, src, src_len, limit, 0, crc_op, nullptr, dst_cap, results, false); }
   catch (...) { return many_threw(ctx, n, results); }
+}
+
+
+// zipc_hip_recode_many: many_streams with the recode sequence as its kernels' step.  The pipeline works with plain
+// results (status, checksum, out_len); the zipc_hip_recode_results come back beside them into ctx->pin_rres, on the
+// context's queue in front of the event the pipeline waits for before it takes a sub-batch.
+//  * The call succeeded: every sub-batch was taken, and results[] is what came back.
+//  * The call failed: the pipeline has overwritten the plain results of the sub-batches it did not take with the call's
+//    status and no bytes, and does not say which those were.  A stream keeps what came back for it only where that says
+//    the same as its plain result: an OK stream's plain result is OK only if its sub-batch was taken (its bytes are in
+//    the caller's buffer), and a stream that stopped has no bytes either way, so its own verdict is as true as the
+//    call's.  Every other entry carries the plain status at stage 0.
+static int recode_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len, const size_t *limit,
+                       const uint32_t *expect_crc32, const size_t *mid_cap, int level, void *const *dst, const size_t *dst_cap,
+                       zipc_hip_recode_result *results) {
+  auto fail = [&](int st) {
+    if (results) for (size_t i = 0; i < n; i++) results[i] = zipc_hip_recode_result{(uint32_t)st, 0, 0, 0, 0, 0};
+    return st;
+  };
+  if (!ctx || (n && (!src || !src_len || !mid_cap || !dst || !dst_cap || !results)) || level < 0 || level > 3) return fail(ZIPC_HIP_ERR_INVALID_ARG);
+  for (size_t i = 0; i < n; i++)
+    if ((!src[i] && src_len[i]) || (!dst[i] && dst_cap[i])) return fail(ZIPC_HIP_ERR_INVALID_ARG);
+  if (n == 0) return ZIPC_HIP_OK;
+  std::vector<zipc_hip_stream_result> plain(n, zipc_hip_stream_result{MANY_RESULT_UNSET, 0, 0});
+  const RecodeMany rc{mid_cap, expect_crc32};
+  const int st = many_streams(ctx, MANY_RECODE, n, src, src_len, limit, level, ZIPC_HIP_CRC_CRC32, dst, dst_cap, plain.data(), true, &rc);
+  const zipc_hip_recode_result *back = ctx->pin_rres.cap >= n * sizeof(RecodeResult) ? (const zipc_hip_recode_result *)ctx->pin_rres.p : nullptr;
+  if (st == ZIPC_HIP_OK && back) {
+    memcpy(results, back, n * sizeof *results);
+    return st;
+  }
+  for (size_t i = 0; i < n; i++) {
+    const zipc_hip_stream_result &p = plain[i];
+    if (p.status == MANY_RESULT_UNSET) results[i] = zipc_hip_recode_result{(uint32_t)(st ? st : ZIPC_HIP_ERR_HIP), 0, 0, 0, 0, 0};  // (the pipeline never ran)
+    else if (back && back[i].status == p.status && back[i].out_len == p.out_len) results[i] = back[i];
+    else results[i] = zipc_hip_recode_result{p.status, 0, 0, 0, 0, 0};
+  }
+  return st;
+}
+int zipc_hip_recode_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len, const size_t *limit,
+                         const uint32_t *expect_crc32, const size_t *mid_cap, int level, void *const *dst, const size_t *dst_cap,
+                         zipc_hip_recode_result *results) {
+  try { return recode_many(ctx, n, src, src_len, limit, expect_crc32, mid_cap, level, dst, dst_cap, results); }
+  catch (...) {
+    try { if (ctx) ctx->last_error = "zipc_hip: out of memory (or no thread) on the host while setting up a many-stream call"; } catch (...) {}
+    if (results) for (size_t i = 0; i < n; i++) results[i] = zipc_hip_recode_result{ZIPC_HIP_ERR_NOMEM, 0, 0, 0, 0, 0};
+    return ZIPC_HIP_ERR_NOMEM;
+  }
 }
 
 // ---- the zlib container (zlib_container.h has the rules; zlib.hip the two kernels of the batch forms) --------------
@@ -1070,7 +1241,7 @@ static int zlib_many(zipc_hip_ctx *ctx, bool decompress, size_t n, const void *c
     if (p.status != ST_OK) { in_len[i] = 0; in_cap[i] = 0; }
     results[i] = zipc_hip_stream_result{ZLIB_RESULT_UNSET, 0, 0};
   }
-  const int st = many_streams(ctx, decompress, n, in_src.data(), in_len.data(), decompress ? limit : nullptr, level, zlib_crc_op(ctx),
+  const int st = many_streams(ctx, decompress ? MANY_INFLATE : MANY_DEFLATE, n, in_src.data(), in_len.data(), decompress ? limit : nullptr, level, zlib_crc_op(ctx),
                               in_dst.data(), in_cap.data(), results);
   for (size_t i = 0; i < n; i++) {
     StreamResult inner{results[i].status, results[i].checksum, results[i].out_len};

@@ -53,6 +53,9 @@ struct zipc_hip_ctx {
   Buf blocks_scratch, tok_scratch;                // inflate of streams by a wave per block: candidates, chains; a word per output byte
   Buf descs_marked;                               // ... a call's descriptors with those streams marked as done, for the one waves of the rest
   Buf zlib_descs, zlib_pre;                       // the zlib batch forms: the descriptors the codec runs with, the container checks' verdicts (zlib.hip)
+  Buf recode_descs, recode_res, recode_verdicts;  // the recode forms: the descriptors inflate, then deflate run with, their results, what is known of a stream between the steps (recode.hip)
+  Buf io_mid, io_rdesc, io_rres;                  // ... of host streams: the middle arena of a sub-batch, the call's recode descriptors and results
+  Buf pin_rres;                                   // ... the results as they come back (pinned)
   Buf chain_check_links;                          // lz_chain's run-time check: the links the exchange kernel made of a batch's first streams
   unsigned long long *chain_check_host = nullptr; // ... [0] differences, [1] positions compared in the context's first batch; [2], [3]: the same for the create-time probe (device-visible host memory)
   bool chain_checked = false;                     // ... that first batch has been seen

@@ -1,7 +1,8 @@
 // kernels.h -- the kernels, constants and structs that more than one translation unit needs: checksum.hip's (api.hip, deflate.hip)
-// and zlib.hip's (api.hip).  deflate.hip and inflate.hip keep theirs to themselves, behind launch_deflate / launch_inflate (ctx.h).
+// and zlib.hip's and recode.hip's (api.hip).  deflate.hip and inflate.hip keep theirs to themselves, behind launch_deflate / launch_inflate (ctx.h).
 #pragma once
 
+#include "recode_rules.h"
 #include "zd_common.h"
 
 namespace zd {
@@ -13,6 +14,14 @@ __global__ void zlib_open_kernel(const uint8_t *__restrict__ src_arena, const St
 __global__ void zlib_close_kernel(uint8_t *__restrict__ dst_arena, const StreamDesc *__restrict__ descs,
                                   const ZlibPre *__restrict__ pre, StreamResult *__restrict__ results, uint32_t n_streams,
                                   int compress, int level);
+
+// ---- recode.hip: before, between and behind inflate and deflate of a batch, a lane per stream (rules: recode_rules.h)
+__global__ void recode_open_kernel(const RecodeDesc *__restrict__ descs, uint32_t n_streams, uint64_t max_mid_cap,
+                                   StreamDesc *__restrict__ inner, RecodeVerdict *__restrict__ verdicts);
+__global__ void recode_link_kernel(const RecodeDesc *__restrict__ descs, uint32_t n_streams, const StreamResult *__restrict__ inflated,
+                                   StreamDesc *__restrict__ inner, RecodeVerdict *__restrict__ verdicts);
+__global__ void recode_close_kernel(uint32_t n_streams, const RecodeVerdict *__restrict__ verdicts, const StreamResult *__restrict__ deflated,
+                                    RecodeResult *__restrict__ results, StreamResult *__restrict__ plain);
 
 // ---- checksum.hip
 constexpr uint32_t CRC_PIECE_BYTES = 128;  // bytes per thread of crc32_segments_kernel

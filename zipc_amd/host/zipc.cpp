@@ -596,4 +596,44 @@ std::vector<std::pair<Fpath::t, Result<Unit>>> Archive::test_all() const {
   return out;
 }
 
+std::vector<std::pair<Fpath::t, Result<Unit>>> Archive::recode_deflated(std::optional<zipc_deflate::level> level) {
+  std::vector<std::pair<Fpath::t, Result<Unit>>> out;
+  std::vector<zipc_deflate::RecodeItem> items;
+  std::vector<const Member *> members;
+  for (const auto &kv : members_) {
+    const Member &m = kv.second;
+    if (m.is_dir()) continue;
+    const File &f = m.file();
+    if (f.compression_().kind != compression::Deflate || f.is_encrypted()) continue;
+    zipc_deflate::RecodeItem it;
+    it.data = f.compressed_bytes().data() + f.start();
+    it.len = (std::size_t)f.compressed_size();
+    it.decompressed_size = (std::size_t)f.decompressed_size();
+    it.expect_crc_32 = f.decompressed_crc_32();
+    items.push_back(it);
+    members.push_back(&m);
+  }
+  auto res = zipc_deflate::recode_many(items, level);
+  std::vector<Member> made;
+  bool all_ok = true;
+  for (std::size_t k = 0; k < items.size(); k++) {
+    const Member &m = *members[k];
+    if (!res[k].ok) {  // (the texts of File::to_binary_string: the CRC's message as it is, inflate's behind "deflate: ")
+      out.push_back({m.path(), Result<Unit>::Error(res[k].stage == 2 ? res[k].error : "deflate: " + res[k].error)});
+      all_ok = false;
+      continue;
+    }
+    // (the length it inflated to, as deflate_of_binary_string takes the string's: the directory's size is only the most it may be)
+    auto f = File::make(compression::of_int(8), std::make_shared<const std::string>(std::move(res[k].value)), (long long)res[k].decompressed_size,
+                        res[k].checksum);
+    auto mm = f.ok ? Member::make(m.path(), std::move(f.value), m.mtime(), m.mode()) : Result<Member>::Error(f.error);
+    if (!mm.ok) { out.push_back({m.path(), Result<Unit>::Error(mm.error)}); all_ok = false; continue; }
+    made.push_back(std::move(mm.value));
+    out.push_back({m.path(), Result<Unit>::Ok(Unit{})});
+  }
+  if (all_ok)
+    for (const Member &m : made) add(m);
+  return out;
+}
+
 }  // namespace zipc

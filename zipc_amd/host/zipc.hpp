@@ -10,7 +10,7 @@
 //
 // Beyond the reference (which handles one member per call) Archive has two batch
 // operations that hand all members to the GPU at once -- the use the hot path was
-// built for: add_deflated_files and extract_all.
+// built for: add_deflated_files and extract_all -- and recode_deflated, which is both in one.
 #pragma once
 
 #include <map>
@@ -169,6 +169,13 @@ class Archive {  // type t and its functions, zipc.mli:287-384
   // the device and only their results come back; the others take the single-member path.  Same members, same order, same
   // messages as extract_all.
   std::vector<std::pair<Fpath::t, Result<Unit>>> test_all() const;
+  // File.to_binary_string |> File.deflate_of_binary_string ?level of every Deflate, non-encrypted file member (the
+  // reference's `recode --deflate`, test/zipc_tool.ml:437-545) as ONE batch that stays on the device: every member is
+  // inflated to at most the directory's size, its CRC-32 held against the directory's, and deflated again
+  // (zipc_deflate::recode_many).  Per such member, in path order, Ok or to_binary_string's error text; when all are Ok the
+  // members are replaced, path, mtime and mode kept, the size the length a member really inflated to (the directory's may
+  // say more), as deflate_of_binary_string takes it from the string -- otherwise the archive stays as it is.
+  std::vector<std::pair<Fpath::t, Result<Unit>>> recode_deflated(std::optional<zipc_deflate::level> level = std::nullopt);
 
  private:
   std::map<std::string, Member> members_;

@@ -440,4 +440,44 @@ std::vector<ManyResult> inflate_and_crc_32_many(const std::vector<ManyItem> &ite
   return out;
 }
 
+std::vector<RecodeResult> recode_many(const std::vector<RecodeItem> &items, std::optional<level> lvl) {
+  const std::size_t n = items.size();
+  std::vector<RecodeResult> out(n);
+  std::vector<const void *> src(n);
+  std::vector<void *> dst(n);
+  std::vector<std::size_t> len(n), mid(n), limit(n), cap(n);
+  std::vector<uint32> expect(n);
+  std::vector<ManyItem> by_output(n);  // the work goes by the decompressed bytes
+  std::size_t n_expect = 0;
+  for (std::size_t i = 0; i < n; i++) {
+    if (!items[i].decompressed_size) throw std::invalid_argument("recode_many: decompressed_size missing");
+    src[i] = items[i].data;
+    len[i] = items[i].len;
+    mid[i] = limit[i] = *items[i].decompressed_size;
+    cap[i] = zipc_hip_deflate_bound(mid[i]);
+    out[i].value.resize(cap[i]);
+    dst[i] = &out[i].value[0];
+    if (items[i].expect_crc_32) { expect[i] = *items[i].expect_crc_32; n_expect++; }
+    by_output[i].len = mid[i];
+  }
+  if (n_expect != 0 && n_expect != n) throw std::invalid_argument("recode_many: expect_crc_32 for all items or for none");
+  std::vector<zipc_hip_recode_result> res(n);
+  over_devices(by_output, [&](zipc_hip_ctx *ctx, std::size_t lo, std::size_t hi) {
+    const int st = zipc_hip_recode_many(ctx, hi - lo, src.data() + lo, len.data() + lo, limit.data() + lo, n_expect ? expect.data() + lo : nullptr,
+                                        mid.data() + lo, level_of(lvl), dst.data() + lo, cap.data() + lo, res.data() + lo);
+    if (st) throw std::runtime_error(std::string("zipc_hip_recode_many: ") + message(st) + " (" + zipc_hip_last_error(ctx) + ")");
+  });
+  for (std::size_t i = 0; i < n; i++) {
+    if (res[i].status != ZIPC_HIP_ERR_CHECKSUM) throw_if_library_failure((int)res[i].status);
+    out[i].ok = res[i].status == ZIPC_HIP_OK;
+    out[i].value.resize(out[i].ok ? res[i].out_len : 0);
+    out[i].checksum = res[i].checksum;
+    out[i].stage = (int)res[i].stage;
+    out[i].decompressed_size = (std::size_t)res[i].mid_len;
+    if (res[i].status == ZIPC_HIP_ERR_CHECKSUM) out[i].error = crc_error(expect[i], res[i].checksum);
+    else if (!out[i].ok) out[i].error = message((int)res[i].status);
+  }
+  return out;
+}
+
 }  // namespace zipc_deflate

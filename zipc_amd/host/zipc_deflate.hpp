@@ -150,4 +150,23 @@ std::vector<ManyResult> inflate_and_crc_32_many(const std::vector<ManyItem> &ite
 // from the device (zipc_hip_inflate_many_check: what testing an archive takes)
 std::vector<ManyResult> inflate_and_crc_32_many_check(const std::vector<ManyItem> &items);
 
+// inflate_and_crc_32, Crc_32.check and deflate of every item in one go (zipc_hip_recode_many): what the reference's
+// `recode` does to a member (test/zipc_tool.ml:437-545, test/test.ml:58-74 redeflate_recode), with the decompressed
+// bytes staying on the device -- the old stream crosses the bus on the way in, the new one on the way back.  Items
+// need decompressed_size; expect_crc_32 is given for all of them or for none.  Per item: ok, value = the recoded
+// stream, checksum = the CRC-32 of the decompressed bytes; or error = inflate's message (stage 1), or Crc_32.check's
+// (stage 2): zipc_hip_recode_result's stages.  decompressed_size: what the stream inflated to -- the item's
+// decompressed_size is only the most it may be (inflate's ?decompressed_size), and a recoded member has this one.
+struct RecodeItem {
+  const char *data = nullptr;
+  std::size_t len = 0;
+  std::optional<std::size_t> decompressed_size;
+  std::optional<Crc_32::t> expect_crc_32;
+};
+struct RecodeResult : ManyResult {
+  int stage = 0;
+  std::size_t decompressed_size = 0;
+};
+std::vector<RecodeResult> recode_many(const std::vector<RecodeItem> &items, std::optional<level> lvl = std::nullopt);
+
 }  // namespace zipc_deflate

@@ -194,6 +194,15 @@ int zipc_host_add_files_deflate(zipc_host_archive *a, size_t n, const char *cons
   });
 }
 
+int zipc_host_recode_deflated(zipc_host_archive *a, int level, char *err, size_t errcap) {
+  if (!a || level > 3) return ZIPC_HOST_INVALID;
+  return guarded(err, errcap, [&] {
+    for (const auto &r : a->z.recode_deflated(opt_level(level)))
+      if (!r.second.ok) { set_err(err, errcap, r.first + ": " + r.second.error); return (int)ZIPC_HOST_ERROR; }
+    return (int)ZIPC_HOST_OK;
+  });
+}
+
 size_t zipc_host_encoding_size(const zipc_host_archive *a) { return a ? a->z.encoding_size() : 0; }
 
 int zipc_host_to_binary_string(const zipc_host_archive *a, const char *first, size_t first_len, void *dst, size_t cap,

@@ -352,7 +352,27 @@ int main(int argc, char **argv) {
       if (a.recode_as != 0) {
         std::vector<std::string> datas;
         std::vector<zipc::Archive::NewFile> files;
-        for (const auto &r : z.extract_all()) {  // (members that cannot be decoded are kept as they are; so are directories)
+        // --deflate: the deflated members are inflated, checked and deflated again in one batch that stays on the device
+        // (Archive::recode_deflated); only the stored ones are extracted here and added below.  The first member in path
+        // order that fails ends the command, whichever way it went.
+        std::vector<std::pair<zipc::Fpath::t, zipc_deflate::Result<std::string>>> extracted;
+        std::vector<std::string> recoded_on_device;
+        if (a.recode_as == 1) {
+          std::map<std::string, std::string> errors;  // path -> message, of both ways
+          for (const auto &r : out.recode_deflated(a.level)) {
+            if (r.second.ok) recoded_on_device.push_back(r.first);
+            else errors[r.first] = r.second.error;
+          }
+          z.fold([&](const zipc::Member &m) {
+            if (m.is_dir() || !m.file().can_extract() || m.file().compression_().kind == zipc::compression::Deflate) return;
+            extracted.push_back({m.path(), m.file().to_binary_string()});
+            if (!extracted.back().second.ok) errors[m.path()] = extracted.back().second.error;
+          });
+          if (!errors.empty()) die(errors.begin()->first + ": " + errors.begin()->second);
+        } else {
+          extracted = z.extract_all();
+        }
+        for (const auto &r : extracted) {  // (members that cannot be decoded are kept as they are; so are directories)
           const zipc::Member *m = z.find(r.first);
           if (!m || m->is_dir() || !m->file().can_extract()) continue;  // (File.can_extract: kept as it is, zipc_tool.ml:432)
           if (!r.second.ok) die(r.first + ": " + r.second.error);
@@ -376,13 +396,16 @@ int main(int argc, char **argv) {
             out.add(m.value);
           }
         }
-        for (const auto &f : files) {  // err_checksum, zipc_tool.ml:426-428
-          const zipc_deflate::uint32 was = z.find(f.path)->file().decompressed_crc_32(), now = out.find(f.path)->file().decompressed_crc_32();
+        std::vector<std::string> recoded = recoded_on_device;
+        for (const auto &f : files) recoded.push_back(f.path);
+        std::sort(recoded.begin(), recoded.end());  // (path order, as the members were handled)
+        for (const auto &path : recoded) {  // err_checksum, zipc_tool.ml:426-428
+          const zipc_deflate::uint32 was = z.find(path)->file().decompressed_crc_32(), now = out.find(path)->file().decompressed_crc_32();
           if (was != now)
-            die(f.path + ": Recoding changed the checksum from " + zipc_deflate::Crc_32::pp(was) + " to " + zipc_deflate::Crc_32::pp(now) + " (zipc bug)");
+            die(path + ": Recoding changed the checksum from " + zipc_deflate::Crc_32::pp(was) + " to " + zipc_deflate::Crc_32::pp(now) + " (zipc bug)");
           if (a.verbose) {
-            const zipc::File &o = z.find(f.path)->file(), &n = out.find(f.path)->file();
-            std::cerr << "Recode " << pct(n.compressed_size(), n.decompressed_size()) << " (was " << pct(o.compressed_size(), o.decompressed_size()) << ") " << f.path << "\n";
+            const zipc::File &o = z.find(path)->file(), &n = out.find(path)->file();
+            std::cerr << "Recode " << pct(n.compressed_size(), n.decompressed_size()) << " (was " << pct(o.compressed_size(), o.decompressed_size()) << ") " << path << "\n";
           }
         }
       }

@@ -315,3 +315,52 @@ def zlib_decompress_many(streams, decompressed_size=None, ctx=None):
                 out[i] = Error((None, _message(r.status, data[i][0] & 0x0F if data[i] else 0)))
         todo = again
     return out
+
+
+def recode_many(streams, decompressed_size=None, expect_crc32=None, level=None, ctx=None):
+    """Every raw deflate stream inflated, its CRC-32 checked and deflated again at `level` in one call
+    (zipc_hip_recode_many): what the reference's `recode` does to a member (test/zipc_tool.ml:437-545) -- inflate_and_crc_32,
+    Crc_32.check, deflate -- with the decompressed bytes staying on the device.  A list of Ok((crc32, bytes)) |
+    Error(message): inflate's message, or Crc_32.check's.  decompressed_size / expect_crc32: None, or one value per stream.
+    Without sizes every stream starts with room for three times its length, as inflate does, and the streams that need
+    more go again."""
+    ctx = ctx or default_context()
+    data = [bytes(s) for s in streams]
+    n = len(data)
+    has_limit = decompressed_size is not None
+    if has_limit and len(decompressed_size) != n:
+        raise ValueError("decompressed_size: one size per stream")
+    if expect_crc32 is not None and len(expect_crc32) != n:
+        raise ValueError("expect_crc32: one value per stream")
+    out = [None] * n
+    todo = list(range(n))
+    mids = {i: (decompressed_size[i] if has_limit else max(3 * len(data[i]), 1024)) for i in todo}
+    while todo:
+        m = len(todo)
+        keep, sp = _many_arrays([data[i] for i in todo])  # (the copies the pointers point into live until the call is through)
+        caps = [lib().zipc_hip_deflate_bound(mids[i]) for i in todo]
+        bufs = [C.create_string_buffer(c) for c in caps]
+        _, dp = _many_arrays(bufs)
+        res = (_lib.RecodeResult * m)()
+        lim = (C.c_size_t * m)(*[decompressed_size[i] for i in todo]) if has_limit else None
+        crc = (C.c_uint32 * m)(*[expect_crc32[i] & 0xFFFFFFFF for i in todo]) if expect_crc32 is not None else None
+        st = lib().zipc_hip_recode_many(ctx.handle, m, sp, (C.c_size_t * m)(*[len(data[i]) for i in todo]), lim, crc,
+                                        (C.c_size_t * m)(*[mids[i] for i in todo]), _level(level), dp, (C.c_size_t * m)(*caps), res)
+        if st != OK:
+            ctx.check(st)
+        del keep
+        again = []
+        for i, r, b in zip(todo, res, bufs):
+            if r.status == ERR_DST_TOO_SMALL and r.stage == 1 and not has_limit:
+                mids[i] *= 2
+                again.append(i)
+            elif r.status == OK:
+                out[i] = Ok((int(r.checksum), b.raw[:r.out_len]))
+            elif r.status == ERR_CHECKSUM:
+                out[i] = Error(crc_error(expect_crc32[i] & 0xFFFFFFFF, int(r.checksum)))
+            elif r.status in (_lib.ERR_HIP, _lib.ERR_INVALID_ARG, _lib.ERR_NO_DEVICE, _lib.ERR_NOMEM) or r.stage == 3:
+                ctx.check(r.status)  # (stage 3: the destination is deflate's bound -- the library's own failure)
+            else:
+                out[i] = Error(_message(r.status))
+        todo = again
+    return out

@@ -42,6 +42,7 @@ SYMBOLS = [
     ("zipc_host_add_file_deflate", C.c_int,
      [_P, C.c_char_p, _SZ, _P, _SZ, C.c_int, C.POINTER(MemberOpts), C.c_char_p, _SZ]),
     ("zipc_host_add_files_deflate", C.c_int, [_P, _SZ, _P, _P, _P, _P, C.c_int, C.c_char_p, _SZ]),
+    ("zipc_host_recode_deflated", C.c_int, [_P, C.c_int, C.c_char_p, _SZ]),
     ("zipc_host_encoding_size", _SZ, [_P]),
     ("zipc_host_to_binary_string", C.c_int, [_P, C.c_char_p, _SZ, _P, _SZ, C.POINTER(_SZ), C.c_char_p, _SZ]),
     ("zipc_host_member_to_binary_string", C.c_int,
@@ -183,6 +184,11 @@ class Archive:
         err = C.create_string_buffer(_ERRCAP)
         _check(lib().zipc_host_add_files_deflate(self._h, n, paths, plens, datas, dlens, -1 if level is None else level,
                                                  err, _ERRCAP), err)
+
+    def recode_deflated(self, level=None):
+        """every deflated file member inflated, CRC-checked and deflated again at `level`, one batch that stays on the GPU"""
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().zipc_host_recode_deflated(self._h, -1 if level is None else level, err, _ERRCAP), err)
 
     def encoding_size(self):
         return lib().zipc_host_encoding_size(self._h)
