@@ -181,7 +181,10 @@ size_t zipc_hip_zlib_bound(size_t len);
 /* deflate / crc_32_and_deflate / adler_32_and_deflate
  * (zipc_deflate.mli:128-150; zipc_deflate.ml:1247-1260).  level is explicit
  * here; the shim passes ZIPC_HIP_LEVEL_BEST when ?level is absent, which is
- * what the reference does (zipc_deflate.ml:817). */
+ * what the reference does (zipc_deflate.ml:817).  dst_cap: the rule stated at
+ * zipc_hip_deflate_batch decides whether the stream fits (it is not "the output
+ * fits"; zipc_hip_deflate_bound(len) always does); ZIPC_HIP_ERR_DST_TOO_SMALL
+ * leaves *out_len = 0, *checksum = 0 and dst as it was. */
 int zipc_hip_deflate(zipc_hip_ctx *ctx, const void *src, size_t len, int level,
                      int crc_op, void *dst, size_t dst_cap, size_t *out_len,
                      uint32_t *checksum);
@@ -198,7 +201,8 @@ int zipc_hip_zlib_compress(zipc_hip_ctx *ctx, const void *src, size_t len, int l
  * instead of n calls of the single-stream forms -- Zipc.File.deflate_of_binary_string
  * / to_binary_string over all members (src/zipc.ml:180-186,208-231).  limit may
  * be NULL (no ?decompressed_size for any stream); a stream whose output does not
- * fit reports ZIPC_HIP_ERR_DST_TOO_SMALL (or the reference's size message when a
+ * fit (to deflate: by the dst_cap rule stated at zipc_hip_deflate_batch) reports
+ * ZIPC_HIP_ERR_DST_TOO_SMALL (or the reference's size message when a
  * limit is given) in its own result.  The call itself fails only for bad
  * arguments or HIP errors.
  * Staging: the call runs as a pipeline of a few sub-batches.  Each is gathered into
@@ -298,7 +302,25 @@ int zipc_hip_inflate_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_d
  * device against the descriptors: if a stream is longer than max_src_len or the sum exceeds
  * total_src_len, EVERY stream of the batch reports ZIPC_HIP_ERR_INVALID_ARG and nothing is
  * compressed. max_src_len above ZIPC_HIP_MAX_STREAM_LEN fails the call; a single descriptor
- * with src_len or dst_cap above it reports ZIPC_HIP_ERR_INVALID_ARG in its own result only. */
+ * with src_len or dst_cap above it reports ZIPC_HIP_ERR_INVALID_ARG in its own result only.
+ * dst_cap, the rule by which a stream fits -- the same in every form the library takes (a wave per stream, a wave per
+ * block) and in every call that deflates (the host forms, the zlib forms with the room their container leaves,
+ * zipc_hip_recode_batch); it is NOT "the output fits":
+ *   a compressing level: the blocks are tested one by one, in order, each before it is written.  A block passes when the
+ *     bits of the blocks in front of it plus its own size, rounded up to whole bytes, do not exceed dst_cap.  The size of a
+ *     fixed or a stored block is its real size; the size of a dynamic block is the reference's ESTIMATE of it
+ *     (bit_length_of_dynamic_huffman_block, zipc_deflate.ml:1071-1079), which counts the code-length symbols of every
+ *     block so far -- the reference never resets those counts -- and so is exact for a stream's first block and high
+ *     from the second on.  Hence a dst_cap that holds the whole output can be refused (70 000 zero bytes: 97 bytes of
+ *     output, 101 needed), and a block in the middle of a stream can be the one that decides;
+ *   ZIPC_HIP_LEVEL_NONE: the stream fits iff src_len + 5 * nblocks <= dst_cap, nblocks = 1 for an empty stream and
+ *     ceil(src_len / 65534) otherwise;
+ *   dst_cap = zipc_hip_deflate_bound(src_len) always fits.
+ * A stream that does not fit reports ZIPC_HIP_ERR_DST_TOO_SMALL with out_len 0.  Nothing is written behind dst_cap, nor at
+ * or behind the first whole byte of the first block that did not pass; in front of that, whole bytes of the blocks that
+ * passed may have been written (of a stream whose first block does not pass, and at ZIPC_HIP_LEVEL_NONE: nothing).  Its
+ * checksum is 0 with either Adler-32, and with ZIPC_HIP_CRC_CRC32 the CRC-32 of its source: that pass runs over the source
+ * whatever the verdict.  (zipc_hip_deflate hands out no checksum with an error status.) */
 int zipc_hip_deflate_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
                            const zipc_hip_stream_desc *d_descs,
                            zipc_hip_stream_result *d_results, size_t n_streams,
@@ -367,9 +389,9 @@ typedef struct {            /* 32 bytes */
  * its ZIPC_HIP_ERR_INVALID_ARG at stage 3).  level outside 0..3, or max_mid_cap above ZIPC_HIP_MAX_STREAM_LEN (one
  * stream's included: inflate's path for stored streams beyond 4 GiB has nothing deflate could take), fails the call
  * with ZIPC_HIP_ERR_INVALID_ARG.  Nothing is written behind any stream's dst_cap or mid_cap, and nothing to the
- * destination slot of a stream that stops at stage 0, 1 or 2; one that stops at stage 3 has what zipc_hip_deflate_batch
- * leaves of a stream that does not fit: nothing of the block that did not fit nor of those behind it (of a stream of one
- * block: nothing).
+ * destination slot of a stream that stops at stage 0, 1 or 2; one that stops at stage 3 did not fit by the dst_cap rule
+ * stated at zipc_hip_deflate_batch, and has what that call leaves of such a stream: nothing of the block that did not fit
+ * nor of those behind it (of a stream of one block: nothing).
  * The defining property: for every stream, the result and the destination bytes are what the caller gets from
  * zipc_hip_inflate_batch (ZIPC_HIP_CRC_CRC32) into the middle arena, the link rule above applied on the host, and
  * zipc_hip_deflate_batch (level, ZIPC_HIP_CRC_NOP) of the streams that go on. */

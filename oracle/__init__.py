@@ -31,7 +31,8 @@ MESSAGES = {
 class BlockInfo(C.Structure):
     _fields_ = [("kind", C.c_int), ("final", C.c_int), ("src_start", C.c_uint32),
                 ("src_len", C.c_uint32), ("n_syms", C.c_uint32),
-                ("nlen", C.c_int64), ("flen", C.c_int64), ("dlen", C.c_int64)]
+                ("nlen", C.c_int64), ("flen", C.c_int64), ("dlen", C.c_int64),
+                ("bit_start", C.c_int64), ("bit_end", C.c_int64)]
 
 
 def build(force: bool = False) -> str:

@@ -824,6 +824,11 @@ static inline void write_bits(encoder *e, uint64_t v, int count) {
   }
 }
 
+/* the writer's bit position, for the trace */
+static int64_t enc_bit_pos(const encoder *e) {
+  return (int64_t)e->dst.len * 8 + e->dst_bits_len;
+}
+
 /* write_non_compressed_block zd.ml:873-877 */
 static void write_non_compressed_block(encoder *e, int final) {
   int64_t len = e->block_src_len;
@@ -1055,11 +1060,13 @@ static void write_block(encoder *e, int final) {
     b->src_len = (uint32_t)e->block_src_len;
     b->n_syms = (uint32_t)e->block_syms_len;
     b->nlen = nlen; b->flen = flen; b->dlen = dlen;
+    b->bit_start = enc_bit_pos(e);
   }
-  e->n_blocks++;
   if (kind == ZD_BLOCK_STORED) write_non_compressed_block(e, final);
   else if (kind == ZD_BLOCK_FIXED) write_fixed_huffman_block(e, final);
   else write_dynamic_huffman_block(e, final);
+  if (e->blocks && e->n_blocks < e->max_blocks) e->blocks[e->n_blocks].bit_end = enc_bit_pos(e);
+  e->n_blocks++;
 }
 
 /* write_all_non_compressed zd.ml:1106-1116 (`None level fast path) */
@@ -1078,9 +1085,11 @@ static void write_all_non_compressed(encoder *e) {
       memset(b, 0, sizeof *b);
       b->kind = ZD_BLOCK_STORED; b->final = final;
       b->src_start = (uint32_t)start; b->src_len = (uint32_t)len;
+      b->bit_start = enc_bit_pos(e);
     }
-    e->n_blocks++;
     write_non_compressed_block(e, final);
+    if (e->blocks && e->n_blocks < e->max_blocks) e->blocks[e->n_blocks].bit_end = enc_bit_pos(e);
+    e->n_blocks++;
     if (final) return;
     e->block_src_start = start + len;
   }

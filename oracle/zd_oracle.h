@@ -58,6 +58,7 @@ typedef struct {
   uint32_t src_len;    /* block_src_len   */
   uint32_t n_syms;     /* block_syms_len incl. end-of-block */
   int64_t nlen, flen, dlen; /* the three cost estimates of write_block */
+  int64_t bit_start, bit_end; /* the writer's bit position (dst.len * 8 + dst_bits_len) before and after the block */
 } zd_block_info;
 
 const char *zd_strerror(int status);

@@ -244,14 +244,25 @@ static uint32_t parse_segments_model(const uint8_t *s, uint32_t len, const uint3
   return nblk;
 }
 
-// kinds[] receives the block kinds (0 stored, 1 fixed, 2 dynamic), up to max_kinds
+// kinds[] receives the block kinds (0 stored, 1 fixed, 2 dynamic), up to max_kinds.
+// dst_cap: the kernels' rule (include/zipc_hip.h at zipc_hip_deflate_batch), block by block: the bits in front of a block
+// plus its size -- a dynamic block's ESTIMATE dlen, a fixed or stored block's real size -- rounded up to bytes must not
+// exceed dst_cap.  A stream that does not fit returns 16 with *out_len = 0 and *adler_out = 0; the one-wave form has
+// then written the whole bytes of the blocks in front (deflate_emit_wave<0>), the by-blocks form nothing
+// (deflate_scan_kernel), `None nothing (deflate_stored_kernel).
 extern "C" int sim_deflate(const uint8_t *src, uint32_t len, int level, uint8_t *dst, uint64_t dst_cap,
                            uint64_t *out_len, uint32_t *adler_out, int *kinds, int max_kinds,
                            int *n_kinds) {
   BitWriter w;
   uint32_t adler = 1;
   int nk = 0;
+  *out_len = 0;
+  *adler_out = 0;
+  *n_kinds = 0;
+  auto fits = [&](uint64_t bits_before, uint64_t est) { return ((bits_before + est + 7) >> 3) <= dst_cap; };
   if (level == LEVEL_NONE) {  // write_all_non_compressed zd.ml:1106-1116
+    const uint64_t nblocks = (uint64_t)len / MAX_BLOCK_SRC_LEN + ((len % MAX_BLOCK_SRC_LEN) || len == 0 ? 1 : 0);
+    if ((uint64_t)len + 5 * nblocks > dst_cap) return 16;  // deflate_stored_kernel's test
     uint32_t start = 0;
     for (;;) {
       uint32_t n = len - start < (uint32_t)MAX_BLOCK_SRC_LEN ? len - start : (uint32_t)MAX_BLOCK_SRC_LEN;
@@ -433,7 +444,9 @@ extern "C" int sim_deflate(const uint8_t *src, uint32_t len, int level, uint8_t 
         P.kind = (nlen <= P.dlen && nlen <= P.flen) ? 0 : P.flen <= P.dlen ? 1 : 2;
         const uint64_t sbits = (uint64_t)(((pending + 3u + 7u) & ~7u) - pending) + (4 + (uint64_t)src_len) * 8;
         P.bit_start = bits;
-        bits += P.kind == 0 ? sbits : P.kind == 1 ? P.flen : P.dbits;
+        const uint64_t block_bits = P.kind == 0 ? sbits : P.kind == 1 ? P.flen : P.dbits;
+        if (!fits(bits, P.kind == 2 ? P.dlen : block_bits)) return 16;  // deflate_scan_kernel's test: nothing is written
+        bits += block_bits;
         P.bit_end = bits;
       }
     }
@@ -461,6 +474,14 @@ extern "C" int sim_deflate(const uint8_t *src, uint32_t len, int level, uint8_t 
       coder_make_dynamic(c);
       uint64_t flen, dlen;
       kind = coder_choose(c, bd.src_len, w.nbits, flen, dlen);
+      // deflate_emit_wave<0>'s test: the whole bytes of the blocks in front are written by now
+      const uint64_t before = (uint64_t)w.out.size() * 8 + (uint64_t)w.nbits;
+      const uint64_t sbits = (uint64_t)((((uint32_t)w.nbits + 3u + 7u) & ~7u) - (uint32_t)w.nbits) + (4 + (uint64_t)bd.src_len) * 8;
+      if (!fits(before, kind == 0 ? sbits : kind == 1 ? flen : dlen)) {
+        if (w.out.size() > dst_cap) return 94;  // (the blocks in front passed the test)
+        if (!w.out.empty()) memcpy(dst, w.out.data(), w.out.size());
+        return 16;
+      }
       }
       if (nk < max_kinds) kinds[nk] = kind;
       nk++;
@@ -491,7 +512,7 @@ extern "C" int sim_deflate(const uint8_t *src, uint32_t len, int level, uint8_t 
   *out_len = w.out.size();
   *adler_out = adler;
   *n_kinds = nk;
-  if (w.out.size() > dst_cap) return 16;
+  if (w.out.size() > dst_cap) return 94;  // the per-block test lets nothing through that does not fit
   memcpy(dst, w.out.data(), w.out.size());
   return 0;
 }

@@ -3,6 +3,7 @@ of each: inflate with CRC-32, Crc_32.check, deflate at a level.  Nothing here ru
 import functools
 import zlib
 
+import deflate_fit
 import util
 
 
@@ -60,26 +61,19 @@ def expectation(c, level):
     if c.expect is not None and crc != c.expect:
         return Expect(6, 2, crc, data)
     out = _deflate(data, level)
-    if len(out) > (bound(c.mid_cap) if c.dst_cap is None else c.dst_cap):
-        return Expect(16, 3, crc, data, would_be=out, may_write=blocks_in_front(data, level, out, c.dst_cap))
+    cap = bound(c.mid_cap) if c.dst_cap is None else c.dst_cap
+    if not deflate_fit.fits(data, level, cap):  # (not "len(out) > cap": tests/deflate_fit.py has the rule)
+        return Expect(16, 3, crc, data, would_be=out, may_write=blocks_in_front(data, level, out, cap))
     return Expect(0, 0, crc, data, out)
 
 
 def blocks_in_front(data, level, out, dst_cap):
-    """An upper bound of the bytes of `out` that lie in front of the first block that does not fit dst_cap.  One block:
-    none.  `None (stored blocks): none either, the whole length is known before a byte is stored.  The two-block case of
-    error_cases(): the last block codes data[65530:] or less -- at least 4466 bytes drawn evenly from four values, two
-    bits of entropy each, which no code brings under 4466 * 2 / 8 = 1116 bytes on average, and a Huffman code for them
-    spends those two bits a literal at the least -- so the first block ends at least 1116 bytes in front of out's end."""
-    import oracle
-
-    blocks = oracle.deflate_trace(data, level=level)[3]
-    if len(blocks) == 1 or level == 0:
-        return 0
-    assert len(blocks) == 2 and blocks[1].src_len >= 4466 and set(data) == {0, 1, 2, 3}
-    first = len(out) - 1116
-    assert first <= dst_cap < len(out)  # (the first block fits, the second does not)
-    return first
+    """The bytes of `out` that lie in front of the first block that does not fit dst_cap, in whole bytes: what deflate may
+    have left of the stream (deflate_fit.expect's whole_bytes_in_front).  One block: none.  `None (stored blocks): none
+    either, the whole length is known before a byte is stored."""
+    status, _, front = deflate_fit.expect(data, level, dst_cap)
+    assert status == 16 and front < len(out)
+    return front
 
 
 @functools.lru_cache(maxsize=None)
@@ -145,7 +139,7 @@ def error_cases():
         Case("dst_cap_too_small", s, len(data), len(data), crc, dst_cap=20),                     # (one block: less than any level makes of 6000 bytes of words)
         Case("stray_flag", s, len(data), len(data), crc, flags=4),
         two_block_stream_without_room(),
-    ]
+    ] + middle_block_binds()
 
 
 def two_block_stream_without_room():
@@ -157,8 +151,22 @@ def two_block_stream_without_room():
     return Case("dst_cap_holds_the_first_block_only", _deflate(data, 1), len(data), len(data), oracle.crc32(data), dst_cap=20900)
 
 
+def middle_block_binds():
+    """196 612 zero bytes with room for what they recode to at `Default (233 bytes) and with the least room the rule takes
+    (238): three dynamic blocks and a fixed one, and the third one's estimate decides -- refused at stage 3, then accepted
+    (at `Fast and `Best too; at `None both are far too small)"""
+    import oracle
+
+    data = deflate_fit.ZEROS196K
+    out, blocks = deflate_fit.trace(data, 2)
+    clen, least = len(out), deflate_fit.min_cap(blocks)
+    assert (clen, least) == (233, 238) and not deflate_fit.fits(data, 2, clen) and deflate_fit.fits(data, 2, least)
+    return [Case("zeros196k_room_%s" % what, _deflate(data, 2), len(data), len(data), oracle.crc32(data), dst_cap=cap)
+            for what, cap in (("for_the_output", clen), ("the_rule_takes", least))]
+
+
 def ragged_batch():
-    """the good streams with the six that stop scattered among them"""
+    """the good streams with the ones that stop (and the one that just fits) scattered among them"""
     cases = list(good_cases())
     for j, e in enumerate(error_cases()):
         cases.insert(3 + 6 * j, e)

@@ -573,7 +573,9 @@ def test_deflate_dst_too_small_is_reported(gpu_ctx):
 def test_deflate_dst_too_small_is_reported_for_a_long_stream(gpu_ctx, oracle):
     """the same through the forms a long stream takes (blocks coded by a wave each, deflate_scan_kernel decides):
     a capacity below the output fails the stream and leaves the bytes behind the capacity alone; the exact size fits
-    when the reference's own estimates let it (they run high: the code-length counts are never reset)"""
+    when the reference's own estimates let it (they run high: the code-length counts are never reset).  Where the edge
+    is: tests/deflate_fit.py states the rule, tests/test_gpu_deflate_fit.py holds every form to it on both sides of the
+    edge; the + 600 here is room to spare, not the edge"""
     import ctypes as C
 
     from zipc_amd import _lib

@@ -4,6 +4,7 @@ code under test."""
 import collections
 import functools
 
+import deflate_fit
 import util
 
 # limit: ?decompressed_size, or None; cap: the destination's room (>= limit); flags: descriptor bits beyond HAS_LIMIT
@@ -90,7 +91,8 @@ def decompress_expectations():
 
 
 COMPRESS_LENGTHS = (0, 1, 5, 65534, 65535, 70000, 200000)
-# name, data, cap: None = zlib_bound(len), "exact" / "exact-1" = the oracle's size (less one), or a number
+# name, data, cap: None = zlib_bound(len), "exact" / "exact-1" = the oracle's size (less one), "least" = six bytes more
+# than the least room deflate's rule takes (tests/deflate_fit.py), or a number
 CCase = collections.namedtuple("CCase", "name data cap")
 
 
@@ -103,6 +105,8 @@ def compress_cases():
     small = util.text(5000, 7)
     for cap in (0, 5, "exact", "exact-1"):
         cases.append(CCase("cap_%s" % cap, small, cap))
+    for cap in ("exact", "least"):  # four blocks, the third one's estimate decides: room for the output is refused
+        cases.append(CCase("zeros196k_cap_%s" % cap, deflate_fit.ZEROS196K, cap))
     return tuple(cases)
 
 
@@ -115,8 +119,9 @@ def compress_expectations(level):
     for c in compress_cases():
         st, z, adler = oracle.zlib_compress(c.data, level)
         assert st == 0
-        cap = {None: None, "exact": len(z), "exact-1": len(z) - 1}.get(c.cap, c.cap)
-        if cap is not None and cap < len(z):
+        cap = {None: None, "exact": len(z), "exact-1": len(z) - 1, "least": deflate_fit.least_room(c.data, level) + 6}.get(c.cap, c.cap)
+        # a stream fits iff there is room for the container and deflate's rule takes the rest (not "cap >= len(z)")
+        if cap is not None and (cap < 6 or not deflate_fit.fits(c.data, level, cap - 6)):
             out.append((c, cap, Expect(ST_DST_TOO_SMALL, b"", 0, cap < 6)))
         else:
             out.append((c, cap, Expect(0, z, adler, False)))
