@@ -166,6 +166,13 @@ int zipc_hip_adler32(zipc_hip_ctx *ctx, const void *src, size_t len, uint32_t *a
 int zipc_hip_inflate(zipc_hip_ctx *ctx, const void *src, size_t len, int has_limit,
                      size_t limit, int crc_op, void *dst, size_t dst_cap,
                      size_t *out_len, uint32_t *checksum);
+/* What one host stream inflates to, with nothing inflated: zipc_hip_inflate_size_batch (below) of a batch of one, around
+ * a copy of the stream to the device and 16 bytes back.  Returns the stream's status -- what zipc_hip_inflate
+ * (ZIPC_HIP_CRC_NOP) returns for the same src, len, has_limit and limit into a dst of ZIPC_HIP_MAX_STREAM_LEN bytes --
+ * and on ZIPC_HIP_OK its decompressed length in *out_len (0 otherwise): the dst_cap that call needs.  The stream is
+ * walked by ONE wave whatever its length (see zipc_hip_inflate_size_batch). */
+int zipc_hip_inflate_size(zipc_hip_ctx *ctx, const void *src, size_t len, int has_limit,
+                          size_t limit, size_t *out_len);
 
 /* zlib_decompress (zipc_deflate.mli:104-118; zipc_deflate.ml:720-740).  On
  * ZIPC_HIP_ERR_CHECKSUM, *expect and *found hold the two Adler-32 values. */
@@ -351,6 +358,42 @@ int zipc_hip_zlib_decompress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, v
 int zipc_hip_zlib_compress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
                                  const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
                                  size_t n_streams, size_t max_src_len, size_t total_src_len, int level);
+
+/* Sizing: what every stream of a batch inflates to, and whether it does, before there is a destination -- a raw deflate
+ * stream carries no decompressed size and a zlib stream only an Adler-32, and every decode form above needs a dst_cap.
+ * Same descriptors and results as zipc_hip_inflate_batch, all pointers DEVICE pointers; ONE kernel launch, a wave per
+ * stream, enqueued on the context's stream and never synchronised (no path of it reads anything back).
+ * The defining property: for every stream, status and out_len are what zipc_hip_inflate_batch (ZIPC_HIP_CRC_NOP) reports
+ * for the same src_off, src_len, limit and flags with dst_cap = ZIPC_HIP_MAX_STREAM_LEN; checksum is 0.  No byte of any
+ * arena is written -- there is no destination arena; the source is only read -- and dst_off and dst_cap of the
+ * descriptors are not looked at (a dst_cap above ZIPC_HIP_MAX_STREAM_LEN is no error here).  Hence:
+ *   - ZIPC_HIP_ERR_DST_TOO_SMALL appears only for a stream that inflates beyond ZIPC_HIP_MAX_STREAM_LEN.  (That path is
+ *     not tested: a wave would have to walk 4 GiB of output.)
+ *   - with ZIPC_HIP_STREAM_HAS_LIMIT, a stream that inflates beyond its limit is ZIPC_HIP_ERR_SIZE_EXCEEDED, out_len 0;
+ *     one that ends below it is ZIPC_HIP_OK with its true length, as with the reference's ?decompressed_size.
+ *   - every message of inflate is made with inflate's checks in inflate's order (a distance beyond the output so far
+ *     is checked against the true output position): an empty source is ZIPC_HIP_ERR_CORRUPTED, as the reference says.
+ *   - a flag bit other than ZIPC_HIP_STREAM_HAS_LIMIT, or src_len above ZIPC_HIP_MAX_STREAM_LEN, is
+ *     ZIPC_HIP_ERR_INVALID_ARG in that stream's own result.
+ *   - null ctx, d_descs or d_results, or n_streams above 0x7FFFFFFF, fails the call with ZIPC_HIP_ERR_INVALID_ARG;
+ *     n_streams == 0 is ZIPC_HIP_OK and nothing is enqueued.
+ *   - a stream is always sized by its one wave: there is no form by blocks, so a long stream costs what one wave takes
+ *     to walk it -- 4.5 to 7 ms a MiB of text, where zipc_hip_inflate of a long stream alone goes by blocks and takes a
+ *     fraction of that -- while a batch of many streams is sized in less time than it is decoded.
+ * The use: size the batch, read the results, lay the destinations out with dst_cap = out_len, call
+ * zipc_hip_inflate_batch (INTEGRATION.md has the recipe). */
+int zipc_hip_inflate_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
+                                const zipc_hip_stream_desc *d_descs,
+                                zipc_hip_stream_result *d_results, size_t n_streams);
+/* The same for WHOLE zlib streams (stream i of the source arena as in zipc_hip_zlib_decompress_batch): the container's
+ * checks before (csrc/zlib.hip, unchanged), the size kernel over the bodies [2, len-2), and a close, a lane per stream:
+ * a stream that fails its header check (or has a flag bit other than ZIPC_HIP_STREAM_HAS_LIMIT) reports that status with
+ * out_len 0, every other stream what the size kernel says of its body.  checksum is 0.  The Adler-32 is NOT compared --
+ * there are no bytes to take it of -- so a stream that is sized ZIPC_HIP_OK can still be ZIPC_HIP_ERR_CHECKSUM when it is
+ * decompressed.  Enqueued on the context's stream, never synchronised; the same argument rules as above. */
+int zipc_hip_zlib_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
+                             const zipc_hip_stream_desc *d_descs,
+                             zipc_hip_stream_result *d_results, size_t n_streams);
 
 /* Recode on the device: every stream of the source arena -- a raw deflate stream, a ZIP member's bytes -- is inflated
  * into its room in a MIDDLE arena, its CRC-32 taken there and compared where the descriptor expects one, and what it

@@ -84,6 +84,7 @@ SYMBOLS = [
     ("zipc_hip_crc32", C.c_int, [_P, _P, _SZ, _U32P]),
     ("zipc_hip_adler32", C.c_int, [_P, _P, _SZ, _U32P]),
     ("zipc_hip_inflate", C.c_int, [_P, _P, _SZ, C.c_int, _SZ, C.c_int, _P, _SZ, _SZP, _U32P]),
+    ("zipc_hip_inflate_size", C.c_int, [_P, _P, _SZ, C.c_int, _SZ, _SZP]),
     ("zipc_hip_zlib_decompress", C.c_int,
      [_P, _P, _SZ, C.c_int, _SZ, _P, _SZ, _SZP, _U32P, _U32P, _U32P]),
     ("zipc_hip_deflate_bound", _SZ, [_SZ]),
@@ -99,6 +100,8 @@ SYMBOLS = [
     ("zipc_hip_deflate_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int, C.c_int]),
     ("zipc_hip_zlib_decompress_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ]),
     ("zipc_hip_zlib_compress_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int]),
+    ("zipc_hip_inflate_size_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
+    ("zipc_hip_zlib_size_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_recode_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int]),
     ("zipc_hip_recode_many", C.c_int, [_P, _SZ, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("zipc_hip_checksum_device", C.c_int, [_P, _P, _SZ, C.c_int, C.c_int, _P]),

@@ -114,6 +114,29 @@ def zlib_compress_batch(ctx: Context, src, dst, descs_dev, results_dev, n_stream
         ctx.synchronize()
 
 
+def inflate_size_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int, sync: bool = True):
+    """zipc_hip_inflate_size_batch: what every raw deflate stream of `src` inflates to -- status and out_len as
+    inflate_batch reports them into a destination of the largest size, checksum 0 -- with nothing written: there is no
+    destination arena, and dst_off / dst_cap of the descriptors are not looked at."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_inflate_size_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def zlib_size_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int, sync: bool = True):
+    """zipc_hip_zlib_size_batch: the same for whole zlib streams -- the header's verdict, or the size of the body.  The
+    Adler-32 is not compared: a stream sized OK can still fail its checksum when it is decompressed."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_zlib_size_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
 def recode_results_from_device(t) -> np.ndarray:
     return t.cpu().numpy().view(RECODE_RESULT_DTYPE).copy()
 
@@ -199,6 +222,6 @@ def compact_descs(results: np.ndarray, descs: np.ndarray, dst_cap_of_out, limit_
 
 __all__ = ["DESC_DTYPE", "RESULT_DTYPE", "RECODE_DESC_DTYPE", "RECODE_RESULT_DTYPE", "make_descs", "make_recode_descs", "to_device",
            "results_from_device", "recode_results_from_device", "recode_batch",
-           "inflate_batch", "deflate_batch", "zlib_decompress_batch", "zlib_compress_batch", "checksum_device", "reserve",
+           "inflate_batch", "deflate_batch", "inflate_size_batch", "zlib_size_batch", "zlib_decompress_batch", "zlib_compress_batch", "checksum_device", "reserve",
            "deflate_bound", "zlib_bound",
            "uniform_layout", "compact_descs", "OK"]

@@ -456,6 +456,12 @@ int zipc_hip_inflate_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_d
   return launch_inflate(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, max_dst_cap, crc_op, nullptr, true);
 }
 
+int zipc_hip_inflate_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                zipc_hip_stream_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  return launch_inflate_size(ctx, d_src_arena, d_descs, d_results, n_streams);
+}
+
 int zipc_hip_deflate_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
                            const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
                            size_t n_streams, size_t max_src_len, size_t total_src_len, int level,
@@ -653,6 +659,30 @@ static int one_stream(zipc_hip_ctx *ctx, bool is_inflate, const void *src, size_
 int zipc_hip_inflate(zipc_hip_ctx *ctx, const void *src, size_t len, int has_limit, size_t limit,
                      int crc_op, void *dst, size_t dst_cap, size_t *out_len, uint32_t *checksum) {
   return one_stream(ctx, true, src, len, has_limit, limit, 0, crc_op, dst, dst_cap, out_len, checksum);
+}
+
+// what one host stream inflates to: a batch of one around a copy in and the result's 16 bytes back
+int zipc_hip_inflate_size(zipc_hip_ctx *ctx, const void *src, size_t len, int has_limit, size_t limit, size_t *out_len) {
+  if (!ctx || (!src && len) || !out_len) return ZIPC_HIP_ERR_INVALID_ARG;
+  *out_len = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int st = stage_in(ctx, src, len);
+  if (st) return st;
+  HIP_TRY(ctx, ctx->ensure(ctx->io_desc, sizeof(StreamDesc)));
+  HIP_TRY(ctx, ctx->ensure(ctx->io_res, sizeof(StreamResult)));
+  StreamDesc d;
+  memset(&d, 0, sizeof d);
+  d.src_len = len;
+  d.limit = limit; d.flags = has_limit ? STREAM_HAS_LIMIT : 0;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->io_desc.p, &d, sizeof d, hipMemcpyHostToDevice, ctx->stream));
+  st = zipc_hip_inflate_size_batch(ctx, ctx->io_src.p, (const zipc_hip_stream_desc *)ctx->io_desc.p, (zipc_hip_stream_result *)ctx->io_res.p, 1);
+  if (st) return st;
+  StreamResult r;
+  HIP_TRY(ctx, hipMemcpyAsync(&r, ctx->io_res.p, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (r.status != ST_OK) return (int)r.status;
+  *out_len = r.out_len;
+  return ZIPC_HIP_OK;
 }
 
 int zipc_hip_deflate(zipc_hip_ctx *ctx, const void *src, size_t len, int level, int crc_op, void *dst,
@@ -1185,6 +1215,21 @@ int zipc_hip_zlib_decompress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, v
                               max_dst_cap, zlib_crc_op(ctx));
   if (st) return st;
   return zlib_close(ctx, d_dst_arena, d_descs, d_results, n_streams, 0, 0);
+}
+
+// the sizes of a batch of zlib streams: the container's checks, the size kernel over the bodies, the checks' verdicts over its results
+int zipc_hip_zlib_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                             zipc_hip_stream_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = zlib_open(ctx, d_src_arena, d_descs, n_streams, 0);
+  if (st) return st;
+  st = zipc_hip_inflate_size_batch(ctx, d_src_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, d_results, n_streams);
+  if (st) return st;
+  ZD_LAUNCH(ctx, "zlib_close_size", zlib_close_size_kernel, dim3((unsigned)((n_streams + 255) / 256)), dim3(256), 0,
+            (const ZlibPre *)ctx->zlib_pre.p, (StreamResult *)d_results, (uint32_t)n_streams);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
 }
 
 int zipc_hip_zlib_compress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,

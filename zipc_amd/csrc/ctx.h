@@ -130,4 +130,8 @@ hipError_t launch_deflate(zipc_hip_ctx *ctx, const uint8_t *d_src, uint8_t *d_ds
 int launch_inflate(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
                    zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op, const StreamDesc *h_descs,
                    bool first_of_call);
+// inflate.hip: zipc_hip_inflate_size_batch behind its argument checks (a ZIPC_HIP_* status): inflate_size_kernel, a wave per
+// stream, one launch on ctx->cur
+int launch_inflate_size(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                        size_t n_streams);
 }  // namespace zd

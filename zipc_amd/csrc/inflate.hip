@@ -42,7 +42,8 @@
 // ONE long stream handed over alone gets a wave per BLOCK instead (further down: "ONE stream by a wave per BLOCK"):
 // the same wave code in two more modes -- IM_DRY walks a block for its end and size, IM_TOKEN stores its literals
 // and writes down what its matches copy -- around a search for block headers, a chain of the blocks and pointer
-// jumping over the copies.
+// jumping over the copies.  A fourth mode, IM_SIZE, is the stream's wave with nothing stored: what a stream inflates to,
+// and whether it does, before there is a destination (inflate_size_kernel, zipc_hip_inflate_size_batch).
 // The launch code is the last section (zd::launch_inflate); its rules between two launches: forms.h, inflate_blocks.h.
 #include <deque>
 
@@ -476,7 +477,7 @@ __device__ __forceinline__ uint32_t wide_turn(InflateLane &d, const LaneLds &L, 
   const uint32_t h0 = d.hole_min;
   const uint32_t h1 = h0 < first_match_dst ? h0 : first_match_dst;  // also what queued destinations are relative to
   const uint32_t hole = mrank == 0 ? h0 : h1;  // the turn's first match only sees the queued copies
-  // (IM_DRY / IM_TOKEN copy nothing: no queue, no holes)
+  // (IM_DRY / IM_TOKEN / IM_SIZE copy nothing: no queue, no holes)
   const uint32_t bad_match = MODE != IM_REAL ? over(sp.dist, dstp)
                                              : over(sp.dist, dstp) | over(mrank + 1u, qfree) | over(dstp - h1, QUEUE_REL_MAX) |
                                                    over(src_end, hole);
@@ -488,7 +489,7 @@ __device__ __forceinline__ uint32_t wide_turn(InflateLane &d, const LaneLds &L, 
   const uint32_t c = (uint32_t)__builtin_ctzll(cut_m);  // a lane on the path, or the sink
   const mask_t commit_m = commit0_m & ((1ull << c) - 1ull);
   const mask_t commit_match_m = commit_m & match_m;
-  if (MODE != IM_DRY && lane_in(commit_m & lit_m)) dst[dstp] = (uint8_t)sp.lit;
+  if (im_stores(MODE) && lane_in(commit_m & lit_m)) dst[dstp] = (uint8_t)sp.lit;
   // every lane writes a queue word: the ones without a committed match into the spare slot
   if (MODE == IM_REAL)
     L.queue(lane_in(commit_match_m) ? (int)(d.q_count + mrank) : QUEUE_ENTRIES) = queue_pack(dstp - h1, sp.dist, sp.length);
@@ -559,7 +560,7 @@ __device__ __forceinline__ uint32_t strided_turn(InflateLane &d, const LaneLds &
   uint32_t c = ~m == 0ull ? 64u : (uint32_t)__builtin_ctzll(~m);
   const uint32_t room = d.cap_min - d.out_pos;
   c = c < room ? c : room;
-  if (MODE != IM_DRY && (uint32_t)lane < c) dst[d.out_pos + (uint32_t)lane] = (uint8_t)(e >> 8);
+  if (im_stores(MODE) && (uint32_t)lane < c) dst[d.out_pos + (uint32_t)lane] = (uint8_t)(e >> 8);
   d.out_pos += c;
   d.advance(c * n);
   return c;
@@ -601,7 +602,8 @@ __device__ __forceinline__ void wave_match(uint8_t *dst, uint32_t *__restrict__ 
 // makes the reference's check of a distance against it (zd.ml:614).
 constexpr uint32_t BLOCK_DRY_BASE = 32768;
 
-// The stream's wave: MODE IM_REAL is the whole stream (inflate_batch_kernel); the other two stop at the end of the
+// The stream's wave: MODE IM_REAL is the whole stream (inflate_batch_kernel), and so is IM_SIZE, which stores nothing
+// (inflate_size_kernel: dst_arena is null, the result is the status and the size); the other two stop at the end of the
 // block they were started on.
 // (returns, in every lane, what the block modes found of their block)
 // MULTI (with IM_DRY): an explorer (inflate_explore_kernel) -- the wave goes on from block to block and lists every
@@ -643,7 +645,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
   const int lane = threadIdx.x;
   const bool crc_adler = MODE == IM_REAL && (crc_op == CRC_ADLER32 || crc_op == CRC_ADLER32_RFC);
   const bool adler_rfc = crc_op == CRC_ADLER32_RFC;
-  const bool writer = lane == 0 && MODE != IM_DRY;  // (the lane that stores a literal decoded alone)
+  const bool writer = lane == 0 && im_stores(MODE);  // (the lane that stores a literal decoded alone)
 
   LaneLds L;
   L.at(lds_raw);  // (the input ring first: its reads encode their offsets)
@@ -652,8 +654,9 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
   A.src = src_arena;
   A.dst = dst_arena;
   InflateLane d;
-  lane_init(d, sd);
-  if (MODE != IM_REAL && d.status == ST_OK) {
+  if (MODE == IM_SIZE) lane_init_size(d, sd);  // (no destination: dst_off and dst_cap are not looked at)
+  else lane_init(d, sd);
+  if (MODE != IM_REAL && MODE != IM_SIZE && d.status == ST_OK) {
     d.in_word = (uint32_t)(at.bit >> 5);
     d.boff = (uint32_t)at.bit & 31u;
     d.ring_wr = d.in_word;
@@ -684,7 +687,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
   uint32_t prev_hdr_bits = 0;
   // a block has ended (the phase says what the stream's wave would do next): the block modes stop here, or go on
   auto block_done = [&]() {
-    if (MODE == IM_REAL || d.status != ST_OK) return;
+    if (MODE == IM_REAL || MODE == IM_SIZE || d.status != ST_OK) return;
     if (!MULTI) { d.phase = PH_DONE; return; }
     const uint64_t end_bit = (uint64_t)d.in_word * 32u + d.boff;
     if (blk_hdr_bit != NO_BIT) {
@@ -710,7 +713,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
     d.out_pos = BLOCK_DRY_BASE;
     d.blk_out_start = BLOCK_DRY_BASE;
   };
-  uint8_t *dst = dst_arena + d.dst_off;
+  uint8_t *dst = MODE == IM_SIZE ? nullptr : dst_arena + d.dst_off;  // (IM_SIZE: there is no arena to form an address from)
   const uint8_t *src = src_arena + d.src_off;
 
 #ifdef ZD_INFLATE_PHASES  // timing-only build: the results carry cycle counts (tools/exp_inflate_phases.py)
@@ -909,7 +912,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
     }
 
     // ---- services
-    if (d.q_count) {  // fill the queued copies: entry `lane`, all loads before the stores
+    if (MODE != IM_SIZE && d.q_count) {  // fill the queued copies: entry `lane`, all loads before the stores (IM_SIZE: never any, and no `dst`)
       DeferredCopy c0;
       c0.len = 0;
       if ((uint32_t)lane < d.q_count) deferred_load(c0, dst, d.hole_min, L.queue(lane));
@@ -921,11 +924,11 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
       wave_match<MODE>(dst, tok, d.out_pos, d.req_dist, d.req_len, lane, L.x + LDS_SPAN_TILE_BYTE);
       lane_after_match(d);
     } else if (d.phase == PH_REQ_COPY) {
-      if (MODE != IM_DRY) wave_copy(dst + d.out_pos, src + d.req_src, d.req_len, lane);
+      if (im_stores(MODE)) wave_copy(dst + d.out_pos, src + d.req_src, d.req_len, lane);
       lane_after_copy(d, crc_adler);
       block_done();
     }
-    if (d.phase == PH_REQ_ADLER) {
+    if (MODE != IM_SIZE && d.phase == PH_REQ_ADLER) {
       // the block's bytes were stored by other lanes of this wave: make them visible
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
       d.adler = wave_adler_update(d.adler, dst + d.blk_out_start, d.out_pos - d.blk_out_start, lane, adler_rfc);
@@ -945,8 +948,8 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
   e.end_bit = (uint64_t)d.in_word * 32u + d.boff;
   e.out_len = d.out_pos - (MODE == IM_DRY ? BLOCK_DRY_BASE : at.out_pos);
   e.pad = MODE == IM_DRY ? ck.n : left_early ? 1u : 0u;
-  if (MODE != IM_REAL) return e;
-  if (writer) {
+  if (MODE != IM_REAL && MODE != IM_SIZE) return e;
+  if (writer || (MODE == IM_SIZE && lane == 0)) {
     StreamResult r;
     r.status = d.status;
     r.out_len = d.status == ST_OK ? d.out_pos : 0;
@@ -957,7 +960,8 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
     r.status = (uint32_t)((__builtin_readcyclecounter() - ph_begin) >> 6);
     r.checksum = (uint32_t)(ph_hdr >> 6);
     r.out_len = (ph_wide >> 6) | ((ph_plain >> 6) << 32);
-    for (int i = 0; i < 8; i++) ((uint64_t *)dst)[i] = span_ph[i];  // over the stream's first output bytes (dst slots are 256-byte aligned)
+    if (MODE == IM_REAL)
+      for (int i = 0; i < 8; i++) ((uint64_t *)dst)[i] = span_ph[i];  // over the stream's first output bytes (dst slots are 256-byte aligned)
 #endif
     *result = r;
   }
@@ -1012,6 +1016,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   at.bit = 0; at.out_pos = 0; at.chunk0 = 0;
   inflate_wave<IM_REAL, false, true>(lds_raw, src_arena, dst_arena, descs[stream], at, results + stream,
                                      span_scratch + (size_t)stream * SPAN_IDX_ENTRIES, nullptr, crc_op);
+}
+// Sizing: the stream's wave over the whole stream with every check and no store (IM_SIZE) -- results[stream] = the status
+// inflate_batch_kernel would report into a destination of MAX_STREAM_LEN bytes, and the size on ST_OK; checksum 0.  No
+// arena but the source is touched (the descriptors' dst_off / dst_cap are not read): the only global stores are the span
+// decoder's index in the stream's slot of scratch and the result.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void inflate_size_kernel(const uint8_t *__restrict__ src_arena, const StreamDesc *__restrict__ descs,
+                                                          StreamResult *__restrict__ results, uint32_t n_streams,
+                                                          uint16_t *__restrict__ span_scratch) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LDS_BYTES_PER_LANE];
+  const uint32_t stream = blockIdx.x;
+  if (stream >= n_streams) return;
+  int crc_op = CRC_NOP;
+  if (inflate_skips_stream(descs[stream].flags, crc_op, results + stream)) return;
+  BlockStart at;
+  at.bit = 0; at.out_pos = 0; at.chunk0 = 0;
+  inflate_wave<IM_SIZE>(lds_raw, src_arena, nullptr, descs[stream], at, results + stream,
+                        span_scratch + (size_t)stream * SPAN_IDX_ENTRIES, nullptr, CRC_NOP);
 }
 
 
@@ -2063,6 +2084,18 @@ static int inflate_batch_one_wave(zipc_hip_ctx *ctx, const void *d_src_arena, vo
     if (st == ZIPC_HIP_OK) HIP_TRY(ctx, e);
   }
   return st;
+}
+
+// zipc_hip_inflate_size_batch behind its argument checks (ctx.h): one launch, a wave per stream, on the context's stream
+int launch_inflate_size(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                        size_t n_streams) {
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_streams * INFLATE_SCRATCH_PER_STREAM));
+  ZD_LAUNCH(ctx, "inflate_size", inflate_size_kernel, dim3((unsigned)n_streams), dim3(64), 0, (const uint8_t *)d_src_arena,
+            (const StreamDesc *)d_descs, (StreamResult *)d_results, (uint32_t)n_streams, (uint16_t *)ctx->inflate_scratch.p);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
 }
 
 // zipc_hip_inflate_batch behind its argument checks (ctx.h)

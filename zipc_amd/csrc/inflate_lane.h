@@ -577,8 +577,13 @@ ZD_HD bool lane_block_header(InflateLane &d, const LaneLds &L, const uint8_t *__
 enum : int { SYM_OK = 0, SYM_EOB = 1, SYM_STOP = 2 };
 // What a wave does with the bytes (inflate.hip): IM_REAL the stream's output; IM_DRY nothing -- one block's symbols
 // are walked for its end and its size; IM_TOKEN literals are stored and a match leaves, per byte, the position it
-// copies (one stream's blocks side by side: the copies are resolved once all of them are known).
-enum : int { IM_REAL = 0, IM_DRY = 1, IM_TOKEN = 2 };
+// copies (one stream's blocks side by side: the copies are resolved once all of them are known); IM_SIZE nothing
+// either, but of the WHOLE stream: from bit 0 and output position 0, block after block like IM_REAL, with IM_REAL's
+// limit and every one of its checks at the true output position -- the stream's status and size, no byte of it
+// (inflate_size_kernel; there is no destination: lane_init_size).
+enum : int { IM_REAL = 0, IM_DRY = 1, IM_TOKEN = 2, IM_SIZE = 3 };
+// the modes that store the bytes they decode (the other two only count them)
+ZD_HD constexpr bool im_stores(int mode) { return mode == IM_REAL || mode == IM_TOKEN; }
 
 // A decoded match (its bits in c): the reference's checks, then Buf.recopy zd.ml:615 -- queued, or
 // handed to the wave
@@ -931,6 +936,14 @@ ZD_HD void lane_init(InflateLane &d, const StreamDesc &s) {
   bool has_limit = (s.flags & STREAM_HAS_LIMIT) != 0;
   d.limit = has_limit ? (s.limit > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)s.limit) : 0xFFFFFFFFu;
   d.cap_min = d.limit < d.hard_cap ? d.limit : d.hard_cap;
+}
+// IM_SIZE: the same without a destination -- dst_off and dst_cap are not looked at (whatever they hold is no error),
+// the room is the longest stream there is; src_len's rule and the limit are lane_init's
+ZD_HD void lane_init_size(InflateLane &d, const StreamDesc &s) {
+  StreamDesc t = s;
+  t.dst_off = 0;
+  t.dst_cap = MAX_STREAM_LEN;
+  lane_init(d, t);
 }
 
 }  // namespace zd

@@ -479,7 +479,8 @@ ZD_WV void span_fill_by_wave(uint8_t *tile, const uint8_t *gbase, uint32_t dp, u
 #define ZD_SPAN_PH(i) do {} while (0)
 #endif
 // MODE (inflate_lane.h IM_*): IM_DRY walks and checks the symbols and moves the position, touching neither `dst` nor a
-// tile; IM_TOKEN stores the literals and, for every byte of a match, the output position it is a copy of in tok[]
+// tile (IM_SIZE: the same, at the stream's true output position, `dst` null); IM_TOKEN stores the literals and, for
+// every byte of a match, the output position it is a copy of in tok[]
 // (inflate.hip: one stream by a wave per block; srcpos: SPAN_TILE u16 of LDS, the tile's sources while they are
 // sorted out).
 // bits_cap: a span walks no further than this many bits (a wave that takes a block over from a checkpoint on and only
@@ -775,7 +776,7 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
         err = bad ? 1u : err;
         const bool is_match = good && !s.is_lit;
         const bool fly = MODE == IM_REAL && is_match && s.outlen - 4u <= 4u && s.val >= o2;
-        if (MODE != IM_DRY && good && s.is_lit) {
+        if (im_stores(MODE) && good && s.is_lit) {
           tile[o] = (uint8_t)s.val;
           if (s.outlen == 2u) tile[o + 1u] = (uint8_t)s.val2;
         }
@@ -908,7 +909,7 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
     uint32_t my_open = mine ? nh : 0u;
     for (;;) {
       const uint32_t hincl = wv::scan_incl(my_open), h_total = wv::readlane(hincl, 63u);
-      if (h_total == 0u) break;
+      if (MODE == IM_SIZE || h_total == 0u) break;  // (IM_SIZE: no holes, and no `dst` to fill them from)
       uint32_t n_open = h_total < SPAN_LIST_MAX ? h_total : SPAN_LIST_MAX;
       {
         uint32_t cursor = mine ? o0 : 0u, at = hincl - my_open;
@@ -1103,7 +1104,7 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
     }
     ZD_SPAN_PH(5);
     // the tile leaves (IM_TOKEN: the bytes of its matches are whatever the tile held; tok[] says what they are)
-    for (uint32_t i = ulane * 16u; MODE != IM_DRY && i < tile_len; i += 1024u) {
+    for (uint32_t i = ulane * 16u; im_stores(MODE) && i < tile_len; i += 1024u) {
       if (i + 16u <= tile_len) {
         const uint32_t *t = (const uint32_t *)(tile + i);
         wv::Quad q;

@@ -14,6 +14,7 @@ __global__ void zlib_open_kernel(const uint8_t *__restrict__ src_arena, const St
 __global__ void zlib_close_kernel(uint8_t *__restrict__ dst_arena, const StreamDesc *__restrict__ descs,
                                   const ZlibPre *__restrict__ pre, StreamResult *__restrict__ results, uint32_t n_streams,
                                   int compress, int level);
+__global__ void zlib_close_size_kernel(const ZlibPre *__restrict__ pre, StreamResult *__restrict__ results, uint32_t n_streams);
 
 // ---- recode.hip: before, between and behind inflate and deflate of a batch, a lane per stream (rules: recode_rules.h)
 __global__ void recode_open_kernel(const RecodeDesc *__restrict__ descs, uint32_t n_streams, uint64_t max_mid_cap,

@@ -6,6 +6,7 @@
 //                      stream, or the room behind the header -- into the context's scratch, with the check's verdict;
 //   zlib_close_kernel  puts that verdict and the codec's result together: the Adler-32 compared with the stream's own,
 //                      or the header and the trailer stored around what deflate wrote.
+//   zlib_close_size_kernel  the same behind inflate's size kernel (zipc_hip_zlib_size_batch): the verdict, or the body's size.
 // The rules themselves are zlib_container.h's (the host forms and the tests compile the same functions).  Nothing is
 // read back: the calls enqueue and return like the raw batch forms.
 #include "kernels.h"
@@ -81,6 +82,14 @@ __global__ __launch_bounds__(256) void zlib_close_kernel(uint8_t *__restrict__ d
     zlib_put_trailer(o + 2 + inner.out_len, inner.checksum);
   }
   results[i] = r;
+}
+
+// zipc_hip_zlib_size_batch's close: the container check's verdict over the size kernel's (zlib_close_size)
+__global__ __launch_bounds__(256) void zlib_close_size_kernel(const ZlibPre *__restrict__ pre, StreamResult *__restrict__ results,
+                                                              uint32_t n_streams) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_streams) return;
+  results[i] = zlib_close_size(pre[i].status, results[i]);
 }
 
 }  // namespace zd

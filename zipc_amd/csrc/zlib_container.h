@@ -66,6 +66,14 @@ ZD_HD StreamResult zlib_close_decompress(uint32_t pre, uint32_t expect, StreamRe
   else if (inner.status == ST_OK && inner.checksum != expect) { inner.status = ST_CHECKSUM; inner.out_len = 0; }
   return inner;
 }
+// Sizing a zlib stream (zipc_hip_zlib_size_batch): `inner` is the size kernel's verdict of the body.  A stream that failed
+// its own check says so; every other one is the body's -- its status, and on ST_OK what it inflates to.  The Adler-32 is
+// NOT compared (there are no bytes to take it of): a stream sized ST_OK can still be ST_CHECKSUM when it is decompressed.
+ZD_HD StreamResult zlib_close_size(uint32_t pre, StreamResult inner) {
+  if (pre != ST_OK) { inner.status = pre; inner.out_len = 0; }
+  inner.checksum = 0;
+  return inner;
+}
 // zlib_compress: `inner` is deflate's, the result counts the container's bytes too.  *wrap: the caller has to put the
 // header and the trailer (inner.checksum, behind inner.out_len bytes of payload) around what deflate wrote.
 ZD_HD StreamResult zlib_close_compress(uint32_t pre, StreamResult inner, bool *wrap) {

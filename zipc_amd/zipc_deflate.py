@@ -152,6 +152,22 @@ def inflate(s, decompressed_size=None, start=0, len=None, ctx=None):
     return Ok(r.value[0]) if r.is_ok() else r
 
 
+def inflate_size(s, decompressed_size=None, start=0, len=None, ctx=None):
+    """What `inflate` of the same arguments would hand back, without the bytes: Ok (decompressed length) | Error msg.  The
+    stream is walked on the device with every check of inflate and nothing is stored (zipc_hip_inflate_size); the
+    reference has no such value -- it is what its `inflate` without ?decompressed_size finds out by growing a buffer."""
+    data = _range(s, start, len)
+    ctx = ctx or default_context()
+    has_limit = decompressed_size is not None
+    out_len = C.c_size_t()
+    st = lib().zipc_hip_inflate_size(ctx.handle, data, data.__len__(), int(has_limit), decompressed_size or 0, C.byref(out_len))
+    if st == OK:
+        return Ok(out_len.value)
+    if st in (_lib.ERR_HIP, _lib.ERR_INVALID_ARG, _lib.ERR_NO_DEVICE, _lib.ERR_NOMEM):
+        ctx.check(st)
+    return Error(_message(st))
+
+
 def inflate_and_crc_32(s, decompressed_size=None, start=0, len=None, ctx=None):
     """zipc_deflate.mli:93-97"""
     return _inflate(s, decompressed_size, start, len, CRC_CRC32, ctx)
