@@ -5,7 +5,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libhost_sim.so")
-SRCS = ["sim_inflate.cpp", "sim_deflate.cpp", "sim_chain.cpp", "sim_forms.cpp"]
+SRCS = ["sim_inflate.cpp", "sim_deflate.cpp", "sim_chain.cpp", "sim_forms.cpp", "sim_adler.cpp"]
 
 
 def lib():
@@ -68,6 +68,21 @@ def _bind(L):
     L.sim_resolve_grid.argtypes = [C.c_int, C.c_uint32]
     L.sim_blocks_shares.restype = None
     L.sim_blocks_shares.argtypes = [u32p, u32p, C.c_uint64, u64p, u64p, u64p]
+    return bind_adler(L)
+
+
+def bind_adler(L):
+    """sim_adler.cpp's entry points (a library of that file alone has no others: the mutants of tests/test_adler_chain_sim.py)"""
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    L.sim_adler_shape.restype = None
+    L.sim_adler_shape.argtypes = [C.c_uint64, u64p]
+    L.sim_adler_chain.restype = C.c_int
+    L.sim_adler_chain.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u64p]
+    for f in (L.sim_adler_serial, L.sim_adler_rfc):
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, u32p]
+    L.sim_crc_finish_grid.restype = C.c_uint64
+    L.sim_crc_finish_grid.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p]
     return L
 
 
@@ -180,3 +195,60 @@ def blocks_shares(L, waves, chunks):
     span_at, sums_at, total = (C.c_uint64 * n)(), (C.c_uint64 * n)(), (C.c_uint64 * 2)()
     L.sim_blocks_shares((C.c_uint32 * n)(*waves), (C.c_uint32 * n)(*chunks), n, span_at, sums_at, total)
     return list(span_at), total[0], list(sums_at), total[1]
+
+
+# ---- zipc_amd/csrc/adler_chain.h through sim_adler.cpp: the Adler-32 chunk chain over chunk sums, the CRC-32 finish's grid
+ADLER_REPLAY, ADLER_WALK = 0, 1
+
+
+def adler_shape(L, length):
+    """(n_chunks, n_runs, per) that zipc_hip_checksum_device takes for a buffer of that length"""
+    out = (C.c_uint64 * 3)()
+    L.sim_adler_shape(length, out)
+    return tuple(out)
+
+
+def _sums(S1, S2):
+    import numpy as np
+
+    a, b = np.ascontiguousarray(S1, dtype=np.uint32), np.ascontiguousarray(S2, dtype=np.uint32)
+    assert a.shape == b.shape and a.ndim == 1
+    return a, b
+
+
+def adler_chain(L, S1, S2, length, n_runs=0, replay_max=0, amb_cap=0, seed=0):
+    """the five launches over the chunk sums of a buffer of `length` bytes (chunk 0 is its first length % 5552 bytes)
+    -> (value, dict(path, n_amb, n_runs, per)); n_runs, replay_max, amb_cap: 0 for the product's"""
+    a, b = _sums(S1, S2)
+    v, info = C.c_uint32(), (C.c_uint64 * 4)()
+    st = L.sim_adler_chain(a.ctypes.data, b.ctypes.data, len(a), length, n_runs, replay_max, amb_cap, seed, C.byref(v), info)
+    assert st == 0, "the sums are not those of %d bytes" % length
+    return v.value, dict(zip(("path", "n_amb", "n_runs", "per"), info))
+
+
+def adler_serial(L, S1, S2, length):
+    a, b = _sums(S1, S2)
+    v = C.c_uint32()
+    assert L.sim_adler_serial(a.ctypes.data, b.ctypes.data, len(a), length, C.byref(v)) == 0
+    return v.value
+
+
+def adler_rfc(L, S1, S2, length):
+    a, b = _sums(S1, S2)
+    v = C.c_uint32()
+    assert L.sim_adler_rfc(a.ctypes.data, b.ctypes.data, len(a), length, C.byref(v)) == 0
+    return v.value
+
+
+def crc_finish_grid(L, nseg, segs=None, threads=0):
+    """crc32_finish_kernel's reads of nseg partials -> (used, loaded, dict(threads, rows, padp, one_thread)): the partial
+    at every place of the fold in order (-1: a virtual zero), and every index a thread fetches"""
+    import numpy as np
+
+    segs = nseg if segs is None else segs
+    cap = (nseg // 256 + 16) * 1024 + 16
+    used, loaded = np.empty(cap, np.int64), np.empty(cap, np.uint64)
+    nl, info = C.c_uint64(), (C.c_uint64 * 4)()
+    nu = L.sim_crc_finish_grid(nseg, segs, threads, used.ctypes.data, cap, loaded.ctypes.data, cap, C.byref(nl), info)
+    assert nu <= cap and nl.value <= cap
+    return used[:nu], loaded[:nl.value], dict(zip(("threads", "rows", "padp", "one_thread"), info))

@@ -23,6 +23,8 @@ stricter refusal must change NO result: those are listed as expected to survive,
 override) passing under them is what shows the hand-off right.  The relaxed mutants (LANE_INFLATE_RELAXED) run only in
 the host models, in child processes: tests/test_host_sim.py::test_inflate_lane_mutants_are_killed.
 
+The mutants of the Adler-32 chunk chain (ADLER_MUTANTS, zipc_amd/csrc/adler_chain.h) are killed on the CPU only:
+tests/test_adler_chain_sim.py::test_adler_chain_mutants_are_killed.
 The coder_choose mutants are killed on the CPU: tests/test_host_sim.py::test_coder_choose_mutants_are_killed.
 Each text must occur exactly once in its file, so a change of the kernels cannot quietly make a mutant a no-op.
 """
@@ -106,6 +108,44 @@ LANE_INFLATE_RELAXED = [
     ("lane_incomplete_ok", "inflate_lane.h",
      "if ((num_codes > 1 && available > 0) || (num_codes == 1 && L.u16(counts_off, 1) != 1))",
      "if (num_codes == 1 && L.u16(counts_off, 1) != 1)"),
+]
+# (name, file, text, replacement, killer): one-line mutants of the Adler-32 chunk chain's arithmetic, killed on the CPU only --
+# each built into a host model of its own (tests/host_sim/sim_adler.cpp) and run in a child process by
+# tests/test_adler_chain_sim.py::test_adler_chain_mutants_are_killed.  killer: the case of tests/checksum_cases.py
+# mutation_cases() whose result it must change, or ("equivalent", why): it must change none.
+# (The ambiguity bounds the other way -- `<=` for `<` -- only replay a chunk more: equivalent by construction, not listed.)
+ADLER_MUTANTS = [
+    ("amb_low_bound_less_1", "adler_chain.h", "return C < ADLER_BASE ||", "return C < ADLER_BASE - 1 ||",
+     ("equivalent", "|s2| <= 65520, so a chunk with C = 65520 never goes negative: the bound is one wider than it must be")),
+    ("amb_low_bound_less_2", "adler_chain.h", "return C < ADLER_BASE ||", "return C < ADLER_BASE - 2 ||", "low_bound_stays_negative_last"),
+    ("amb_mid_lower_bound_plus_1", "adler_chain.h", "(C > 0x80000000ull - ADLER_BASE &&", "(C > 0x80000000ull - ADLER_BASE + 1 &&",
+     "mid_lower_bound"),
+    ("amb_mid_upper_bound_less_1", "adler_chain.h", "C < 0x80000000ull + ADLER_BASE);", "C < 0x80000000ull + ADLER_BASE - 1);",
+     ("equivalent", "s2 >= -65520, so C = 2^31 + 65520 stays at or above 2^31: the bound is one wider than it must be")),
+    ("amb_mid_upper_bound_less_2", "adler_chain.h", "C < 0x80000000ull + ADLER_BASE);", "C < 0x80000000ull + ADLER_BASE - 2);",
+     "mid_upper_bound"),
+    ("a_term_without_225", "adler_chain.h", "hi_k ? ADLER_BASE - 225u : 0u", "hi_k ? 0u : 0u", "ff_chunks"),
+    ("hi_k_strict", "adler_chain.h", "return C >= 0x80000000ull;", "return C > 0x80000000ull;",
+     ("equivalent", "C = 2^31 is ambiguous: the chunk is replayed exactly, its a term is taken back out by the same function, "
+                    "and the branch of an ambiguous chunk is read by nobody (the next chunk takes exact_next or does not care)")),
+    ("zero_residue_negative", "adler_chain.h", "(rr == 0 ? 0 : (int32_t)rr - (int32_t)ADLER_BASE)", "((int32_t)rr - (int32_t)ADLER_BASE)",
+     "zero_behind_hi_then_mid"),
+    ("exact_at_ignored", "adler_chain.h", "k == st.exact_at ? st.exact_next : adler_signed_s2(rr, prev)", "adler_signed_s2(rr, prev)",
+     "adjacent_exact"),
+    ("prev_branch_no_walk_back", "adler_chain.h", "  while (run >= 0 && run_last_hi[run] == 0xFFFFFFFFu) run--;\n", "",
+     ("equivalent", "run (k - 1) / per holds chunk k - 1, so it is never empty: the walk back never takes a step")),
+    ("prev_branch_of_k", "adler_chain.h", "int64_t run = (int64_t)((k - 1) / per);", "int64_t run = (int64_t)(k / per);",
+     "opens_run_behind_hi"),
+    ("delta_not_carried", "adler_chain.h", "const uint32_t rr = addmod(res, st.delta);", "const uint32_t rr = addmod(res, 0u);",
+     "delta_carried"),
+    ("final_without_delta", "adler_chain.h", "(total_res + st.delta) % ADLER_BASE", "(total_res + 0u) % ADLER_BASE", "mid_upper_bound"),
+    ("final_ignores_exact_at", "adler_chain.h", "if (st.exact_at == n_chunks) final_s2", "if (false && st.exact_at == n_chunks) final_s2",
+     "low_bound_stays_negative_last"),
+    ("fallback_at_the_limit", "adler_chain.h", "n_amb > amb_cap || n_amb > replay_max", "n_amb > amb_cap || n_amb >= replay_max",
+     "replay_at_its_limit"),
+    ("per_rounded_down", "adler_chain.h", "(n_chunks + n_runs - 1) / n_runs : 1", "n_chunks / n_runs : 1", "ten_chunks_four_runs"),
+    ("rfc_chain_bytes_not_reduced", "adler_chain.h", "(nb[i] % ADLER_BASE) * c1", "nb[i] * c1",
+     ("equivalent", "a run's bytes stay below 2^37 for any length the launches take and c1 < 2^16: the 64-bit product cannot wrap")),
 ]
 # what runs against each GPU mutant: the vectors under the default form, then under every override (one process each)
 TESTS = "tests/test_gpu_parity.py"

@@ -256,7 +256,7 @@ hipError_t crc32_finish_launch(zipc_hip_ctx *ctx, int mode, const StreamDesc *d_
     ZD_LAUNCH(ctx, "crc32_finish", crc32_finish_streams_kernel, dim3((unsigned)((n_ranges + 255) / 256)), dim3(256), 0,
               mode, d_descs, d_results, (uint32_t)n_ranges, (uint32_t)segs, ctx->crc_consts, partials);
   else
-    ZD_LAUNCH(ctx, "crc32_finish", crc32_finish_kernel, dim3((unsigned)n_ranges), dim3(segs > 4096 ? 1024 : 256), 0, mode,
+    ZD_LAUNCH(ctx, "crc32_finish", crc32_finish_kernel, dim3((unsigned)n_ranges), dim3(crc_finish_threads(segs)), 0, mode,
               d_descs, d_results, single_len, (uint32_t)segs, ctx->crc_consts, (const uint32_t *)ctx->crc_nib.p,
               partials, d_single_out);
   return hipGetLastError();
@@ -525,12 +525,11 @@ int zipc_hip_checksum_device(zipc_hip_ctx *ctx, const void *d_buf, size_t len, i
     ~Joiner() { if (on) { c->cur = c->stream; (void)c->join(1); } }
   } joiner{ctx, false};
   if (want_adler32) {
-    const uint64_t n_chunks = len ? len / ADLER_CHUNK + 1 : 0;
+    const uint64_t n_chunks = adler_n_chunks(len);  // (the chain's shape: adler_chain.h)
     // chunk sums, then the ambiguous-chunk list and the per-run arrays of the chain kernels
     const size_t sums_bytes = ((size_t)(n_chunks + 1) * sizeof(uint2) + 255) / 256 * 256;
     AdlerRuns R;
-    R.n_runs = 1024;  // one thread per run; at least ~8 chunks per run
-    while (R.n_runs < ADLER_MAX_RUNS && (uint64_t)R.n_runs * 8 < n_chunks) R.n_runs *= 2;
+    R.n_runs = adler_n_runs(n_chunks);
     const size_t run_bytes = (size_t)R.n_runs * sizeof(uint32_t);
     HIP_TRY(ctx, ctx->ensure(ctx->adler_sums, sums_bytes + ADLER_AMB_CAP * 16 + 5 * run_bytes + 256));
     uint2 *sums = (uint2 *)ctx->adler_sums.p;
@@ -563,7 +562,7 @@ int zipc_hip_checksum_device(zipc_hip_ctx *ctx, const void *d_buf, size_t len, i
       ZD_LAUNCH(ctx, "adler_chunks", adler_chunks_kernel, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0,
                 (const uint8_t *)d_buf, (uint64_t)len, n_chunks, sums);
     }
-    const uint64_t per = n_chunks ? (n_chunks + R.n_runs - 1) / R.n_runs : 1;
+    const uint64_t per = adler_per(n_chunks, R.n_runs);
     HIP_TRY(ctx, hipMemsetAsync(R.amb_count, 0, sizeof(uint32_t), ctx->stream));
     ZD_LAUNCH(ctx, "adler_runs_s1", adler_runs_s1_kernel, dim3(R.n_runs / 256), dim3(256), 0, (const uint2 *)sums,
               n_chunks, per, R);

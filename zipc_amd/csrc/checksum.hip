@@ -300,7 +300,7 @@ __global__ __launch_bounds__(1024) void crc32_finish_kernel(
   uint32_t raw = 0;
   if (nseg <= 1) {
     raw = nseg ? P[0] : 0;
-  } else if (nseg <= 16) {  // short ranges (the batch forms' streams): Horner by the one thread that stores
+  } else if (crc_finish_by_one_thread(nseg)) {  // short ranges (the batch forms' streams): Horner by the one thread that stores
     if (t == 0)
       for (uint32_t j = 0; j < (uint32_t)nseg; j++) raw = gf2_mul(raw, K.xseg) ^ P[j];
   } else {
@@ -308,18 +308,19 @@ __global__ __launch_bounds__(1024) void crc32_finish_kernel(
     // (a run of consecutive partials per thread read a cache line per thread and step: C3's finish took 0.11 ms, a tenth
     // of the pass over the 4 GiB themselves) -- so its Horner step is a shift by a whole ROW, x^(8 * segment * NT), whose
     // nibble table the workgroup makes first; the tree then shifts by a segment, two, four ...
-    const uint64_t R = (nseg + NT - 1) / NT;
-    const uint64_t padp = NT * R - nseg;
+    const uint64_t R = crc_finish_rows(nseg, NT);
+    const uint64_t padp = crc_finish_padp(nseg, NT);  // (the index rules: adler_chain.h)
     const uint32_t xrow = xpow8n_tab(K, (uint64_t)CRC_SEG * NT);
     if (t < GF2_NIB_WORDS) NS[t] = gf2_mul(((uint32_t)t & 15u) << (4 * (t >> 4)), xrow);  // (gf2_nib_table's entries, one per thread)
     __syncthreads();
     uint32_t c = 0;
+    static_assert(CRC_FINISH_ROWS_AT_ONCE == 8, "adler_chain.h");
     for (uint64_t j0 = 0; j0 < R; j0 += 8) {  // eight rows' words requested together (clamped index, value selected afterwards: one
       uint32_t v[8];                          // load at a time behind a branch cost a memory round trip per row)
 #pragma unroll
       for (int u = 0; u < 8; u++) {
-        const int64_t idx = (int64_t)((j0 + (uint64_t)u) * NT + (uint64_t)t) - (int64_t)padp;
-        const uint32_t w = P[idx >= 0 && j0 + (uint64_t)u < R ? idx : 0];
+        const int64_t idx = crc_finish_index(j0 + (uint64_t)u, NT, (uint32_t)t, padp);
+        const uint32_t w = P[crc_finish_load_index(idx, j0 + (uint64_t)u, R)];
         v[u] = idx >= 0 ? w : 0u;
       }
 #pragma unroll
@@ -368,49 +369,22 @@ __global__ __launch_bounds__(256) void adler_chunks_kernel(const uint8_t *__rest
 // (s1' = s1 + A1, s2' = s2 + bytes_of_run * s1 + A2 for a run that maps (0, 0) to (A1, A2)).
 __global__ __launch_bounds__(1024) void adler_rfc_finish_kernel(const uint2 *__restrict__ sums, uint64_t n,
                                                                 uint64_t n_chunks, uint32_t *__restrict__ out) {
+  static_assert(ADLER_RFC_THREADS == 1024, "adler_chain.h");
   __shared__ uint32_t a1[1024], a2[1024];
   __shared__ uint64_t nb[1024];
   const uint32_t t = threadIdx.x;
-  const uint64_t per = (n_chunks + 1023) / 1024;
-  const uint64_t lo = (uint64_t)t * per, hi = lo + per < n_chunks ? lo + per : n_chunks;
-  const uint64_t r = n % ADLER_CHUNK;
-  uint32_t s1 = 0, s2 = 0;
-  uint64_t bytes = 0;
-  for (uint64_t k = lo; k < hi; k++) {
-    const uint32_t len = k == 0 ? (uint32_t)r : ADLER_CHUNK;
-    adler_chunk_step(s1, s2, len, sums[k].x, sums[k].y, true);
-    bytes += len;
-  }
+  uint64_t lo, hi;
+  adler_run_bounds(t, adler_rfc_per(n_chunks), n_chunks, lo, hi);
+  uint32_t s1, s2;
+  uint64_t bytes;
+  adler_rfc_fold_run(sums, lo, hi, (uint32_t)(n % ADLER_CHUNK), s1, s2, bytes);
   a1[t] = s1; a2[t] = s2; nb[t] = bytes;
   __syncthreads();
-  if (t == 0) {
-    uint64_t c1 = 1, c2 = 0;  // Adler-32 starts at (1, 0)
-    for (int i = 0; i < 1024; i++) {
-      c2 = (c2 + (nb[i] % ADLER_BASE) * c1 + a2[i]) % ADLER_BASE;
-      c1 = (c1 + a1[i]) % ADLER_BASE;
-    }
-    out[0] = (uint32_t)((c2 << 16) | c1);
-  }
+  if (t == 0) out[0] = adler_rfc_chain(a1, a2, nb, 1024);
 }
 
-// The chunk chain (src/zipc_deflate.ml:196: s1/s2 := SIGNED rem after every chunk)
-// for hundreds of thousands of chunks, without walking them one by one.
-//   s1 never goes negative, so s1 before chunk k is (1 + sum of S1) mod 65521: a scan.
-//   s2: with x = s2 before the chunk (|x| < 65521) the reference computes
-//   srem32(wrap32(x + C)), C = n * s1 + S2 < 2^32.  Unless C lies within 65521 of 0
-//   or of 2^31 the branch taken depends on C alone: below 2^31 the result is
-//   (x + C) mod p >= 0, above it is congruent to x + C - 225 (2^32 mod 65521 = 225)
-//   with a non-positive representative.  So the residues follow from a second scan
-//   of a_k = C_k - 225 * hi_k; the few chunks whose branch does depend on x
-//   ("ambiguous", about 6e-5 of them on random data) are then replayed exactly, in
-//   order, by one thread, each replay shifting all later residues by a constant.
+// The chunk chain: its arithmetic is adler_chain.h (HIP-free, pinned in tests/host_sim); here are its launches.
 constexpr uint32_t CHAIN_THREADS_A = 1024;
-
-// (a + b) mod p for a, b <= p
-__device__ __forceinline__ uint32_t addmod(uint32_t a, uint32_t b) {
-  const uint32_t s = a + b;
-  return s >= ADLER_BASE ? s - ADLER_BASE : s;
-}
 
 __device__ __forceinline__ uint32_t block_excl_scan_mod(uint32_t v, uint32_t *sh, int t) {
   // exclusive scan of per-thread values (each < 65521) over the 1024 threads, mod p
@@ -427,15 +401,6 @@ __device__ __forceinline__ uint32_t block_excl_scan_mod(uint32_t v, uint32_t *sh
   return incl >= v ? incl - v : incl + ADLER_BASE - v;
 }
 
-// what pass 2 already knows about an ambiguous chunk, kept for the replay
-struct AmbRecord {
-  uint32_t k;          // chunk index
-  uint32_t s1;         // s1 before the chunk
-  uint32_t a_partial;  // sum of a_j over the chunks of its run before it (mod p)
-  uint32_t prev_hi;    // branch of chunk k-1 as C_{k-1} alone decides it
-};
-static_assert(sizeof(AmbRecord) == 16, "kernels.h sizes the list with 16 bytes per entry");
-
 // The chain runs as five small launches over R runs of `per` consecutive chunks
 // (R a multiple of 1024, up to 64 Ki: a thread per run, hundreds of workgroups):
 //   adler_runs_s1    sum of S1 per run
@@ -448,8 +413,8 @@ __global__ __launch_bounds__(256) void adler_runs_s1_kernel(const uint2 *__restr
                                                             uint64_t per, AdlerRuns R) {
   const uint64_t run = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (run >= R.n_runs) return;
-  const uint64_t lo = run * per < n_chunks ? run * per : n_chunks;
-  const uint64_t hi = lo + per < n_chunks ? lo + per : n_chunks;
+  uint64_t lo, hi;
+  adler_run_bounds(run, per, n_chunks, lo, hi);
   uint64_t acc = 0;
   for (uint64_t k = lo; k < hi; k++) acc += sums[k].x;
   R.sum[run] = (uint32_t)(acc % ADLER_BASE);
@@ -502,37 +467,23 @@ __global__ __launch_bounds__(256) void adler_runs_a_kernel(const uint2 *__restri
   const uint64_t run = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (run >= R.n_runs) return;
   const uint32_t r = (uint32_t)(n % ADLER_CHUNK);
-  const uint64_t lo = run * per < n_chunks ? run * per : n_chunks;
-  const uint64_t hi = lo + per < n_chunks ? lo + per : n_chunks;
+  uint64_t lo, hi;
+  adler_run_bounds(run, per, n_chunks, lo, hi);
   uint64_t s1 = R.s1_before[run], a_acc = 0;
   uint32_t last_hi = 0xFFFFFFFFu;  // branch of the previous chunk (unknown for the first of the run)
   for (uint64_t k = lo; k < hi; k++) {
     const uint2 sm = sums[k];
-    const uint32_t len = k == 0 ? r : ADLER_CHUNK;
-    const uint64_t C = (uint64_t)len * s1 + sm.y;  // < 2^32
-    const bool hi_k = C >= 0x80000000ull;
-    const bool ambiguous = C < ADLER_BASE || (C > 0x80000000ull - ADLER_BASE && C < 0x80000000ull + ADLER_BASE);
-    if (ambiguous) {
+    AmbRecord rec;
+    if (adler_runs_a_step(k, adler_chunk_len(k, r), sm.x, sm.y, s1, a_acc, last_hi, rec)) {
       const uint32_t slot = atomicAdd(R.amb_count, 1u);
-      if (slot < amb_cap) {
-        AmbRecord rec;
-        rec.k = (uint32_t)k;
-        rec.s1 = (uint32_t)s1;
-        rec.a_partial = (uint32_t)a_acc;
-        rec.prev_hi = last_hi;
-        amb[slot] = rec;
-      }
+      if (slot < amb_cap) amb[slot] = rec;
     }
-    a_acc = (a_acc + C % ADLER_BASE + (hi_k ? ADLER_BASE - 225u : 0u)) % ADLER_BASE;
-    s1 = (s1 + sm.x) % ADLER_BASE;
-    last_hi = hi_k ? 1u : 0u;
   }
   R.sum[run] = (uint32_t)a_acc;       // the run's a sum (the S1 sums are no longer needed)
   R.last_hi[run] = last_hi;
   R.s1_after[run] = (uint32_t)s1;
 }
 
-constexpr uint32_t REPLAY_MAX = 4096;  // ambiguous chunks replayed out of LDS; more: plain walk
 __global__ __launch_bounds__(CHAIN_THREADS_A) void adler_replay_kernel(const uint2 *__restrict__ sums, uint64_t n,
                                                                        uint64_t n_chunks, uint64_t per, AdlerRuns R,
                                                                        uint32_t *__restrict__ amb_raw,
@@ -553,70 +504,31 @@ __global__ __launch_bounds__(CHAIN_THREADS_A) void adler_replay_kernel(const uin
   const uint32_t r = (uint32_t)(n % ADLER_CHUNK);
   const uint32_t *run_res = R.res_before, *run_a = R.sum, *run_last_hi = R.last_hi;
   const uint32_t n_amb = R.amb_count[0];
-  if (n_amb > amb_cap || n_amb > REPLAY_MAX) {
+  if (adler_replay_falls_back(n_amb, amb_cap, REPLAY_MAX)) {
     // adversarial input: more ambiguous chunks than worth sorting -- plain walk
     if (t != 0) return;
-    uint32_t a1, a2;
-    adler_unpack(1u, a1, a2);
-    for (uint64_t k = 0; k < n_chunks; k++) adler_chunk_step(a1, a2, k == 0 ? r : ADLER_CHUNK, sums[k].x, sums[k].y);
-    out[0] = adler_pack(a1, a2);
+    out[0] = adler_plain_walk(sums, n_chunks, r);
     return;
   }
-  // branch of the chunk before position k when k opens a run: last chunk of the
-  // nearest earlier non-empty run
-  auto prev_branch = [&](uint64_t k, uint32_t rec_prev_hi) -> bool {
-    if (rec_prev_hi != 0xFFFFFFFFu) return rec_prev_hi != 0;
-    if (k == 0) return false;
-    int64_t run = (int64_t)((k - 1) / per);
-    while (run >= 0 && run_last_hi[run] == 0xFFFFFFFFu) run--;
-    return run >= 0 && run_last_hi[run] != 0;
-  };
   for (uint32_t i = (uint32_t)t; i < n_amb; i += CHAIN_THREADS_A) keys[i] = amb[i].k;
   __syncthreads();
   for (uint32_t i = (uint32_t)t; i < n_amb; i += CHAIN_THREADS_A) {  // rank sort (chunk indices are distinct)
     const AmbRecord rec = amb[i];
     uint32_t rank = 0;
     for (uint32_t j = 0; j < n_amb; j++) rank += keys[j] < rec.k ? 1u : 0u;
-    const uint2 sm = sums[rec.k];
-    const uint32_t len = rec.k == 0 ? r : ADLER_CHUNK;
-    const uint32_t C = len * rec.s1 + sm.y;  // < 2^32
-    r_k[rank] = rec.k;
-    r_res[rank] = addmod(run_res[rec.k / per], rec.a_partial);
-    r_C[rank] = C;
-    r_pc[rank] = addmod(C % ADLER_BASE, C >= 0x80000000u ? ADLER_BASE - 225u : 0u);
-    r_prev[rank] = prev_branch(rec.k, rec.prev_hi) ? 1 : 0;
+    const ReplayRecord p = adler_replay_prepare(rec, r, sums[rec.k].y, per, run_res, run_last_hi);
+    r_k[rank] = p.k;
+    r_res[rank] = p.res;
+    r_C[rank] = p.C;
+    r_pc[rank] = p.pc;
+    r_prev[rank] = p.prev;
   }
   __syncthreads();
   if (t != 0) return;
   // ---- replay of the ambiguous chunks, in order, by one thread
-  uint32_t delta = 0;            // correction (mod p) of every predicted residue from here on
-  int32_t exact_next = 0;        // exact s2 after the last replayed chunk ...
-  uint64_t exact_at = ~0ull;     // ... valid as the input of chunk `exact_at`
-  for (uint32_t i = 0; i < n_amb; i++) {
-    const uint32_t k = r_k[i];
-    const uint32_t rr = addmod(r_res[i], delta);
-    const int32_t x = k == exact_at ? exact_next : (r_prev[i] ? (rr == 0 ? 0 : (int32_t)rr - (int32_t)ADLER_BASE) : (int32_t)rr);
-    const uint32_t t2 = r_C[i] + (uint32_t)x;                 // wraps like the reference's int32
-    const int32_t outv = (int32_t)t2 % (int32_t)ADLER_BASE;  // the reference's signed rem
-    const uint32_t ro = (uint32_t)(outv < 0 ? outv + (int32_t)ADLER_BASE : outv);
-    const uint32_t predicted = addmod(rr, r_pc[i]);
-    delta = addmod(addmod(delta, ro), ADLER_BASE - predicted);
-    exact_next = outv;
-    exact_at = (uint64_t)k + 1;
-  }
-  // state after the last chunk
-  uint32_t final_s2;
-  if (exact_at == n_chunks) final_s2 = (uint32_t)(int32_t)exact_next;
-  else {
-    const uint64_t last_run = n_chunks ? (n_chunks - 1) / per : 0;
-    const uint64_t total_res = n_chunks ? ((uint64_t)run_res[last_run] + run_a[last_run]) % ADLER_BASE : 0;
-    const uint64_t rr = (total_res + delta) % ADLER_BASE;
-    const bool ph = n_chunks ? prev_branch(n_chunks, 0xFFFFFFFFu) : false;
-    final_s2 = (uint32_t)(int32_t)(ph ? (rr == 0 ? 0 : (int64_t)rr - ADLER_BASE) : (int64_t)rr);
-  }
-  const uint64_t lr = n_chunks ? (n_chunks - 1) / per : 0;
-  const uint64_t s1_all = n_chunks ? R.s1_after[lr] : 1;
-  out[0] = adler_pack((uint32_t)s1_all, final_s2);
+  ReplayState st;
+  for (uint32_t i = 0; i < n_amb; i++) adler_replay_step(st, r_k[i], r_res[i], r_C[i], r_pc[i], r_prev[i] != 0);
+  out[0] = adler_replay_final(st, n_chunks, per, run_res, run_a, run_last_hi, R.s1_after);
 }
 
 }  // namespace zd

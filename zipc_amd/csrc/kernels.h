@@ -2,6 +2,7 @@
 // and zlib.hip's and recode.hip's (api.hip).  deflate.hip and inflate.hip keep theirs to themselves, behind launch_deflate / launch_inflate (ctx.h).
 #pragma once
 
+#include "adler_chain.h"
 #include "recode_rules.h"
 #include "zd_common.h"
 
@@ -60,8 +61,7 @@ __global__ void adler_chunks_kernel(const uint8_t *__restrict__ p, uint64_t n, u
 // RFC 1950's Adler-32 from the chunk sums (one workgroup)
 __global__ void adler_rfc_finish_kernel(const uint2 *__restrict__ sums, uint64_t n, uint64_t n_chunks,
                                         uint32_t *__restrict__ out);
-constexpr uint32_t ADLER_AMB_CAP = 8192;  // ambiguous-chunk records (16 bytes each)
-constexpr uint32_t ADLER_MAX_RUNS = 65536;
+// (ADLER_AMB_CAP records of 16 bytes, ADLER_MAX_RUNS: adler_chain.h)
 // per-run arrays of the Adler chain (device scratch, n_runs entries each)
 struct AdlerRuns {
   uint32_t n_runs;       // a multiple of 1024
