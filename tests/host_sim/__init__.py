@@ -5,7 +5,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libhost_sim.so")
-SRCS = ["sim_inflate.cpp", "sim_deflate.cpp", "sim_chain.cpp", "sim_forms.cpp", "sim_adler.cpp"]
+SRCS = ["sim_inflate.cpp", "sim_deflate.cpp", "sim_chain.cpp", "sim_forms.cpp", "sim_adler.cpp", "sim_many.cpp"]
 
 
 def lib():
@@ -68,7 +68,19 @@ def _bind(L):
     L.sim_resolve_grid.argtypes = [C.c_int, C.c_uint32]
     L.sim_blocks_shares.restype = None
     L.sim_blocks_shares.argtypes = [u32p, u32p, C.c_uint64, u64p, u64p, u64p]
-    return bind_adler(L)
+    return bind_many(bind_adler(L))
+
+
+def bind_many(L):
+    """sim_many.cpp's entry points (a library of that file alone has no others: the mutants of tests/test_many_plan.py)"""
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    L.sim_many_slot.restype = C.c_uint64
+    L.sim_many_slot.argtypes = [C.c_uint64]
+    L.sim_many_chunks.restype = C.c_uint64
+    L.sim_many_chunks.argtypes = [C.c_long, C.c_uint64]
+    L.sim_many_plan.restype = C.c_uint64
+    L.sim_many_plan.argtypes = [C.c_int, C.c_uint64, u64p, u64p, u64p, u64p, u32p, C.c_long, C.c_long, u64p, u64p, u64p, u64p, u64p, u64p]
+    return L
 
 
 def bind_adler(L):
@@ -252,3 +264,27 @@ def crc_finish_grid(L, nseg, segs=None, threads=0):
     nu = L.sim_crc_finish_grid(nseg, segs, threads, used.ctypes.data, cap, loaded.ctypes.data, cap, C.byref(nl), info)
     assert nu <= cap and nl.value <= cap
     return used[:nu], loaded[:nl.value], dict(zip(("threads", "rows", "padp", "one_thread"), info))
+
+
+# ---- zipc_amd/csrc/host_pipeline.h through sim_many.cpp: the plan of a many-stream call
+MANY_DEFLATE, MANY_INFLATE, MANY_RECODE = 0, 1, 2
+MANY_SCALARS = ("src_arena_end", "dst_arena_end", "max_src", "max_cap", "max_mid", "K", "n_max", "total_max", "mid_arena",
+                "mid_total_max", "ahead")
+RECODE_DESC_FIELDS = ("src_off", "src_len", "mid_off", "mid_cap", "dst_off", "dst_cap", "limit", "flags", "expect_crc32")
+
+
+def many_plan(L, op, src_len, dst_cap, limit=None, mid_cap=None, expect_crc32=None, chunks=0, chunk_min=1024):
+    """plan_many of a call -> dict of MANY_SCALARS, src_off, dst_off, cut and, for a recode, rdescs (dicts of
+    RECODE_DESC_FIELDS) and inflate_descs (tuples: src_off, src_len, dst_off, dst_cap, limit, flags, reserved)"""
+    n = len(src_len)
+    arr = lambda v, t=C.c_uint64: None if v is None else (t * max(n, 1))(*v)
+    scalars, cut = (C.c_uint64 * len(MANY_SCALARS))(), (C.c_uint64 * 65)()
+    src_off, dst_off = (C.c_uint64 * max(n, 1))(), (C.c_uint64 * max(n, 1))()
+    rd, ind = (C.c_uint64 * (9 * max(n, 1)))(), (C.c_uint64 * (7 * max(n, 1)))()
+    k = L.sim_many_plan(op, n, arr(src_len), arr(dst_cap), arr(limit), arr(mid_cap), arr(expect_crc32, C.c_uint32), chunks, chunk_min,
+                        scalars, src_off, dst_off, cut, rd, ind)
+    out = dict(zip(MANY_SCALARS, scalars), src_off=list(src_off[:n]), dst_off=list(dst_off[:n]), cut=list(cut[:k + 1]))
+    if op == MANY_RECODE:
+        out["rdescs"] = [dict(zip(RECODE_DESC_FIELDS, rd[9 * i:9 * i + 9])) for i in range(n)]
+        out["inflate_descs"] = [tuple(ind[7 * i:7 * i + 7]) for i in range(n)]
+    return out

@@ -1,7 +1,9 @@
 // pipeline_sim.cpp -- the many-stream forms' host pipeline (zipc_amd/csrc/host_pipeline.h: the staging pools, the thread
 // that feeds the device, the thread that takes results back) with host threads standing in for the device.  Built by
 // tests/test_sanitizers.py with -fsanitize=thread and with -fsanitize=address,undefined: the code is the product's,
-// unchanged; only the five Device callbacks differ from api.hip's.
+// unchanged; only the five Device callbacks differ from many.hip's.  The streams' slots are plan_many's, and so is the cut
+// on a third of the calls (with a small chunk_min, so that the shrink rule and the taper are walked too); the other calls
+// cut at random, which is where empty sub-batches come from.
 //
 // The stand-in device: three in-order queues (copy in, kernels, way back), each a thread that runs closures in the order
 // they were enqueued, plus events one queue records and another waits for -- the shape of the three HIP queues.  Its
@@ -22,7 +24,7 @@
 
 using namespace zd_host;
 
-struct Desc { uint64_t src_off, src_len, dst_off, dst_cap; };
+using Desc = zd::StreamDesc;
 
 // an in-order queue: a thread that runs closures one after the other
 class Queue {
@@ -115,7 +117,7 @@ struct SimDevice {
       }
       memcpy(pin_res + lo, dev_res.data() + lo, (hi - lo) * sizeof(zipc_hip_stream_result));
       done_k->fire();
-      if (!job.want_bytes) ev_out[g].fire();  // results only: nothing else comes back (api.hip records ev_out behind the kernels)
+      if (!job.want_bytes) ev_out[g].fire();  // results only: nothing else comes back (many.hip records ev_out behind the kernels)
     });
     if (!job.want_bytes) return ZIPC_HIP_OK;
     copy_out.push([this, g, lo, hi, done_k] {
@@ -144,8 +146,6 @@ static int one_call(std::mt19937_64 &rng, Pools &pools, int inject) {
   std::vector<const void *> src(n);
   std::vector<void *> dst(n);
   std::vector<size_t> src_len(n), dst_cap(n);
-  std::vector<Desc> descs(n);
-  uint64_t so = 0, dof = 0;
   const bool long_ones = rng() % 4 == 0;
   for (size_t i = 0; i < n; i++) {
     size_t len = rng() % 5 == 0 ? 0 : 1 + rng() % 20000;
@@ -159,20 +159,24 @@ static int one_call(std::mt19937_64 &rng, Pools &pools, int inject) {
     const size_t cap = rng() % 11 == 0 ? len / 3 : len + 16;  // some too small
     dsts[i].assign(cap + 1, 0xEE);
     src[i] = srcs[i].data(); dst[i] = dsts[i].data(); src_len[i] = len; dst_cap[i] = cap;
-    descs[i] = Desc{so, len, dof, cap};
-    so += (len + 255) / 256 * 256 + 256;
-    dof += (cap + 255) / 256 * 256 + 256;
   }
   ManyJob<Desc> job;
-  const size_t K = 1 + rng() % 6;
-  job.cut.assign(K + 1, n);
-  job.cut[0] = 0;
-  for (size_t g = 1; g < K; g++) job.cut[g] = std::min(n, job.cut[g - 1] + (size_t)(rng() % (2 * n / K + 1)));
-  for (size_t g = 0; g < K; g++) job.n_max = std::max(job.n_max, job.cut[g + 1] - job.cut[g]);
+  const ManyPlan plan = plan_many(MANY_DEFLATE, n, src_len.data(), dst_cap.data(), nullptr, nullptr, nullptr, (long)(1 + rng() % 6), (long)(1 + rng() % 8));
+  job.take(plan);
+  if (rng() % 3 != 0) {  // a cut of its own: sub-batches of any size, empty ones among them
+    const size_t K = 1 + rng() % 6;
+    job.cut.assign(K + 1, n);
+    job.cut[0] = 0;
+    job.n_max = 0;
+    for (size_t g = 1; g < K; g++) job.cut[g] = std::min(n, job.cut[g - 1] + (size_t)(rng() % (2 * n / K + 1)));
+    for (size_t g = 0; g < K; g++) job.n_max = std::max(job.n_max, job.cut[g + 1] - job.cut[g]);
+  }
+  const size_t K = job.cut.size() - 1;
+  const uint64_t so = job.src_arena_end, dof = job.dst_arena_end;
   std::vector<uint8_t> pin_src(so + 64), pin_dst(dof + 64);
   std::vector<zipc_hip_stream_result> pin_res(n), results(n, zipc_hip_stream_result{0xDEAD, 0xDEAD, 0xDEAD});
   job.n = n; job.src = src.data(); job.src_len = src_len.data(); job.dst = dst.data(); job.dst_cap = dst_cap.data();
-  job.results = results.data(); job.descs = descs.data(); job.src_arena_end = so; job.dst_arena_end = dof;
+  job.results = results.data();
   job.want_bytes = rng() % 5 != 0;
   job.packed = job.want_bytes && rng() % 4 != 0; job.ahead = rng() % 3 == 0; job.h2d_bytes = rng() % 3 == 0 ? 0 : 1 << (12 + rng() % 10);
   job.pin_src = pin_src.data(); job.pin_dst = pin_dst.data(); job.pin_res = pin_res.data();
@@ -183,7 +187,7 @@ static int one_call(std::mt19937_64 &rng, Pools &pools, int inject) {
   std::string why;
   ManyTimes times;
   const int st = many_pipeline(job, dev, pools, why, rng() % 2 ? &times : nullptr);
-  dev.drain();  // (api.hip waits for its three queues after a failure in the same way)
+  dev.drain();  // (many.hip waits for its three queues after a failure in the same way)
   size_t defined_upto = n;
   if (inject) {
     // a sub-batch that holds no streams cannot fail: the injection may not have fired

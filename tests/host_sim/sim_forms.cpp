@@ -1,5 +1,5 @@
 // The launch rules of zipc_amd/csrc/forms.h and inflate_blocks.h and the scratch layout of deflate_scratch.h behind a C view.
-// TEST TOOLING ONLY: the very headers deflate.hip, inflate.hip and api.hip compile, so that tests/test_host_sim.py can hold
+// TEST TOOLING ONLY: the very headers deflate.hip, inflate.hip, api.hip and many.hip compile, so that tests/test_host_sim.py can hold
 // every threshold to rows written out by hand.
 #include <string.h>
 

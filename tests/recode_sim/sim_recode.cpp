@@ -1,5 +1,5 @@
 // sim_recode.cpp -- zipc_amd/csrc/recode_rules.h compiled with g++: open, link and close of a recode as the kernels of
-// recode.hip and the host form of api.hip apply them, over a table of streams read from stdin, with arrays standing in
+// recode.hip and the host form's plan (host_pipeline.h) apply them, over a table of streams read from stdin, with arrays standing in
 // for the context's scratch and a stub standing in for the codec.  Test tooling only (tests/test_recode_rules.py builds it
 // plain and under the address and undefined-behaviour sanitizers, and runs it as a process of its own).
 //

@@ -1,5 +1,5 @@
 """zipc_hip_deflate_many / zipc_hip_inflate_many (include/zipc_hip.h) on batches big and
-ragged enough that the call runs as a pipeline of several sub-batches (api.hip many_streams:
+ragged enough that the call runs as a pipeline of several sub-batches (many.hip many_streams:
 4 of them from 4096 streams on, the first and the last half as large as the others, each
 through gather, copy in, kernels, the way back -- the outputs end to end, written into the
 pinned buffer by a kernel -- and scatter on its own queues, events and host threads; a
@@ -76,7 +76,7 @@ def test_many_streams_chunked_staging_equals_oracle(gpu_ctx, oracle):
 
     lib = _lib.lib()
     n = 4500
-    assert n // 4 >= 1024  # many_streams() keeps its default of 4 sub-batches only if each holds >= 1024 streams
+    assert n // 4 >= 1024  # plan_many keeps its default of 4 sub-batches only if each holds >= 1024 streams
     plain = _ragged_inputs(n, 5)
     level = 2
 

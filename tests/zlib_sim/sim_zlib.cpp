@@ -1,5 +1,5 @@
 // sim_zlib.cpp -- zipc_amd/csrc/zlib_container.h compiled with g++: the container's rules as the kernels of zlib.hip and
-// the host forms of api.hip apply them, for tests/test_zlib_rules.py to hold against the oracle.  Test tooling only.
+// the host forms of api.hip and many.hip apply them, for tests/test_zlib_rules.py to hold against the oracle.  Test tooling only.
 #include "../../zipc_amd/csrc/zlib_container.h"
 
 extern "C" {

@@ -1,5 +1,5 @@
 #!/bin/bash
-# After a change to the many-stream host forms (api.hip many_streams): their tests, the old library beside the new one
+# After a change to the many-stream host forms (many.hip many_streams, host_pipeline.h plan_many): their tests, the old library beside the new one
 # on the same box (zipc_amd/lib/libzipc_hip_old.so, if one was built), every switch of the forms in turn, and where each
 # sub-batch of a call was when.   usage (on the GPU box): bash tools/gpu_host_check.sh <tag>
 TAG=${1:-r05}

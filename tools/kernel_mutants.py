@@ -147,6 +147,19 @@ ADLER_MUTANTS = [
     ("rfc_chain_bytes_not_reduced", "adler_chain.h", "(nb[i] % ADLER_BASE) * c1", "nb[i] * c1",
      ("equivalent", "a run's bytes stay below 2^37 for any length the launches take and c1 < 2^16: the 64-bit product cannot wrap")),
 ]
+# (name, file, text, replacement, killer): one-line mutants of the many-stream forms' plan (host_pipeline.h plan_many), killed on
+# the CPU only -- each built into a model of its own (tests/host_sim/sim_many.cpp) by
+# tests/test_many_plan.py::test_plan_mutants_are_killed.  killer: the row of that file's ROWS it must fail.  A wrong cut still
+# gives right bytes: no parity test would notice any of these.
+MANY_PLAN_MUTANTS = [
+    ("taper_shares_not_doubled", "host_pipeline.h", "taper ? 2 * g - 1 : g;", "taper ? g : g;", "taper_K4"),
+    ("taper_divides_by_K", "host_pipeline.h", "so / shares * before", "so / K * before", "taper_K4"),
+    ("shrink_either_clause", "host_pipeline.h", "n / K < least && so / K < least * 65536", "n / K < least || so / K < least * 65536",
+     "shrink_bytes_at_the_limit"),
+    ("slot_without_its_gap", "host_pipeline.h", "return (len + 255) / 256 * 256 + 256;", "return (len + 255) / 256 * 256;", "slots"),
+    ("mid_off_runs_on", "host_pipeline.h", "uint64_t mo = 0;", "uint64_t mo = p.mid_arena;", "recode_mid_arena"),
+    ("six_from_two_gib", "host_pipeline.h", "staged_bytes >= ((uint64_t)1 << 30)", "staged_bytes >= ((uint64_t)1 << 31)", "count_at_a_gib"),
+]
 # what runs against each GPU mutant: the vectors under the default form, then under every override (one process each)
 TESTS = "tests/test_gpu_parity.py"
 SELECT = "second_readings_vectors"

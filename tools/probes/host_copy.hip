@@ -1,6 +1,6 @@
 // How fast do bytes cross the bus when a KERNEL moves them (stores into / loads from pinned host memory) beside the
 // copy engines (hipMemcpyAsync), what do both directions at once cost each other, and what does a kernel that works on
-// device memory lose meanwhile?  Behind api.hip many_streams: results come back by a kernel that writes the pinned
+// device memory lose meanwhile?  Behind many.hip many_streams: results come back by a kernel that writes the pinned
 // buffer.  What this prints on the pool's MI355X boxes (profiles/r05_host_copy.txt):
 //  * alone, every way of moving 256 MiB takes 4.7-4.9 ms (55-57 GB/s): engine or kernel, in or out, 64 to 4096 workgroups;
 //  * an engine copy out beside an engine copy in: 13.4 / 14.1 ms -- unless ANY wave is resident (a kernel spinning on

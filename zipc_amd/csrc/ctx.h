@@ -8,6 +8,7 @@
 
 #include "../../include/zipc_hip.h"
 #include "kernels.h"
+#include "recode_rules.h"
 
 struct zipc_hip_ctx {
   int device = 0;
@@ -42,7 +43,7 @@ struct zipc_hip_ctx {
   };
   Buf io_src, io_dst, io_desc, io_res, io_small;  // staging of the host forms
   Buf pin_src, pin_dst, pin_res;                  // pinned host memory of the many-stream host forms
-  Buf io_pack_off;                                // ... where each output of a sub-batch begins once they lie end to end (api.hip pack_offsets_kernel)
+  Buf io_pack_off;                                // ... where each output of a sub-batch begins once they lie end to end (many.hip pack_offsets_kernel)
   hipStream_t copy_in = nullptr, copy_out = nullptr;  // their H2D / D2H queues (made on first use)
   Buf crc_partials, adler_sums;                   // checksum kernels
   Buf crc_nib;                                    // nibble tables of the CRC merge constants (kernels.h)
@@ -134,4 +135,22 @@ int launch_inflate(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena
 // stream, one launch on ctx->cur
 int launch_inflate_size(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
                         size_t n_streams);
+// recode.hip: zipc_hip_recode_batch behind its argument checks, and the kernels' step of zipc_hip_recode_many (a ZIPC_HIP_*
+// status): open -> inflate with its CRC-32 pass -> link -> deflate -> close on ctx->stream.  d_plain: null, or n StreamResults
+// for the many-stream pipeline; h_inflate_descs, first_of_call: launch_inflate's.  recode_reserve: its scratch for n streams,
+// for a caller that wants it grown before anything is in flight
+int recode_reserve(zipc_hip_ctx *ctx, size_t n);
+int launch_recode(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_mid_arena, void *d_dst_arena, const RecodeDesc *d_descs,
+                  RecodeResult *d_results, StreamResult *d_plain, size_t n, size_t max_mid_cap, size_t total_mid_cap, int level,
+                  const StreamDesc *h_inflate_descs, bool first_of_call);
+// zlib.hip: the checksum the zlib forms of this context ask the codec for, and the container's kernels around the codec's
+// (a ZIPC_HIP_* status each): open leaves the codec's descriptors in ctx->zlib_descs and the checks' verdicts in ctx->zlib_pre
+int zlib_crc_op(const zipc_hip_ctx *ctx);
+int launch_zlib_open(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, size_t n, int compress);
+int launch_zlib_close(zipc_hip_ctx *ctx, void *d_dst_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                      size_t n, int compress, int level);
+int launch_zlib_close_size(zipc_hip_ctx *ctx, zipc_hip_stream_result *d_results, size_t n);
+// many.hip: the staging threads' pools, shared by the process's contexts (zipc_hip_create / zipc_hip_destroy)
+void many_pools_acquire();
+void many_pools_release();
 }  // namespace zd

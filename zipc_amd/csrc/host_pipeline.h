@@ -1,10 +1,13 @@
-// host_pipeline.h -- the host half of the many-stream forms (zipc_hip_deflate_many / zipc_hip_inflate_many), free of HIP.
+// host_pipeline.h -- the host half of the many-stream forms (zipc_hip_deflate_many / zipc_hip_inflate_many /
+// zipc_hip_recode_many), free of HIP.
 //
-// Everything here runs on host threads: the pools behind the gathers and scatters, the copies that go around the cache,
-// and the pipeline that moves a call's sub-batches through   gather -> copy in -> kernels -> way back -> scatter   with one
-// thread feeding the device and a second one taking results back.  The device's part is five callbacks (struct Device
-// below), so that the same code is compiled twice:
-//   * into libzipc_hip.so (api.hip many_streams: the callbacks enqueue copies, kernels and events on three HIP queues);
+// Two things live here.  The PLAN of a call (plan_many below): where every stream lies in the staging arenas, how many
+// sub-batches the call is cut into and where, what the largest sub-batch needs -- pure functions of the call's lengths and
+// two settings, held to rows written out by hand in tests/test_many_plan.py.  And what runs on host threads: the pools
+// behind the gathers and scatters, the copies that go around the cache, and the pipeline that moves a call's sub-batches
+// through   gather -> copy in -> kernels -> way back -> scatter   with one thread feeding the device and a second one
+// taking results back.  The device's part is five callbacks (struct Device below), so that the same code is compiled twice:
+//   * into libzipc_hip.so (many.hip many_streams: the callbacks enqueue copies, kernels and events on three HIP queues);
 //   * into tests/host_sim/pipeline_sim.cpp with g++ -fsanitize=thread / address, where three host threads with in-order
 //     queues and memcpy stand in for the device (round 5's review: "host-side concurrency has no sanitizer coverage").
 // Nothing in this file computes a result: bytes are moved, statuses copied.
@@ -26,6 +29,8 @@
 #include <vector>
 
 #include "../../include/zipc_hip.h"
+#include "forms.h"         // (BLOCKS_BATCH_MIN_DST: from where on a batch's inflate may go by blocks)
+#include "recode_rules.h"  // (recode_open: what inflate is handed of a recode's stream)
 
 namespace zd_host {
 
@@ -177,14 +182,122 @@ static inline void copy_streaming(void *dst, const void *src, size_t len) {
 #endif
 }
 
-// bytes a stream's output takes in the pinned buffer when a sub-batch's outputs lie end to end (api.hip pack_copy_kernel
-// makes the same sums on the device)
-static inline uint64_t packed_size(uint32_t status, uint64_t out_len, uint64_t dst_cap) {
+// bytes a stream's output takes in the pinned buffer when a sub-batch's outputs lie end to end: many.hip's
+// pack_offsets_kernel on the device and the taker below on the host make their sums with this one function
+ZD_HD uint64_t packed_size(uint32_t status, uint64_t out_len, uint64_t dst_cap) {
   return status == ZIPC_HIP_OK && out_len <= dst_cap ? (out_len + 15) / 16 * 16 : 0;
 }
 
+// ---- the plan of a call ------------------------------------------------------------------------------------------
+
+// A stream's room in a staging arena (sources, destinations, recode's middle arena): its length rounded up to 256 bytes,
+// and 256 more, so that every stream begins on a 256-byte boundary with at least 256 bytes between its end and the next.
+inline uint64_t many_slot(uint64_t len) { return (len + 255) / 256 * 256 + 256; }
+
+// ZIPC_HIP_HOST_CHUNKS: sub-batches a many-stream call is cut into; each goes through gather, copy in, kernels, the
+// way back and scatter on its own, so those overlap (1 = one after the other).  Default (a setting below 1): 4, or 6
+// from a GiB of staging on.  (profiles/r05_host_forms_sweep.txt: 4096 x 64 KiB: 3 / 4 / 5 / 6 sub-batches deflate
+// 9.9 / 9.8 / 9.4 / 10.0 ms, inflate 8.3 / 8.9 / 8.9 / 9.5; 16 384 x 64 KiB: 34.0 / 31.2 / 29.8 / 30.2 and
+// 29.4 / 27.6 / 26.6 / 25.7.)
+inline size_t many_chunks(long setting, uint64_t staged_bytes) {
+  long v = setting;
+  if (v < 1) v = staged_bytes >= ((uint64_t)1 << 30) ? 6 : 4;
+  return (size_t)(v > 64 ? 64 : v);
+}
+
+// what the kernels' step of a many-stream call is.  MANY_RECODE: recode.hip's launch_recode (crc_op: CRC-32); its middle
+// arena is one more buffer of the context, as large as the largest sub-batch needs
+enum ManyOp { MANY_DEFLATE = 0, MANY_INFLATE = 1, MANY_RECODE = 2 };
+
+struct ManyPlan {
+  std::vector<zd::StreamDesc> descs;  // every stream's slots: src_off / dst_off are running sums of many_slot
+  uint64_t src_arena_end = 0, dst_arena_end = 0;
+  size_t max_src = 0, max_cap = 0, max_mid = 0;
+  std::vector<size_t> cut;            // sub-batch g holds streams [cut[g], cut[g + 1]); cut.size() - 1 sub-batches
+  size_t n_max = 0, total_max = 0;    // the largest sub-batch's streams; the most source bytes a sub-batch holds
+  bool ahead = false;                 // sub-batch g + 1 is gathered and sent before g's kernels are asked for (many_pipeline)
+  // MANY_RECODE: the call's descriptors (mid_off restarts at 0 in every sub-batch), what inflate is handed of them
+  // (recode_open is the kernel's rule, so the block path has nothing to read back), the largest sub-batch's extent in
+  // the middle arena and the most room a sub-batch's streams declare there
+  std::vector<zd::RecodeDesc> rdescs;
+  std::vector<zd::StreamDesc> inflate_descs;
+  uint64_t mid_arena = 0;
+  size_t mid_total_max = 0;
+  size_t K() const { return cut.size() - 1; }
+  // where stream i's destination slot begins; i = n: where the arena ends
+  uint64_t dst_end(size_t i) const { return i < descs.size() ? descs[i].dst_off : dst_arena_end; }
+};
+
+// limit: null, or every stream's (STREAM_HAS_LIMIT).  mid_cap: MANY_RECODE's, null otherwise; expect_crc32: null, or the
+// CRC-32 every recoded stream must inflate to.  chunks, chunk_min: Tuning's host_chunks and host_chunk_min.
+// The call is cut into K sub-batches: many_chunks of what is staged, fewer while sub-batches would get too small to fill
+// the chip (under chunk_min streams AND under as many source bytes as that many streams of 64 KiB: long members).  From
+// K = 3 on the first and the last sub-batch are half as large as the others: the first is what the bus and the kernels
+// wait for before they have anything to do, the last what the caller waits for when everything else is through.
+inline ManyPlan plan_many(ManyOp op, size_t n, const size_t *src_len, const size_t *dst_cap, const size_t *limit, const size_t *mid_cap,
+                          const uint32_t *expect_crc32, long chunks, long chunk_min) {
+  ManyPlan p;
+  p.descs.resize(n);
+  uint64_t so = 0, dof = 0;
+  for (size_t i = 0; i < n; i++) {
+    zd::StreamDesc &d = p.descs[i];
+    memset(&d, 0, sizeof d);
+    d.src_off = so; d.src_len = src_len[i]; d.dst_off = dof; d.dst_cap = dst_cap[i];
+    if (limit) { d.limit = limit[i]; d.flags = zd::STREAM_HAS_LIMIT; }
+    so += many_slot(src_len[i]);
+    dof += many_slot(dst_cap[i]);
+    p.max_src = src_len[i] > p.max_src ? src_len[i] : p.max_src;
+    p.max_cap = dst_cap[i] > p.max_cap ? dst_cap[i] : p.max_cap;
+    if (op == MANY_RECODE) p.max_mid = mid_cap[i] > p.max_mid ? mid_cap[i] : p.max_mid;
+  }
+  p.src_arena_end = so; p.dst_arena_end = dof;
+  size_t K = many_chunks(chunks, so + dof);
+  const uint64_t least = (uint64_t)chunk_min;
+  while (K > 1 && n / K < least && so / K < least * 65536) K--;
+  p.cut.assign(K + 1, n);
+  p.cut[0] = 0;
+  const bool taper = K >= 3;
+  const size_t shares = taper ? 2 * K - 2 : K;
+  for (size_t g = 1, i = 0; g < K; g++) {
+    const size_t before = taper ? 2 * g - 1 : g;  // shares of sub-batches [0, g)
+    while (i < n && p.descs[i].src_off < so / shares * before) i++;
+    p.cut[g] = i;
+  }
+  for (size_t g = 0; g < K; g++) {
+    size_t t = 0;
+    for (size_t i = p.cut[g]; i < p.cut[g + 1]; i++) t += src_len[i];
+    p.n_max = p.cut[g + 1] - p.cut[g] > p.n_max ? p.cut[g + 1] - p.cut[g] : p.n_max;
+    p.total_max = t > p.total_max ? t : p.total_max;
+  }
+  if (op == MANY_RECODE) {
+    p.rdescs.resize(n);
+    p.inflate_descs.resize(n);
+    for (size_t g = 0; g < K; g++) {
+      uint64_t mo = 0;
+      size_t t = 0;
+      for (size_t i = p.cut[g]; i < p.cut[g + 1]; i++) {
+        const zd::StreamDesc &d = p.descs[i];
+        zd::RecodeDesc &r = p.rdescs[i];
+        memset(&r, 0, sizeof r);
+        r.src_off = d.src_off; r.src_len = d.src_len; r.dst_off = d.dst_off; r.dst_cap = d.dst_cap;
+        r.mid_off = mo; r.mid_cap = mid_cap[i];
+        r.limit = d.limit; r.flags = d.flags;
+        if (expect_crc32) { r.expect_crc32 = expect_crc32[i]; r.flags |= zd::STREAM_EXPECT_CRC32; }
+        (void)zd::recode_open(r, p.max_mid, &p.inflate_descs[i]);
+        mo += many_slot(mid_cap[i]);
+        t += mid_cap[i];
+      }
+      p.mid_arena = mo > p.mid_arena ? mo : p.mid_arena;
+      p.mid_total_max = t > p.mid_total_max ? t : p.mid_total_max;
+    }
+  }
+  p.ahead = (op == MANY_INFLATE && p.max_cap >= zd::BLOCKS_BATCH_MIN_DST) || (op == MANY_RECODE && p.max_mid >= zd::BLOCKS_BATCH_MIN_DST);
+  return p;
+}
+
 // One call of a many-stream form, as the pipeline sees it.  Desc: anything with src_off / dst_off (where stream i's source
-// and destination slots begin in the staging arenas; the pinned buffers mirror the arenas).
+// and destination slots begin in the staging arenas; the pinned buffers mirror the arenas): many.hip's is zd::StreamDesc,
+// and take() fills the slots, the arenas' ends, the cut and `ahead` from the call's plan.
 template <class Desc>
 struct ManyJob {
   size_t n = 0;
@@ -205,6 +318,11 @@ struct ManyJob {
   const uint8_t *pin_dst = nullptr;           // ... outputs as they come back
   const zipc_hip_stream_result *pin_res = nullptr;  // ... results as the device wrote them (n entries)
   size_t threads = 1;                         // host threads per pool, the caller included
+  // (the plan outlives the call: descs points into it)
+  void take(const ManyPlan &p) {
+    descs = p.descs.data(); src_arena_end = p.src_arena_end; dst_arena_end = p.dst_arena_end;
+    cut = p.cut; n_max = p.n_max; ahead = p.ahead;
+  }
 };
 
 // what the pipeline measured on the host (ms from the call's begin), for ZIPC_HIP_HOST_TIMING

@@ -1760,7 +1760,7 @@ __global__ __launch_bounds__(256) void stored_list_copy_kernel(const uint8_t *__
 }
 
 
-// ---- the launches (host side): zd::launch_inflate is what zipc_hip_inflate_batch and the many-stream host forms call (api.hip)
+// ---- the launches (host side): zd::launch_inflate is what zipc_hip_inflate_batch (api.hip) and the many-stream host forms (many.hip) call
 
 // One stream beyond ZIPC_HIP_MAX_STREAM_LEN: the stored blocks it has to start with (inflate.hip) are found
 // and copied with 64-bit offsets -- a chain of equal blocks all at once, blocks of other lengths by a walk over

@@ -1,29 +1,11 @@
-// kernels.h -- the kernels, constants and structs that more than one translation unit needs: checksum.hip's (api.hip, deflate.hip)
-// and zlib.hip's and recode.hip's (api.hip).  deflate.hip and inflate.hip keep theirs to themselves, behind launch_deflate / launch_inflate (ctx.h).
+// kernels.h -- the kernels, constants and structs that more than one translation unit needs: checksum.hip's (api.hip, deflate.hip).
+// Every other unit keeps its kernels to itself, behind the launchers of ctx.h (launch_deflate, launch_inflate, launch_recode, launch_zlib_*).
 #pragma once
 
 #include "adler_chain.h"
-#include "recode_rules.h"
 #include "zd_common.h"
 
 namespace zd {
-
-// ---- zlib.hip: the container around a batch's streams, a lane per stream (rules: zlib_container.h)
-struct ZlibPre { uint32_t status, expect; };  // the container check's verdict; to decompress, the Adler-32 the stream says it has
-__global__ void zlib_open_kernel(const uint8_t *__restrict__ src_arena, const StreamDesc *__restrict__ descs, uint32_t n_streams,
-                                 int compress, StreamDesc *__restrict__ inner, ZlibPre *__restrict__ pre);
-__global__ void zlib_close_kernel(uint8_t *__restrict__ dst_arena, const StreamDesc *__restrict__ descs,
-                                  const ZlibPre *__restrict__ pre, StreamResult *__restrict__ results, uint32_t n_streams,
-                                  int compress, int level);
-__global__ void zlib_close_size_kernel(const ZlibPre *__restrict__ pre, StreamResult *__restrict__ results, uint32_t n_streams);
-
-// ---- recode.hip: before, between and behind inflate and deflate of a batch, a lane per stream (rules: recode_rules.h)
-__global__ void recode_open_kernel(const RecodeDesc *__restrict__ descs, uint32_t n_streams, uint64_t max_mid_cap,
-                                   StreamDesc *__restrict__ inner, RecodeVerdict *__restrict__ verdicts);
-__global__ void recode_link_kernel(const RecodeDesc *__restrict__ descs, uint32_t n_streams, const StreamResult *__restrict__ inflated,
-                                   StreamDesc *__restrict__ inner, RecodeVerdict *__restrict__ verdicts);
-__global__ void recode_close_kernel(uint32_t n_streams, const RecodeVerdict *__restrict__ verdicts, const StreamResult *__restrict__ deflated,
-                                    RecodeResult *__restrict__ results, StreamResult *__restrict__ plain);
 
 // ---- checksum.hip
 constexpr uint32_t CRC_PIECE_BYTES = 128;  // bytes per thread of crc32_segments_kernel

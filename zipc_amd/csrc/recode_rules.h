@@ -6,7 +6,7 @@
 // kernels are not touched: three small steps stand before, between and behind them, and they are pure functions of
 // plain numbers, so the same code is compiled three times:
 //   * into recode.hip's kernels (a lane per stream opens, links and closes on the device; nothing is read back);
-//   * into api.hip's host form (zipc_hip_recode_many hands inflate the descriptors it already knows);
+//   * into the host form's plan (host_pipeline.h plan_many: zipc_hip_recode_many hands inflate the descriptors it already knows);
 //   * into tests/recode_sim/sim_recode.cpp with g++, where tests/test_recode_rules.py checks a table of every rule.
 #pragma once
 

@@ -39,7 +39,7 @@ struct Tuning {
                                //                          false end-of-block starts again, inflate.hip).  test_gpu_fuzz
   int resolve_hops0, resolve_hops1;  // ZIPC_HIP_RESOLVE_HOPS0 / 1  links a thread follows in the first / a later resolve round
                                //                          (default 256).  test_gpu_fuzz
-  // ---- host forms (api.hip many_streams)
+  // ---- host forms (many.hip many_streams; the rule of the two sub-batch settings: host_pipeline.h plan_many)
   long host_threads;           // ZIPC_HIP_HOST_THREADS    staging threads of the many-stream host forms (default 0: 8 threads or the
                                //                          core count).  include/zipc_hip.h
   long host_chunks;            // ZIPC_HIP_HOST_CHUNKS     sub-batches of those forms (default 0: 4, 6 from a GiB staged).  test_gpu_fuzz

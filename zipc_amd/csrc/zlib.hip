@@ -8,8 +8,9 @@
 //                      or the header and the trailer stored around what deflate wrote.
 //   zlib_close_size_kernel  the same behind inflate's size kernel (zipc_hip_zlib_size_batch): the verdict, or the body's size.
 // The rules themselves are zlib_container.h's (the host forms and the tests compile the same functions).  Nothing is
-// read back: the calls enqueue and return like the raw batch forms.
-#include "kernels.h"
+// read back: the calls enqueue and return like the raw batch forms.  The launches at the end of this file are the one
+// way to the kernels (ctx.h).
+#include "ctx.h"
 #include "zlib_container.h"
 
 namespace zd {
@@ -90,6 +91,32 @@ __global__ __launch_bounds__(256) void zlib_close_size_kernel(const ZlibPre *__r
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_streams) return;
   results[i] = zlib_close_size(pre[i].status, results[i]);
+}
+
+int zlib_crc_op(const zipc_hip_ctx *ctx) { return ctx->adler_rfc1950 ? ZIPC_HIP_CRC_ADLER32_RFC1950 : ZIPC_HIP_CRC_ADLER32; }
+
+// zlib_open_kernel over the caller's descriptors: the codec's descriptors and the checks' verdicts, in the context's scratch
+int launch_zlib_open(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, size_t n, int compress) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->ensure(ctx->zlib_descs, n * sizeof(StreamDesc)));
+  HIP_TRY(ctx, ctx->ensure(ctx->zlib_pre, n * sizeof(ZlibPre)));
+  ZD_LAUNCH(ctx, "zlib_open", zlib_open_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint8_t *)d_src_arena,
+            (const StreamDesc *)d_descs, (uint32_t)n, compress, (StreamDesc *)ctx->zlib_descs.p, (ZlibPre *)ctx->zlib_pre.p);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+int launch_zlib_close(zipc_hip_ctx *ctx, void *d_dst_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                      size_t n, int compress, int level) {
+  ZD_LAUNCH(ctx, "zlib_close", zlib_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (uint8_t *)d_dst_arena,
+            (const StreamDesc *)d_descs, (const ZlibPre *)ctx->zlib_pre.p, (StreamResult *)d_results, (uint32_t)n, compress, level);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+int launch_zlib_close_size(zipc_hip_ctx *ctx, zipc_hip_stream_result *d_results, size_t n) {
+  ZD_LAUNCH(ctx, "zlib_close_size", zlib_close_size_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+            (const ZlibPre *)ctx->zlib_pre.p, (StreamResult *)d_results, (uint32_t)n);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
 }
 
 }  // namespace zd

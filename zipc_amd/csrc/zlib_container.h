@@ -4,7 +4,7 @@
 // zlib_decompress (src/zipc_deflate.ml:720-740) and zlib_compress (:1262-1277) are inflate / deflate with Adler-32 plus
 // the rules below.  They are pure functions of plain numbers, so the same code is compiled three times:
 //   * into zlib.hip's two kernels (zipc_hip_zlib_*_batch: a lane per stream opens and closes the container on the device);
-//   * into api.hip's host forms (zipc_hip_zlib_compress / _decompress and the *_many forms);
+//   * into the host forms (api.hip zipc_hip_zlib_compress / _decompress, many.hip the *_many forms);
 //   * into tests/zlib_sim/sim_zlib.cpp with g++, where tests/test_zlib_rules.py holds every (CMF, FLG) pair to the oracle.
 #pragma once
 
@@ -17,6 +17,10 @@ enum : uint32_t { ST_ZLIB_METHOD = 3, ST_ZLIB_WINDOW = 4, ST_ZLIB_DICT = 5, ST_C
 
 constexpr uint64_t ZLIB_MIN_LEN = 6;   // CMF, FLG and the Adler-32: zd.ml:723
 constexpr uint64_t ZLIB_OVERHEAD = 6;  // what zlib_compress adds to deflate's bytes
+
+// what is kept of a stream between open and close (zlib.hip's kernels, many.hip zlib_many): the container check's
+// verdict; to decompress, the Adler-32 the stream says it has
+struct ZlibPre { uint32_t status, expect; };
 
 // The reference's checks of a stream of `len` bytes that begins with cmf, flg, in the reference's order (zd.ml:723-730).
 // (len < ZLIB_MIN_LEN: the two bytes are not looked at -- callers that cannot read them pass anything.)
