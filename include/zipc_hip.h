@@ -113,6 +113,12 @@ const char *zipc_hip_last_error(zipc_hip_ctx *ctx);
  * or 0 when the stream's one wave decoded it (short streams, streams that are not a chain of dynamic blocks,
  * anything that reports an error).  For tests and measurements; the results are the same either way. */
 unsigned zipc_hip_last_inflate_blocks(zipc_hip_ctx *ctx);
+/* the same for sizing: the blocks of the chains that the last sizing call (zipc_hip_inflate_size, any _size_batch form)
+ * sized streams by, a wave per block, or 0 when every stream of it was sized by its one wave.  zipc_hip_last_inflate_blocks
+ * is not touched by a sizing call.  For tests and measurements; the results are the same either way. */
+unsigned zipc_hip_last_size_blocks(zipc_hip_ctx *ctx);
+/* the source length from which one stream goes by a wave per block, to be decoded (given the room) or sized */
+#define ZIPC_HIP_BLOCKS_MIN_SRC ((size_t)40 << 10)
 /* 1 when this context builds hash chains by ordered LDS exchange (deflate.hip lz_chain_xchg_kernel): the probe run
  * by zipc_hip_create found that one LDS exchange instruction serves the lanes that hit one address in ascending lane
  * order, which is the order insert_hash (zipc_deflate.ml:1150-1152) inserts positions in.  0: the probe failed and the
@@ -166,11 +172,13 @@ int zipc_hip_adler32(zipc_hip_ctx *ctx, const void *src, size_t len, uint32_t *a
 int zipc_hip_inflate(zipc_hip_ctx *ctx, const void *src, size_t len, int has_limit,
                      size_t limit, int crc_op, void *dst, size_t dst_cap,
                      size_t *out_len, uint32_t *checksum);
-/* What one host stream inflates to, with nothing inflated: zipc_hip_inflate_size_batch (below) of a batch of one, around
- * a copy of the stream to the device and 16 bytes back.  Returns the stream's status -- what zipc_hip_inflate
+/* What one host stream inflates to, with nothing inflated: zipc_hip_inflate_size_blocks_batch (below) of a batch of one,
+ * around a copy of the stream to the device and 16 bytes back.  Returns the stream's status -- what zipc_hip_inflate
  * (ZIPC_HIP_CRC_NOP) returns for the same src, len, has_limit and limit into a dst of ZIPC_HIP_MAX_STREAM_LEN bytes --
- * and on ZIPC_HIP_OK its decompressed length in *out_len (0 otherwise): the dst_cap that call needs.  The stream is
- * walked by ONE wave whatever its length (see zipc_hip_inflate_size_batch). */
+ * and on ZIPC_HIP_OK its decompressed length in *out_len (0 otherwise): the dst_cap that call needs.  A stream of 40 KiB
+ * and more is sized by a wave per block -- the first half of the launches zipc_hip_inflate decodes it by, and less than
+ * that decode costs -- a shorter one, and any stream the block path does not show to be ZIPC_HIP_OK, by its one wave:
+ * the results are the same either way (zipc_hip_last_size_blocks tells which it was). */
 int zipc_hip_inflate_size(zipc_hip_ctx *ctx, const void *src, size_t len, int has_limit,
                           size_t limit, size_t *out_len);
 
@@ -377,9 +385,10 @@ int zipc_hip_zlib_compress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, voi
  *     ZIPC_HIP_ERR_INVALID_ARG in that stream's own result.
  *   - null ctx, d_descs or d_results, or n_streams above 0x7FFFFFFF, fails the call with ZIPC_HIP_ERR_INVALID_ARG;
  *     n_streams == 0 is ZIPC_HIP_OK and nothing is enqueued.
- *   - a stream is always sized by its one wave: there is no form by blocks, so a long stream costs what one wave takes
- *     to walk it -- 4.5 to 7 ms a MiB of text, where zipc_hip_inflate of a long stream alone goes by blocks and takes a
- *     fraction of that -- while a batch of many streams is sized in less time than it is decoded.
+ *   - in THIS form a stream is always sized by its one wave, so a long stream costs what one wave takes to walk it --
+ *     4.5 to 7 ms a MiB of text -- while a batch of many streams is sized in less time than it is decoded (DESIGN.md
+ *     section 6).  A call that holds long streams is for zipc_hip_inflate_size_blocks_batch (below), which sizes those
+ *     by a wave per block and synchronises; this form stays one launch, never synchronised.
  * The use: size the batch, read the results, lay the destinations out with dst_cap = out_len, call
  * zipc_hip_inflate_batch (INTEGRATION.md has the recipe). */
 int zipc_hip_inflate_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
@@ -394,6 +403,26 @@ int zipc_hip_inflate_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
 int zipc_hip_zlib_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
                              const zipc_hip_stream_desc *d_descs,
                              zipc_hip_stream_result *d_results, size_t n_streams);
+
+/* Sizing with the long streams of the call BY BLOCKS: descriptors, results, argument rules and the defining property of
+ * zipc_hip_inflate_size_batch / zipc_hip_zlib_size_batch, word for word -- status and out_len are what
+ * zipc_hip_inflate_batch (ZIPC_HIP_CRC_NOP) reports with dst_cap = ZIPC_HIP_MAX_STREAM_LEN, checksum is 0, no arena is
+ * written, dst_off and dst_cap are not looked at.  The one difference: the call reads the descriptors and a few counts
+ * back, so it SYNCHRONISES the context's stream (as zipc_hip_inflate_batch does from 256 KiB on), and streams of 40 KiB
+ * to 512 MiB of source -- the longest of the call, as many as the model of csrc/forms.h size_blocks_pick says pay:
+ * all of a few long streams, the few long ones among many short ones, none of thousands of equal ones -- are sized by the
+ * first half of the launches that decode a long stream (csrc/inflate.hip: block headers found, a dry run a block, the
+ * chain of the blocks' sizes) and one short walk of the stream's first 32 KiB of output, which makes the one check the
+ * dry runs leave out (a match distance against the true output position).  A stream is sized that way only where those
+ * steps show it to be ZIPC_HIP_OK; every other stream -- any error, a limit exceeded, a stream of fixed or stored
+ * blocks nobody could chain -- is sized by its one wave, which owns every message.  ZIPC_HIP_INFLATE_BLOCKS=0 keeps every
+ * stream on its one wave.  The zlib form: zipc_hip_zlib_size_batch's open and close around this path over the bodies. */
+int zipc_hip_inflate_size_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
+                                       const zipc_hip_stream_desc *d_descs,
+                                       zipc_hip_stream_result *d_results, size_t n_streams);
+int zipc_hip_zlib_size_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
+                                    const zipc_hip_stream_desc *d_descs,
+                                    zipc_hip_stream_result *d_results, size_t n_streams);
 
 /* Recode on the device: every stream of the source arena -- a raw deflate stream, a ZIP member's bytes -- is inflated
  * into its room in a MIDDLE arena, its CRC-32 taken there and compared where the descriptor expects one, and what it

@@ -25,6 +25,7 @@ ERR_HIP = 17
 ERR_INVALID_ARG = 18
 ERR_NO_DEVICE = 19
 ERR_NOMEM = 20
+BLOCKS_MIN_SRC = 40 << 10  # ZIPC_HIP_BLOCKS_MIN_SRC: from this source length one stream goes by a wave per block
 
 CRC_NOP, CRC_CRC32, CRC_ADLER32, CRC_ADLER32_RFC1950 = 0, 1, 2, 3
 LEVEL_NONE, LEVEL_FAST, LEVEL_DEFAULT, LEVEL_BEST = 0, 1, 2, 3
@@ -72,6 +73,7 @@ SYMBOLS = [
     ("zipc_hip_last_error", C.c_char_p, [_P]),
     ("zipc_hip_chain_check", C.c_int, [_P, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     ("zipc_hip_last_inflate_blocks", C.c_uint, [_P]),
+    ("zipc_hip_last_size_blocks", C.c_uint, [_P]),
     ("zipc_hip_lds_exchange_ordered", C.c_int, [_P]),
     ("zipc_hip_debug_set_slices", None, [C.c_long]),
     ("zipc_hip_debug_chain_positions", _SZ, [_SZ, _SZ]),
@@ -102,6 +104,8 @@ SYMBOLS = [
     ("zipc_hip_zlib_compress_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int]),
     ("zipc_hip_inflate_size_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_zlib_size_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
+    ("zipc_hip_inflate_size_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
+    ("zipc_hip_zlib_size_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_recode_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int]),
     ("zipc_hip_recode_many", C.c_int, [_P, _SZ, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("zipc_hip_checksum_device", C.c_int, [_P, _P, _SZ, C.c_int, C.c_int, _P]),
@@ -173,6 +177,10 @@ class Context:
     def last_inflate_blocks(self) -> int:
         """blocks the last one-stream inflate was decoded by, a wave each (0: by the stream's one wave)"""
         return int(lib().zipc_hip_last_inflate_blocks(self._h))
+
+    def last_size_blocks(self) -> int:
+        """blocks of the chains that sized streams of the last sizing call, a wave per block (0: every stream by its one wave)"""
+        return int(lib().zipc_hip_last_size_blocks(self._h))
 
     def lds_exchange_ordered(self) -> bool:
         """hash chains are built by ordered LDS exchange (the context's probe passed; include/zipc_hip.h)"""

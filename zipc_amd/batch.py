@@ -137,6 +137,23 @@ def zlib_size_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int, s
         ctx.synchronize()
 
 
+def inflate_size_blocks_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int):
+    """zipc_hip_inflate_size_blocks_batch: inflate_size_batch's results, the long streams of the call sized by a wave per
+    block (Context.last_size_blocks tells how many blocks went that way).  The call synchronises the context's stream."""
+    _sync_torch(src)
+    st = lib().zipc_hip_inflate_size_blocks_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    ctx.synchronize()
+
+
+def zlib_size_blocks_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int):
+    """zipc_hip_zlib_size_blocks_batch: the same for whole zlib streams (zlib_size_batch's results)."""
+    _sync_torch(src)
+    st = lib().zipc_hip_zlib_size_blocks_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    ctx.synchronize()
+
+
 def recode_results_from_device(t) -> np.ndarray:
     return t.cpu().numpy().view(RECODE_RESULT_DTYPE).copy()
 
@@ -222,6 +239,6 @@ def compact_descs(results: np.ndarray, descs: np.ndarray, dst_cap_of_out, limit_
 
 __all__ = ["DESC_DTYPE", "RESULT_DTYPE", "RECODE_DESC_DTYPE", "RECODE_RESULT_DTYPE", "make_descs", "make_recode_descs", "to_device",
            "results_from_device", "recode_results_from_device", "recode_batch",
-           "inflate_batch", "deflate_batch", "inflate_size_batch", "zlib_size_batch", "zlib_decompress_batch", "zlib_compress_batch", "checksum_device", "reserve",
+           "inflate_batch", "deflate_batch", "inflate_size_batch", "zlib_size_batch", "inflate_size_blocks_batch", "zlib_size_blocks_batch", "zlib_decompress_batch", "zlib_compress_batch", "checksum_device", "reserve",
            "deflate_bound", "zlib_bound",
            "uniform_layout", "compact_descs", "OK"]

@@ -22,6 +22,7 @@ using namespace zd;
 
 static_assert(sizeof(zipc_hip_stream_desc) == sizeof(StreamDesc), "desc layout");
 static_assert(sizeof(zipc_hip_stream_result) == sizeof(StreamResult), "result layout");
+static_assert(ZIPC_HIP_BLOCKS_MIN_SRC == BLOCKS_MIN_SRC, "forms.h");
 static_assert(sizeof(zipc_hip_recode_desc) == sizeof(RecodeDesc) && sizeof(RecodeDesc) == 64, "recode desc layout");
 static_assert(sizeof(zipc_hip_recode_result) == sizeof(RecodeResult) && sizeof(RecodeResult) == 32, "recode result layout");
 static_assert(ZIPC_HIP_STREAM_EXPECT_CRC32 == STREAM_EXPECT_CRC32 && ZIPC_HIP_ERR_CHECKSUM == ST_CHECKSUM, "recode constants");
@@ -305,6 +306,7 @@ void zipc_hip_destroy(zipc_hip_ctx *ctx) {
   free_buf(ctx->blocks_scratch);
   free_buf(ctx->tok_scratch);
   free_buf(ctx->descs_marked);
+  free_buf(ctx->size_descs); free_buf(ctx->size_head); free_buf(ctx->size_rest);
   free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre);
   free_buf(ctx->recode_descs); free_buf(ctx->recode_res); free_buf(ctx->recode_verdicts);
   free_buf(ctx->io_mid); free_buf(ctx->io_rdesc); free_buf(ctx->io_rres);
@@ -335,6 +337,7 @@ int zipc_hip_synchronize(zipc_hip_ctx *ctx) {
 
 const char *zipc_hip_last_error(zipc_hip_ctx *ctx) { return ctx ? ctx->last_error.c_str() : ""; }
 unsigned zipc_hip_last_inflate_blocks(zipc_hip_ctx *ctx) { return ctx ? ctx->last_inflate_blocks : 0u; }
+unsigned zipc_hip_last_size_blocks(zipc_hip_ctx *ctx) { return ctx ? ctx->last_size_blocks : 0u; }
 int zipc_hip_lds_exchange_ordered(zipc_hip_ctx *ctx) { return ctx && ctx->xchg_ordered ? 1 : 0; }
 int zipc_hip_chain_check(zipc_hip_ctx *ctx, unsigned long long *compared, unsigned long long *differences) {
   if (!ctx || !compared || !differences) return ZIPC_HIP_ERR_INVALID_ARG;
@@ -409,6 +412,12 @@ int zipc_hip_inflate_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena, cons
                                 zipc_hip_stream_result *d_results, size_t n_streams) {
   if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
   return launch_inflate_size(ctx, d_src_arena, d_descs, d_results, n_streams);
+}
+
+int zipc_hip_inflate_size_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                       zipc_hip_stream_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  return launch_inflate_size_blocks(ctx, d_src_arena, d_descs, d_results, n_streams, nullptr);
 }
 
 int zipc_hip_deflate_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
@@ -609,7 +618,8 @@ int zipc_hip_inflate(zipc_hip_ctx *ctx, const void *src, size_t len, int has_lim
   return one_stream(ctx, true, src, len, has_limit, limit, 0, crc_op, dst, dst_cap, out_len, checksum);
 }
 
-// what one host stream inflates to: a batch of one around a copy in and the result's 16 bytes back
+// what one host stream inflates to: zipc_hip_inflate_size_blocks_batch of one around a copy in and the result's 16 bytes back
+// (the descriptor is handed over with the call: nothing is read back before the path is chosen)
 int zipc_hip_inflate_size(zipc_hip_ctx *ctx, const void *src, size_t len, int has_limit, size_t limit, size_t *out_len) {
   if (!ctx || (!src && len) || !out_len) return ZIPC_HIP_ERR_INVALID_ARG;
   *out_len = 0;
@@ -623,7 +633,7 @@ int zipc_hip_inflate_size(zipc_hip_ctx *ctx, const void *src, size_t len, int ha
   d.src_len = len;
   d.limit = limit; d.flags = has_limit ? STREAM_HAS_LIMIT : 0;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->io_desc.p, &d, sizeof d, hipMemcpyHostToDevice, ctx->stream));
-  st = zipc_hip_inflate_size_batch(ctx, ctx->io_src.p, (const zipc_hip_stream_desc *)ctx->io_desc.p, (zipc_hip_stream_result *)ctx->io_res.p, 1);
+  st = launch_inflate_size_blocks(ctx, ctx->io_src.p, (const zipc_hip_stream_desc *)ctx->io_desc.p, (zipc_hip_stream_result *)ctx->io_res.p, 1, &d);
   if (st) return st;
   StreamResult r;
   HIP_TRY(ctx, hipMemcpyAsync(&r, ctx->io_res.p, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
@@ -674,6 +684,19 @@ int zipc_hip_zlib_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const z
   int st = launch_zlib_open(ctx, d_src_arena, d_descs, n_streams, 0);
   if (st) return st;
   st = zipc_hip_inflate_size_batch(ctx, d_src_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, d_results, n_streams);
+  if (st) return st;
+  return launch_zlib_close_size(ctx, d_results, n_streams);
+}
+
+// ... with the long bodies sized by blocks: the same open and close around launch_inflate_size_blocks over the body descriptors
+int zipc_hip_zlib_size_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                    zipc_hip_stream_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  ctx->last_size_blocks = 0;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = launch_zlib_open(ctx, d_src_arena, d_descs, n_streams, 0);
+  if (st) return st;
+  st = launch_inflate_size_blocks(ctx, d_src_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, d_results, n_streams, nullptr);
   if (st) return st;
   return launch_zlib_close_size(ctx, d_results, n_streams);
 }

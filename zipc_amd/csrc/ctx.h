@@ -53,6 +53,7 @@ struct zipc_hip_ctx {
   Buf stored_list;                                // inflate of one stream beyond 4 GiB: the stored blocks a walk listed
   Buf blocks_scratch, tok_scratch;                // inflate of streams by a wave per block: candidates, chains; a word per output byte
   Buf descs_marked;                               // ... a call's descriptors with those streams marked as done, for the one waves of the rest
+  Buf size_descs, size_head, size_rest;                      // sizing by blocks: the call's descriptors with no destination (dst_off 0, dst_cap the longest stream's), the heads' results and span slots, the one-wave results of the streams left
   Buf zlib_descs, zlib_pre;                       // the zlib batch forms: the descriptors the codec runs with, the container checks' verdicts (zlib.hip)
   Buf recode_descs, recode_res, recode_verdicts;  // the recode forms: the descriptors inflate, then deflate run with, their results, what is known of a stream between the steps (recode.hip)
   Buf io_mid, io_rdesc, io_rres;                  // ... of host streams: the middle arena of a sub-batch, the call's recode descriptors and results
@@ -61,6 +62,7 @@ struct zipc_hip_ctx {
   unsigned long long *chain_check_host = nullptr; // ... [0] differences, [1] positions compared in the context's first batch; [2], [3]: the same for the create-time probe (device-visible host memory)
   bool chain_checked = false;                     // ... that first batch has been seen
   uint32_t last_inflate_blocks = 0;               // blocks of the last one-stream inflate that went that way (0: it did not)
+  uint32_t last_size_blocks = 0;                  // blocks of the chains (and heads) that sized streams of the last sizing call by blocks (0: every stream by its one wave)
 
   int name_index(const char *name);
   hipEvent_t get_event();
@@ -135,6 +137,11 @@ int launch_inflate(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena
 // stream, one launch on ctx->cur
 int launch_inflate_size(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
                         size_t n_streams);
+// inflate.hip: zipc_hip_inflate_size_blocks_batch behind its argument checks: the call's long streams (forms.h size_blocks_pick)
+// by the block path's first half and a head walk, the rest by inflate_size_kernel's wave; h_descs: the caller's host copy of
+// the descriptors, or null: they are read back.  Synchronises ctx->stream unless no stream of the call is long.
+int launch_inflate_size_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                               size_t n_streams, const StreamDesc *h_descs);
 // recode.hip: zipc_hip_recode_batch behind its argument checks, and the kernels' step of zipc_hip_recode_many (a ZIPC_HIP_*
 // status): open -> inflate with its CRC-32 pass -> link -> deflate -> close on ctx->stream.  d_plain: null, or n StreamResults
 // for the many-stream pipeline; h_inflate_descs, first_of_call: launch_inflate's.  recode_reserve: its scratch for n streams,

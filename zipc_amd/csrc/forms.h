@@ -342,6 +342,60 @@ inline std::vector<size_t> inflate_blocks_groups(const StreamDesc *sds, const st
   return ends;
 }
 
+// ---------------------------------------------------------------------------------
+// sizing: streams of at least BLOCKS_MIN_SRC bytes by the block path's first half (inflate.hip inflate_size_by_blocks: find,
+// dry, chain -- and a head walk for the one check the dry runs leave out; the verdict's rule: inflate_blocks.h)
+// A stream the path takes at all.  There is no destination, so no capacity to go by: the source's length alone (dst_off and
+// dst_cap are not looked at, as in every sizing form).  A descriptor with a flag bit that is an argument error is the one
+// wave's to report, like every other error.
+inline bool size_blocks_gate(const StreamDesc &sd) {
+  return (sd.flags & ~STREAM_HAS_LIMIT) == 0 && sd.src_len >= BLOCKS_MIN_SRC && sd.src_len <= BLOCKS_MAX_SRC;
+}
+// The model's constants, measured (tools/bench_inflate_size.py --blocks, profiles/inflate_size_blocks.json), in
+// milliseconds per MiB of INPUT:
+//   the one-wave sizing kernel walks a lone stream of text at 15.6 ms a MiB of input (1 -> 16 MiB of text at `Default:
+//   6.95 -> 76.6 ms for 0.26 -> 4.73 MiB of input) and C2's 4-bit symbols at 13.2 - 13.4 (7.21 -> 115.9 ms for 0.54 -> 8.66
+//   MiB); a call's one waves run side by side, so its time is the longest stream's (64 x 1 MiB of text: 4.35 ms, one
+//   alone 6.9);
+//   this path takes 0.80 ms for its launches and read-backs whatever it is given (the intercept of both pairs of points),
+//   and then, for ONE stream, 0.43 ms a MiB of text (0.92 -> 2.83 ms: the explorers and the chain's walks of the oracle's
+//   fixed blocks, a stream's own serial part) and 0.044 - 0.067 a MiB of C2's symbols (0.83 -> 1.38 ms: dynamic blocks,
+//   found by their headers); streams side by side share everything but that serial part (8 -> 64 streams of 1 MiB of
+//   text, 1.2 -> 8.7 MiB of input: 1.17 -> 1.54 ms, 0.049 a MiB, where their one waves take 4.4).
+// So the path's cost is its fixed part, a serial part per MiB of the LONGEST stream it takes (text's 0.43 less the
+// throughput part) and a throughput part per MiB of all it takes (0.067, the largest of the figures there are); the one
+// waves are given C2's 13.2, the smallest -- of each pair the figure that favours the one waves, which need no read-back.
+constexpr double SIZE_WAVE_MS_PER_MIB = 13.2, SIZE_BLOCKS_MS_FIXED = 0.8, SIZE_BLOCKS_SERIAL_MS_PER_MIB = 0.36, SIZE_BLOCKS_MS_PER_MIB = 0.067;
+// which of a call's streams are sized by blocks, in ascending order: the model of inflate_blocks_pick over the sources --
+// the k longest streams that pass the gate, with the k that makes (the block path's fixed cost and its cost per MiB of
+// what it takes, the longest of them once more for its serial part) plus (the one-wave time of the longest stream left)
+// smallest
+inline std::vector<uint32_t> size_blocks_pick(const StreamDesc *sds, size_t n_streams) {
+  std::vector<uint32_t> fit;
+  if (n_streams > BLOCKS_MAX_STREAMS) return fit;
+  uint64_t longest_other = 0;  // (of the streams the block path does not take; one above MAX_STREAM_LEN or with a stray flag bit is refused at once)
+  for (size_t i = 0; i < n_streams; i++) {
+    if (size_blocks_gate(sds[i])) fit.push_back((uint32_t)i);
+    else if ((sds[i].flags & ~STREAM_HAS_LIMIT) == 0 && sds[i].src_len <= MAX_STREAM_LEN && sds[i].src_len > longest_other) longest_other = sds[i].src_len;
+  }
+  if (n_streams == 1) return fit;  // (one stream alone goes by blocks from BLOCKS_MIN_SRC on, as it does to be decoded: inflate_blocks_gate)
+  constexpr double MIB = 1048576.0;
+  std::sort(fit.begin(), fit.end(), [&](uint32_t x, uint32_t y) { return sds[x].src_len != sds[y].src_len ? sds[x].src_len > sds[y].src_len : x < y; });
+  size_t best_k = 0;
+  double best_ms = 0, taken_mib = 0;
+  for (size_t k = 0; k <= fit.size(); k++) {
+    const uint64_t longest_left = k < fit.size() && sds[fit[k]].src_len > longest_other ? sds[fit[k]].src_len : longest_other;
+    const double serial_mib = k ? (double)sds[fit[0]].src_len / MIB : 0.0;  // (the longest stream taken: fit is in descending order)
+    const double ms = (k ? SIZE_BLOCKS_MS_FIXED + serial_mib * SIZE_BLOCKS_SERIAL_MS_PER_MIB + taken_mib * SIZE_BLOCKS_MS_PER_MIB : 0.0) +
+                      (double)longest_left / MIB * SIZE_WAVE_MS_PER_MIB;
+    if (k == 0 || ms < best_ms) { best_ms = ms; best_k = k; }
+    if (k < fit.size()) taken_mib += (double)sds[fit[k]].src_len / MIB;
+  }
+  fit.resize(best_k);
+  std::sort(fit.begin(), fit.end());
+  return fit;
+}
+
 // the batch kernel of a call's one waves: a few streams take the form that shares the tables of blocks with one and the
 // same header (inflate.hip inflate_batch_few_kernel)
 inline bool inflate_few_streams(size_t n_streams) { return n_streams <= 256; }

@@ -43,7 +43,9 @@
 // the same wave code in two more modes -- IM_DRY walks a block for its end and size, IM_TOKEN stores its literals
 // and writes down what its matches copy -- around a search for block headers, a chain of the blocks and pointer
 // jumping over the copies.  A fourth mode, IM_SIZE, is the stream's wave with nothing stored: what a stream inflates to,
-// and whether it does, before there is a destination (inflate_size_kernel, zipc_hip_inflate_size_batch).
+// and whether it does, before there is a destination (inflate_size_kernel, zipc_hip_inflate_size_batch).  A LONG stream is
+// sized by the block path's first half instead -- find, dry, chain: the blocks' sizes added up -- with IM_SIZE's wave over its
+// first 32 KiB of output only, for the one check a dry run leaves out (inflate_size_head_kernel, launch_inflate_size_blocks).
 // The launch code is the last section (zd::launch_inflate); its rules between two launches: forms.h, inflate_blocks.h.
 #include <deque>
 
@@ -637,7 +639,10 @@ __device__ __forceinline__ Explore no_explore() {
   X.est_bits = 0;
   return X;
 }
-template <int MODE, bool MULTI = false, bool REUSE = false>
+// HEAD (with IM_SIZE): the stream's first blocks only (inflate_size_head_kernel) -- the wave stops at the first end of a
+// block at which the output has reached BLOCK_DRY_BASE bytes, or behind the final block, and returns what it found
+// (status, whether the last block it read was final, end bit, output position, in pad the blocks it walked); no result is stored.
+template <int MODE, bool MULTI = false, bool REUSE = false, bool HEAD = false>
 __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t *__restrict__ src_arena, uint8_t *__restrict__ dst_arena,
                                                  const StreamDesc &sd, const BlockStart at, StreamResult *__restrict__ result,
                                                  uint16_t *__restrict__ span_idx, uint32_t *__restrict__ tok, int crc_op,
@@ -687,6 +692,11 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
   uint32_t prev_hdr_bits = 0;
   // a block has ended (the phase says what the stream's wave would do next): the block modes stop here, or go on
   auto block_done = [&]() {
+    if constexpr (HEAD) {  // (from here on no distance can reach before the output: the blocks behind are the dry runs')
+      n_listed++;
+      if (d.status == ST_OK && d.out_pos >= BLOCK_DRY_BASE) d.phase = PH_DONE;
+      return;
+    }
     if (MODE == IM_REAL || MODE == IM_SIZE || d.status != ST_OK) return;
     if (!MULTI) { d.phase = PH_DONE; return; }
     const uint64_t end_bit = (uint64_t)d.in_word * 32u + d.boff;
@@ -948,6 +958,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
   e.end_bit = (uint64_t)d.in_word * 32u + d.boff;
   e.out_len = d.out_pos - (MODE == IM_DRY ? BLOCK_DRY_BASE : at.out_pos);
   e.pad = MODE == IM_DRY ? ck.n : left_early ? 1u : 0u;
+  if constexpr (HEAD) { e.pad = n_listed; return e; }
   if (MODE != IM_REAL && MODE != IM_SIZE) return e;
   if (writer || (MODE == IM_SIZE && lane == 0)) {
     StreamResult r;
@@ -1596,6 +1607,51 @@ __global__ void inflate_blocks_result_kernel(const BlocksJob *__restrict__ jobs,
   r.status = ST_OK; r.checksum = 0; r.out_len = jobs[j].out_len;
   results[jobs[j].stream] = r;
 }
+// ---- sizing by blocks (inflate_size_by_blocks): the head and the verdict; inflate_blocks.h has the argument
+// The head: a wave per picked stream from bit 0 and output position 0, the one-wave sizing kernel's checks (a distance
+// against the true position among them), up to the first block end at 32768 bytes and more (inflate_wave HEAD).
+// streams[j]: the stream's descriptor; heads[j]: what the wave found.  Like inflate_size_kernel it has no arena but the source.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void inflate_size_head_kernel(
+    const uint8_t *__restrict__ src_arena, const StreamDesc *__restrict__ descs, const uint32_t *__restrict__ streams,
+    BlockEnd *__restrict__ heads, uint32_t n, uint16_t *__restrict__ span_scratch) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LDS_BYTES_PER_LANE];
+  const uint32_t j = blockIdx.x;
+  if (j >= n) return;
+  BlockStart at;
+  at.bit = 0; at.out_pos = 0; at.chunk0 = 0;
+  const BlockEnd e = inflate_wave<IM_SIZE, false, false, true>(lds_raw, src_arena, nullptr, descs[streams[j]], at, nullptr,
+                                                                span_scratch + (size_t)j * SPAN_IDX_ENTRIES, nullptr, CRC_NOP);
+  if (threadIdx.x == 0) heads[j] = e;
+}
+// The verdict, a lane per stream of the group (jobs[j], heads[j]): a stream that is sized by blocks (size_blocks_verdict)
+// has its result written and sized[j] = the blocks of what sized it (the chain's, or the head's own); else sized[j] = 0
+// and its result slot is left to the one wave.
+__global__ __launch_bounds__(64) void inflate_size_verdict_kernel(const BlocksJob *__restrict__ jobs, const BlockEnd *__restrict__ heads,
+                                                                 StreamResult *__restrict__ results, uint32_t *__restrict__ sized,
+                                                                 uint32_t n_jobs) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_jobs) return;
+  const BlocksJob J = jobs[j];
+  const BlockEnd h = heads[j];
+  const FindCounts c = *J.counts;
+  const uint32_t n_blocks = c.chain_ok && c.n_blocks <= J.chain_cap ? c.n_blocks : 0u;
+  const int at = n_blocks ? size_chain_at(J.chain, n_blocks, h.end_bit, h.out_len) : SIZE_CHAIN_NONE;
+  const SizeVerdict v = size_blocks_verdict(h.status, h.final_block, h.out_len, c.chain_ok, at, c.out_len);
+  sized[j] = v.sized ? (h.final_block ? h.pad : n_blocks) : 0u;
+  if (!v.sized) return;
+  StreamResult r;
+  r.status = ST_OK; r.checksum = 0; r.out_len = v.out_len;
+  results[J.stream] = r;
+}
+// The streams of such a call that were NOT sized by blocks go through inflate_size_kernel as it is, side by side in a
+// list of their own (a second kernel around the same wave, over a marked copy as launch_inflate has one, changed the
+// registers the compiler gives inflate_size_kernel); a lane per stream then puts every result in its caller's slot.
+__global__ __launch_bounds__(64) void inflate_size_scatter_kernel(const StreamResult *__restrict__ listed, const uint32_t *__restrict__ streams,
+                                                                 StreamResult *__restrict__ results, uint32_t n) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n) results[streams[k]] = listed[k];
+}
+
 // every byte of a match takes the literal its chain of sources ends in (tok[i] after the resolve rounds; a literal's is i).
 // (Four bytes a thread -- one load of their four words, one word stored -- takes the same 0.21-0.23 ms per 64 MiB of text: the
 // kernel is its scattered byte reads.)
@@ -2089,12 +2145,196 @@ static int inflate_batch_one_wave(zipc_hip_ctx *ctx, const void *d_src_arena, vo
 // zipc_hip_inflate_size_batch behind its argument checks (ctx.h): one launch, a wave per stream, on the context's stream
 int launch_inflate_size(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
                         size_t n_streams) {
+  ctx->last_size_blocks = 0;  // (zipc_hip_last_size_blocks: every stream by its one wave)
   if (n_streams == 0) return ZIPC_HIP_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_streams * INFLATE_SCRATCH_PER_STREAM));
   ZD_LAUNCH(ctx, "inflate_size", inflate_size_kernel, dim3((unsigned)n_streams), dim3(64), 0, (const uint8_t *)d_src_arena,
             (const StreamDesc *)d_descs, (StreamResult *)d_results, (uint32_t)n_streams, (uint16_t *)ctx->inflate_scratch.p);
   HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+
+// A group of a sizing call's long streams by the block path's first half: find, dry, sort, chain (explore, sort, chain for
+// a chain that got lost) -- the launches of inflate_blocks_group in its order, over `dd`, the library's copy of the
+// descriptors with dst_off 0 and dst_cap MAX_STREAM_LEN (the chain's room is then min(limit, MAX_STREAM_LEN), and
+// dst_arena + dst_off, which IM_DRY forms and never goes through, is null) -- with the head beside them on a queue of
+// its own, and the verdict behind both.  No tok[], token run, resolve, gather or Adler kernels, no destination.
+// No IM_DRY path loads or stores through the destination: inflate_wave's literal stores, wave_copy and the strided turn's
+// are im_stores(MODE), wave_match is IM_REAL / IM_TOKEN, the queue of deferred copies is filled by IM_REAL alone (wide_turn;
+// lane_match_commit's may_queue), so the service that fills it never runs, PH_REQ_ADLER is entered with crc_adler, which is
+// IM_REAL's; span_decode's tile stores are im_stores, its loads of match sources IM_REAL (the "fly" loads) or behind a
+// count of holes that only IM_REAL raises, the token pass IM_TOKEN.
+// sized[stream]: blocks of what sized it, 0: left to the one wave.  SYNCHRONISES the context's stream.
+static int inflate_size_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, const StreamDesc *dd, StreamResult *d_results,
+                                     const StreamDesc *sds, const uint32_t *streams, size_t nj, uint32_t *sized) {
+  const uint64_t stride = tuning().explore_stride;
+  std::vector<BlocksJob> jobs(nj);
+  for (size_t j = 0; j < nj; j++) jobs[j] = blocks_job(streams[j], sds[streams[j]].src_len, stride);
+  FindCounts *d_counts;
+  BlocksJob *d_jobs;
+  // (no room for the lists, or for the heads: the streams' one waves need none)
+  if (ctx->ensure(ctx->blocks_scratch, carve_blocks_scratch(0, jobs, d_counts, d_jobs)) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }
+  carve_blocks_scratch((uintptr_t)ctx->blocks_scratch.p, jobs, d_counts, d_jobs);
+  const SizeHeadScratch hs = size_head_scratch(nj);
+  if (ctx->ensure(ctx->size_head, hs.bytes + nj * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }
+  uint8_t *hb = (uint8_t *)ctx->size_head.p;
+  BlockEnd *d_heads = (BlockEnd *)(hb + hs.heads);
+  uint32_t *d_streams = (uint32_t *)(hb + hs.streams), *d_sized = (uint32_t *)(hb + hs.bytes);
+  uint8_t *null_dst = nullptr;
+  std::vector<FindCounts> fc(nj);
+  auto read_counts = [&]() -> hipError_t {
+    const hipError_t e = hipMemcpyAsync(fc.data(), d_counts, nj * sizeof(FindCounts), hipMemcpyDeviceToHost, ctx->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
+  };
+  std::deque<std::vector<BlocksJob>> handed;
+  auto hand = [&](const std::vector<uint32_t> &which) -> hipError_t {
+    std::vector<BlocksJob> &v = handed.emplace_back();
+    for (uint32_t j : which) v.push_back(jobs[j]);
+    return hipMemcpyAsync(d_jobs, v.data(), v.size() * sizeof(BlocksJob), hipMemcpyHostToDevice, ctx->stream);
+  };
+  std::vector<size_t> at;
+  auto span_slots = [&](const std::vector<uint32_t> &which) {
+    if (ctx->ensure(ctx->inflate_scratch, blocks_span_slots(jobs, which, at)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    for (size_t k = 0; k < which.size(); k++) jobs[which[k]].span = (uint16_t *)((uint8_t *)ctx->inflate_scratch.p + at[k]);
+    return true;
+  };
+  auto widest = [&](const std::vector<uint32_t> &which, auto need) {
+    unsigned w = 1;
+    for (uint32_t j : which) { const unsigned x = (unsigned)need(jobs[j], j); if (x > w) w = x; }
+    return w;
+  };
+  std::vector<uint32_t> all(nj), alive, keep;
+  for (size_t j = 0; j < nj; j++) all[j] = (uint32_t)j;
+  alive = all;
+  const unsigned ny = (unsigned)nj;
+
+  HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, nj * sizeof(FindCounts), ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_streams, streams, nj * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  // the head depends on nothing the other steps make: on a queue beside them (every path from here goes through the join)
+  HIP_TRY(ctx, ctx->fork(2));
+  ctx->use_slice_stream(1);
+  ZD_LAUNCH(ctx, "inflate_size_head", inflate_size_head_kernel, dim3(ny), dim3(64), 0, src, dd, (const uint32_t *)d_streams, d_heads,
+            (uint32_t)nj, (uint16_t *)(hb + hs.span));
+  ctx->use_slice_stream(0);
+  auto steps = [&]() -> int {
+    HIP_TRY(ctx, hand(alive));
+    ZD_LAUNCH(ctx, "inflate_find_headers", inflate_find_headers_kernel,
+              dim3(widest(alive, [&](const BlocksJob &J, uint32_t) { return (sds[J.stream].src_len + 1023) / 1024; }), ny), dim3(256), 0, src, dd,
+              (const BlocksJob *)d_jobs);
+    ZD_LAUNCH(ctx, "inflate_find_lengths", inflate_find_lengths_kernel,
+              dim3(widest(alive, [](const BlocksJob &J, uint32_t) { return (J.first_cap + 63u) / 64u; }), ny), dim3(64), 0, src, dd,
+              (const BlocksJob *)d_jobs);
+    if (blocks_read_candidates(nj, jobs[0].cand_cap)) {
+      HIP_TRY(ctx, read_counts());
+      keep.clear();
+      for (uint32_t j : alive)
+        if (blocks_found(fc[j], jobs[j])) { jobs[j].n = fc[j].n_cand; keep.push_back(j); }
+      alive.swap(keep);
+      if (alive.empty()) return ZIPC_HIP_OK;
+    } else {
+      jobs[0].n = jobs[0].cand_cap;
+    }
+    if (!span_slots(alive)) return ZIPC_HIP_OK;
+    HIP_TRY(ctx, hand(alive));
+    const unsigned na = (unsigned)alive.size();
+    const unsigned dry_waves = widest(alive, [](const BlocksJob &J, uint32_t) { return J.n; });
+    ZD_LAUNCH(ctx, "inflate_blocks_dry", inflate_blocks_dry_kernel, dim3(dry_waves, na), dim3(64), 0, src, null_dst, dd, (const BlocksJob *)d_jobs);
+    ZD_LAUNCH(ctx, "inflate_sort_blocks", inflate_sort_blocks_kernel, dim3((dry_waves + 255u) / 256u, na), dim3(256), 0, (const BlocksJob *)d_jobs);
+    ZD_LAUNCH(ctx, "inflate_chain", inflate_chain_kernel, dim3(1, na), dim3(64), 0, src, null_dst, dd, (const BlocksJob *)d_jobs, 0);
+    HIP_TRY(ctx, read_counts());
+    std::vector<uint32_t> lost;  // streams whose chain came to a block nobody listed
+    for (uint32_t j : alive)
+      if (blocks_chained(fc[j], jobs[j]) == BLOCKS_LOST) lost.push_back(j);
+    if (!lost.empty()) {
+      for (uint32_t j : lost) blocks_explore_waves(fc[j], jobs[j], sds[jobs[j].stream].src_len, stride);
+      if (!span_slots(lost)) return ZIPC_HIP_OK;  // (their chains stay "not ok")
+      HIP_TRY(ctx, hand(lost));
+      const unsigned nl = (unsigned)lost.size();
+      ZD_LAUNCH(ctx, "inflate_explore", inflate_explore_kernel, dim3(widest(lost, [](const BlocksJob &J, uint32_t) { return J.n; }), nl), dim3(64), 0,
+                src, null_dst, dd, (const BlocksJob *)d_jobs, (uint32_t)(stride * 8u));
+      ZD_LAUNCH(ctx, "inflate_sort_blocks", inflate_sort_blocks_kernel,
+                dim3(widest(lost, [](const BlocksJob &J, uint32_t) { return (J.rec_cap + 255u) / 256u; }), nl), dim3(256), 0, (const BlocksJob *)d_jobs);
+      ZD_LAUNCH(ctx, "inflate_chain", inflate_chain_kernel, dim3(1, nl), dim3(64), 0, src, null_dst, dd, (const BlocksJob *)d_jobs, 1);
+    }
+    return ZIPC_HIP_OK;
+  };
+  const int st = steps();
+  const hipError_t je = ctx->join(2);
+  if (st != ZIPC_HIP_OK) { (void)hipStreamSynchronize(ctx->stream); return st; }
+  HIP_TRY(ctx, je);
+  // the verdict over every stream of the group: one the steps dropped has chain_ok 0 (the counts were cleared, or its
+  // chain said so) and is sized only by a head that saw the final block
+  HIP_TRY(ctx, hand(all));
+  ZD_LAUNCH(ctx, "inflate_size_verdict", inflate_size_verdict_kernel, dim3((ny + 63u) / 64u), dim3(64), 0, (const BlocksJob *)d_jobs,
+            (const BlockEnd *)d_heads, d_results, d_sized, (uint32_t)nj);
+  std::vector<uint32_t> got(nj);
+  HIP_TRY(ctx, hipMemcpyAsync(got.data(), d_sized, nj * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the lists handed to the copies go with this frame)
+  for (size_t j = 0; j < nj; j++) sized[streams[j]] = got[j];
+  return ZIPC_HIP_OK;
+}
+
+// zipc_hip_inflate_size_blocks_batch behind its argument checks (ctx.h): the long streams of the call by blocks, group by
+// group, then inflate_size_kernel's wave for every stream that was not sized that way -- any error, a limit exceeded, a
+// chain that is not chain_ok, no candidates, lists too long, no scratch to be had: that kernel owns every message, as
+// inflate_batch_kernel does for the decode.  The block path reports no error status of its own.
+// h_descs: the caller's host copy of the descriptors, or null: they are read back.  SYNCHRONISES the context's stream
+// (ZIPC_HIP_INFLATE_BLOCKS=0, or a call without a long stream: launch_inflate_size and nothing else).
+int launch_inflate_size_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                               size_t n_streams, const StreamDesc *h_descs) {
+  ctx->last_size_blocks = 0;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!tuning().inflate_blocks || n_streams > BLOCKS_MAX_STREAMS) return launch_inflate_size(ctx, d_src_arena, d_descs, d_results, n_streams);
+  std::vector<StreamDesc> sds;
+  if (h_descs) {
+    sds.assign(h_descs, h_descs + n_streams);
+  } else {
+    sds.resize(n_streams);
+    HIP_TRY(ctx, hipMemcpyAsync(sds.data(), d_descs, n_streams * sizeof(StreamDesc), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  const std::vector<uint32_t> picked = size_blocks_pick(sds.data(), n_streams);
+  if (picked.empty()) return launch_inflate_size(ctx, d_src_arena, d_descs, d_results, n_streams);
+  // the descriptors every kernel of this call runs with: sizing is "dst_cap = MAX_STREAM_LEN", and the caller's dst_off
+  // and dst_cap are not looked at
+  for (StreamDesc &sd : sds) { sd.dst_off = 0; sd.dst_cap = MAX_STREAM_LEN; }
+  HIP_TRY(ctx, ctx->ensure(ctx->size_descs, n_streams * sizeof(StreamDesc)));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->size_descs.p, sds.data(), n_streams * sizeof(StreamDesc), hipMemcpyHostToDevice, ctx->stream));
+  std::vector<uint32_t> sized(n_streams, 0);
+  size_t begin = 0;
+  for (size_t end : size_blocks_groups(sds.data(), picked, tuning().explore_stride)) {
+    const int st = inflate_size_blocks_group(ctx, (const uint8_t *)d_src_arena, (const StreamDesc *)ctx->size_descs.p, (StreamResult *)d_results,
+                                             sds.data(), picked.data() + begin, end - begin, sized.data());
+    if (st) return st;
+    begin = end;
+  }
+  // the others by their one waves: their descriptors in a list of their own (the handled streams are left out of it the
+  // way launch_inflate marks them in its copy), their results put in their slots behind the kernel
+  std::vector<uint32_t> rest;
+  for (size_t i = 0; i < n_streams; i++) {
+    if (sized[i]) ctx->last_size_blocks += sized[i];
+    else rest.push_back((uint32_t)i);
+  }
+  const size_t nr = rest.size();
+  if (nr == 0) return ZIPC_HIP_OK;
+  std::vector<StreamDesc> rest_descs(nr);
+  for (size_t k = 0; k < nr; k++) rest_descs[k] = sds[rest[k]];
+  const size_t idx_at = align_up(nr * sizeof(StreamResult), 256);
+  HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, nr * INFLATE_SCRATCH_PER_STREAM));
+  HIP_TRY(ctx, ctx->ensure(ctx->descs_marked, nr * sizeof(StreamDesc)));
+  HIP_TRY(ctx, ctx->ensure(ctx->size_rest, idx_at + nr * sizeof(uint32_t)));
+  StreamResult *d_listed = (StreamResult *)ctx->size_rest.p;
+  uint32_t *d_idx = (uint32_t *)((uint8_t *)ctx->size_rest.p + idx_at);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->descs_marked.p, rest_descs.data(), nr * sizeof(StreamDesc), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_idx, rest.data(), nr * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  ZD_LAUNCH(ctx, "inflate_size", inflate_size_kernel, dim3((unsigned)nr), dim3(64), 0, (const uint8_t *)d_src_arena,
+            (const StreamDesc *)ctx->descs_marked.p, d_listed, (uint32_t)nr, (uint16_t *)ctx->inflate_scratch.p);
+  ZD_LAUNCH(ctx, "inflate_size_scatter", inflate_size_scatter_kernel, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, (const StreamResult *)d_listed,
+            (const uint32_t *)d_idx, (StreamResult *)d_results, (uint32_t)nr);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the lists go with this frame)
   return ZIPC_HIP_OK;
 }
 

@@ -150,6 +150,72 @@ inline size_t blocks_adler_sums(const std::vector<FindCounts> &fc, const std::ve
   return blocks_shares(which, 12, [&](uint32_t j) { return fc[j].n_chunks; }, at) + 12;
 }
 
+// ---- sizing by blocks (inflate.hip inflate_size_by_blocks): find, dry, chain as above, no token run, and a HEAD
+// Why the answer is exact.  The chain starts at bit 0 and only steps from a block's true end bit to a record that begins at
+// exactly that bit; every record is a real dry decode from its bit with every check of the decoder except the distance
+// against the output position; the chain applies the limit and MAX_STREAM_LEN to the running sum.  So chain_ok means: every
+// block decodes, they end in a final block, the sizes add up to a length within the limit -- all but "no distance reaches
+// before the output".  A distance is at most 32768, so that can only fail in a block whose first byte lies below 32768:
+// the head, one wave from bit 0 and position 0 with the one-wave sizing kernel's checks (the true position), walks exactly
+// those blocks.  It stops at the first block end where the position has reached 32768, or behind the final block.
+// (A block that inflates past 32 bits of length is no wrapped BlockEnd::out_len: the dry run's and the head's room is
+// MAX_STREAM_LEN < 2^32 bytes, beyond which both report ST_DST_TOO_SMALL / ST_SIZE_EXCEEDED, never ST_OK.)
+// Whatever is not shown to be OK that way is left to the stream's one wave, which owns every message.
+//
+// what the chain holds at the head's end: no block that starts at that bit / one, at the head's output position / one, elsewhere
+enum SizeChainAt : int { SIZE_CHAIN_NONE = 0, SIZE_CHAIN_SAME = 1, SIZE_CHAIN_OTHER_POS = 2 };
+ZD_HD int size_chain_at(const BlockStart *chain, uint32_t n_blocks, uint64_t bit, uint64_t out_pos) {
+  uint32_t lo = 0, hi = n_blocks;  // (the chain's blocks are in stream order: the first that starts at or behind `bit`)
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (chain[mid].bit < bit) lo = mid + 1u;
+    else hi = mid;
+  }
+  if (lo >= n_blocks || chain[lo].bit != bit) return SIZE_CHAIN_NONE;
+  return (uint64_t)chain[lo].out_pos == out_pos ? SIZE_CHAIN_SAME : SIZE_CHAIN_OTHER_POS;
+}
+// The verdict: sized by blocks, with this length, if and only if the head is OK and either saw the final block (its own
+// position is the size) or the chain is chain_ok and holds a block that starts exactly at the head's end bit with exactly
+// the head's output position (the two walks agree where they meet: that comparison is free)
+struct SizeVerdict { uint32_t sized; uint64_t out_len; };
+ZD_HD SizeVerdict size_blocks_verdict(uint32_t head_status, uint32_t head_final, uint64_t head_out, uint32_t chain_ok, int chain_at,
+                                      uint64_t chain_out) {
+  SizeVerdict v;
+  v.sized = 0; v.out_len = 0;
+  if (head_status != ST_OK) return v;
+  if (head_final != 0u) { v.sized = 1; v.out_len = head_out; return v; }
+  if (chain_ok != 0u && chain_at == SIZE_CHAIN_SAME) { v.sized = 1; v.out_len = chain_out; }
+  return v;
+}
+// ctx->size_head of a group of nj streams: every head's BlockEnd | the streams' indices | the heads' span index slots
+struct SizeHeadScratch { size_t heads, streams, span, bytes; };
+inline SizeHeadScratch size_head_scratch(size_t nj) {
+  SizeHeadScratch s;
+  s.heads = 0;
+  s.streams = align_up(nj * sizeof(BlockEnd), 256);
+  s.span = s.streams + align_up(nj * sizeof(uint32_t), 256);
+  s.bytes = s.span + nj * INFLATE_SCRATCH_PER_STREAM;
+  return s;
+}
+// The picked streams in groups that go through the steps side by side: there is no tok[], so a group is bounded only by
+// the lists of carve_blocks_scratch -- ends[g] is one past group g's last entry of picked
+constexpr size_t SIZE_BLOCKS_SCRATCH_BUDGET = (size_t)1 << 30;
+inline std::vector<size_t> size_blocks_groups(const StreamDesc *sds, const std::vector<uint32_t> &picked, uint64_t explore_stride) {
+  std::vector<size_t> ends;
+  size_t group_bytes = 0;
+  for (size_t j = 0; j < picked.size(); j++) {
+    std::vector<BlocksJob> one(1, blocks_job(picked[j], sds[picked[j]].src_len, explore_stride));
+    FindCounts *c;
+    BlocksJob *l;
+    const size_t need = (size_t)carve_blocks_scratch(0, one, c, l);
+    const size_t begin = ends.empty() ? 0 : ends.back();
+    if (j > begin && group_bytes + need > SIZE_BLOCKS_SCRATCH_BUDGET) { ends.push_back(j); group_bytes = 0; }
+    group_bytes += need;
+  }
+  if (!picked.empty()) ends.push_back(picked.size());
+  return ends;
+}
+
 // ---- the token run
 // follow: sources written down as what they are copies of -- inflate_span.h -- cost the token run 0.2-0.4 ms a block and a
 // wave per block instead of one per interval, and save the resolve rounds of a long stream more: with 256 hops a

@@ -152,6 +152,19 @@ Adler_32::t Adler_32::string(const std::string &s, std::size_t start, std::size_
 static int inflate_raw(const char *p, std::size_t n, std::optional<std::size_t> decompressed_size, int crc_op,
                        std::string &out, uint32 &checksum) {
   std::size_t cap = decompressed_size ? *decompressed_size : (3 * n < 1024 ? 1024 : 3 * n);
+  if (!decompressed_size && n >= ZIPC_HIP_BLOCKS_MIN_SRC) {
+    // a long stream is sized first (by a wave per block: less than decoding it costs) and decoded once at its exact size.
+    // A status other than OK is the answer: it is by definition what zipc_hip_inflate would say.  (A stream beyond the
+    // longest the sizing forms take is left to the loop.)
+    std::size_t size = 0;
+    const int st = zipc_hip_inflate_size(context(), p, n, 0, 0, &size);
+    if (st == ZIPC_HIP_OK) cap = size;
+    else if (st != ZIPC_HIP_ERR_DST_TOO_SMALL) {
+      throw_if_library_failure(st);
+      out.clear();
+      return st;
+    }
+  }
   for (;;) {
     out.resize(cap);
     std::size_t out_len = 0;

@@ -131,6 +131,18 @@ def _inflate(s, decompressed_size, start, length, crc_op, ctx):
     # without a limit the reference starts at 3x the input and doubles
     # (zipc_deflate.ml:553, Buf.grow :27-38); same policy for the device buffer
     cap = decompressed_size if has_limit else max(3 * n, 1024)
+    if not has_limit and n >= _lib.BLOCKS_MIN_SRC:
+        # a long stream is sized first (by a wave per block: less than decoding it costs) and decoded once at its exact
+        # size.  A status other than OK is the answer: it is by definition what zipc_hip_inflate would say.  (A stream
+        # beyond the longest the sizing forms take is left to the loop.)
+        size = C.c_size_t()
+        st = lib().zipc_hip_inflate_size(ctx.handle, data, n, 0, 0, C.byref(size))
+        if st == OK:
+            cap = size.value
+        elif st != ERR_DST_TOO_SMALL:
+            if st in (_lib.ERR_HIP, _lib.ERR_INVALID_ARG, _lib.ERR_NO_DEVICE, _lib.ERR_NOMEM):
+                ctx.check(st)
+            return Error(_message(st))
     while True:
         dst = C.create_string_buffer(max(cap, 1))
         out_len, crc = C.c_size_t(), C.c_uint32()
