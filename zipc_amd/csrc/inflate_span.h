@@ -89,7 +89,7 @@ struct SpanSym {
   uint32_t tot;     // bits
   uint32_t outlen;  // bytes: 1 (a literal), 2 (two literals), or the match length
   uint32_t val;     // literal byte, or the match distance
-  uint32_t val2;    // the second literal
+  uint32_t val2;    // the second literal in the low byte; bit 8: is_lit once more, for the decode loop (see there)
   bool is_lit, stop;
 };
 // The general form: codes longer than the tables' bits, end of block, anything invalid (their
@@ -126,6 +126,7 @@ ZD_HD SpanSym span_symbol_slow(uint32_t xlo, uint32_t xhi, const LaneLds &L, int
     r.tot = b1;
     r.outlen = 1;
     r.val = lv;
+    r.val2 = 256u;
     return r;
   }
   const uint32_t x2 = funnel32(xhi, xlo, b1);  // b1 <= 20
@@ -174,10 +175,10 @@ ZD_WV SpanSym span_symbol(bool act, uint32_t xlo, uint32_t xhi, const LaneLds &L
   r.val2 = 0;
   if (FULL) {
     r.val = is_lit ? base : ((e2 >> 9) & 0xFFFFu) + bit_field(x2, e2, (e2 >> 5) & 15u);
-    r.val2 = (e >> 23) & 255u;
+    r.val2 = e >> 23;  // (bit 8 is the entry's bit 31: a literal)
   }
   // (a divergent branch is skipped by the whole wave when no lane takes it: nearly always here)
-  if (act && (e == 0u || (!is_lit && e2 == 0u))) r = span_symbol_slow(xlo, xhi, L, lit_max_sym, dist_max_sym);
+  if (act & ((e == 0u) | (!is_lit & (e2 == 0u)))) r = span_symbol_slow(xlo, xhi, L, lit_max_sym, dist_max_sym);
   return r;
 }
 
@@ -191,6 +192,7 @@ struct SpanEnv {
   uint32_t *ring;
   uint32_t max_word;   // words of input that may be loaded 16 bytes at a time
   int lane;
+  uint32_t lane_x;     // lane * 4 ^ SPAN_RING / 2 * 256: see span_ring_next
 };
 struct SpanReader {
   uint32_t w0, w1, w2, w3;  // input words cw .. cw + 3
@@ -232,17 +234,24 @@ ZD_WV void span_reader_refill(SpanReader &R, const SpanEnv &E, bool active) {
     R.has_pend = 1;
   }
 }
-// a step may cross two word boundaries
-ZD_WV bool span_can_step(const SpanReader &R) { return R.cw + 6u <= R.wr; }
+// a step may cross two word boundaries (wr is 12 at least, and changes at the refill points only: the right side is
+// computed once per group of steps)
+ZD_WV bool span_can_step(const SpanReader &R) { return R.cw <= R.wr - 6u; }
+// The ring's word cw + 4 of this lane.  Its place in bytes is ((cw + 4) & 7) * 256 + lane * 4; adding 4 to a number taken
+// modulo 8 flips its bit 2, and the lane's part lies below 256: a shift and ONE three-input bit operation, where the
+// index form compiled to three instructions in every step of both phases (round 7, from the assembly).
+ZD_WV uint32_t span_ring_next(const SpanEnv &E, uint32_t cw) {
+  const uint32_t at = ((cw << 8) & ((SPAN_RING - 1) << 8)) ^ E.lane_x;
+  return *(const uint32_t *)((const uint8_t *)E.ring + at);
+}
 ZD_WV void span_peek(const SpanReader &R, uint32_t p, uint32_t &xlo, uint32_t &xhi) {
   xlo = funnel32(R.w1, R.w0, p);
   xhi = funnel32(R.w2, R.w1, p);
 }
 ZD_WV void span_advance(SpanReader &R, const SpanEnv &E, uint32_t p) {  // the position is now p; every lane calls this
-  const uint32_t *r = E.ring + (uint32_t)E.lane;
   const uint32_t ncw = p >> 5;
   const bool s1 = ncw != R.cw;  // (nearly every step some lane crosses a word: no branch around this)
-  const uint32_t nx = r[((R.cw + 4u) & (SPAN_RING - 1)) * 64u];
+  const uint32_t nx = span_ring_next(E, R.cw);
   R.w0 = s1 ? R.w1 : R.w0;
   R.w1 = s1 ? R.w2 : R.w1;
   R.w2 = s1 ? R.w3 : R.w2;
@@ -252,7 +261,7 @@ ZD_WV void span_advance(SpanReader &R, const SpanEnv &E, uint32_t p) {  // the p
   // versions of the words alive across it: three register moves in every step of every lane (round 6, from the assembly)
   if (wv::any(ncw != R.cw)) {
     const bool s2 = ncw != R.cw;
-    const uint32_t nx2 = r[((R.cw + 4u) & (SPAN_RING - 1)) * 64u];
+    const uint32_t nx2 = span_ring_next(E, R.cw);
     R.w0 = s2 ? R.w1 : R.w0;
     R.w1 = s2 ? R.w2 : R.w1;
     R.w2 = s2 ? R.w3 : R.w2;
@@ -533,6 +542,7 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
   E.ring = (uint32_t *)(L.x + SPAN_RING_OFF);
   E.max_word = max_word;
   E.lane = lane;
+  E.lane_x = ((uint32_t)lane << 2) ^ ((SPAN_RING / 2) << 8);
   uint8_t *tile = L.x + SPAN_TILE_OFF;
   uint16_t *lidx = (uint16_t *)tile;  // phase A's index: in the tile's place (SPAN_IDX_ENTRIES u16) while no tile is being made
   uint32_t *mbits = (uint32_t *)(L.x + SPAN_BITS_OFF);
@@ -733,7 +743,7 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
     span_reader_start(R, E, p);
     wv::sync();
     ZD_SPAN_PH(2);
-    uint32_t err = 0;
+    bool bad_any = false;
     const uint8_t *gbase = dst + out_pos;  // the tile's place in the output; gbase[-n] is final for every n >= 1
     // A match of 4 to 8 bytes whose source lies wholly before the tile (on the configs' data: most)
     // is requested from memory the moment it is decoded and lands SPAN_FLY steps later, when the
@@ -756,6 +766,11 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
     // reader's first words come by global loads too: the compiler's count of them is merged into the loop's, and every
     // group's first peek waited for vmcnt(0).  The test at the bottom, and the reader's words made to land here, once a tile:
     // the landings wait for exactly their own two loads (vmcnt(7), vmcnt(6)).)
+    // (round 7, from the assembly: the kernel holds more wave-uniform values than there are scalar registers, and of all of
+    // them the register allocator parked `dst` in lanes of a vector register -- every step read it back with two
+    // v_readlane_b32 and five wait states before its loads.  A value born here, whose whole life is this loop, stays in
+    // scalar registers.)
+    const wv::GlobalBase far_base = wv::global_base(dst);
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(R.w0), "+v"(R.w1), "+v"(R.w2), "+v"(R.w3));  // (an operand of an asm has landed; a bare s_waitcnt the loads are moved behind)
 #endif
@@ -767,30 +782,37 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
         uint32_t xlo, xhi;
         span_peek(R, p, xlo, xhi);
         const SpanSym s = span_symbol<true>(act, xlo, xhi, L, lit_max, dist_max);
+        // (a flag that comes out of span_symbol's rare branch in a vector register costs three instructions to read back;
+        // a bit of a word that comes out of it anyway costs the compare)
+        const bool s_is_lit = s.val2 > 255u;
         const uint32_t o2 = o + s.outlen;
         // what the plain decoder must see for itself: a stop, more bytes than phase A counted, a
         // distance that reaches before the output (zd.ml:614)
-        const bool bad = act && (s.stop || o2 > o_end || (!s.is_lit && s.val > out_pos + o));
-        const bool good = act && !bad;
+        // (round 7, from the assembly.  These flags are lane masks in scalar registers, and `&` and `|` between them are one
+        // scalar instruction each; written with && and || every one of them became a branch around the next compare -- a dozen
+        // saves and restores of the exec mask in every step, and the test of `act` made twice.  What a lane met is one more
+        // mask, or-ed by the scalar unit; it was a select per step.)
+        const bool bad = act & (s.stop | (o2 > o_end) | (!s_is_lit & (s.val > out_pos + o)));
+        const bool good = act & !bad;
         stop_p = bad ? 0u : stop_p;
-        err = bad ? 1u : err;
-        const bool is_match = good && !s.is_lit;
-        const bool fly = MODE == IM_REAL && is_match && s.outlen - 4u <= 4u && s.val >= o2;
-        if (im_stores(MODE) && good && s.is_lit) {
+        bad_any |= bad;
+        const bool is_match = good & !s_is_lit;
+        const bool fly = MODE == IM_REAL && (is_match & (s.outlen - 4u <= 4u) & (s.val >= o2));
+        if (im_stores(MODE) && (good & s_is_lit)) {
           tile[o] = (uint8_t)s.val;
           if (s.outlen == 2u) tile[o + 1u] = (uint8_t)s.val2;
         }
         if (MODE == IM_REAL) {
           const uint32_t goff = fly ? out_pos + o - s.val : 0u;  // (the output has 8 bytes: checked above)
-          f_a[u] = load_u32_le(dst + goff);
-          f_b[u] = load_u32_le(dst + (goff + (fly ? s.outlen - 4u : 0u)));
+          f_a[u] = wv::load_u32(far_base, goff);
+          f_b[u] = wv::load_u32(far_base, goff + (fly ? s.outlen - 4u : 0u));
           f_meta[u] = fly ? (o + 1u) | (s.outlen << 16) : 0u;
-          nh += is_match && !fly ? 1u : 0u;
-          if (is_match && !fly) {
+          nh += (is_match & !fly) ? 1u : 0u;
+          if (is_match & !fly) {
             store_u16_le(tile + o, (uint16_t)(s.val - 1u));
             tile[o + 2u] = (uint8_t)(s.outlen - 3u);
             span_bits_set(mbits, o, s.outlen);
-            if (s.val >= o2 && s.outlen <= SPAN_LONG) has_far = 1;  // (a hole the pass over far sources is for)
+            if ((s.val >= o2) & (s.outlen <= SPAN_LONG)) has_far = 1;  // (a hole the pass over far sources is for)
           }
         } else if (MODE == IM_TOKEN) {
           if (is_match) {  // (recorded like a hole: a tile that is refused below must leave nothing behind)
@@ -809,6 +831,7 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
       for (int u = 0; u < SPAN_FLY; u++) span_land(tile, f_meta[u], f_a[u], f_b[u]);
     }
     // both phases must have walked the same symbols
+    uint32_t err = bad_any ? 1u : 0u;
     if (mine && err == 0u) {
       if (o != o_end) err = 1;
       if (p != (ent + 1u == n_valid ? p_end : base + (ent + 1u) * SPAN_G + next_epd)) err = 1;

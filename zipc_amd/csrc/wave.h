@@ -60,10 +60,35 @@ __device__ __forceinline__ void store_quad(uint8_t *p, const Quad &q) {
   v.x = q.x; v.y = q.y; v.z = q.z; v.w = q.w;
   store16_unaligned(p, v);
 }
+// A wave-uniform pointer into global memory that is in scalar registers from here on, and the 4 bytes (any alignment) at
+// a lane's offset from it: global_load_dword v, v_off, s[base].  For a loop that loads in every step -- a kernel with
+// more uniform values than scalar registers keeps some in lanes of a vector register, and which ones is not the
+// source's to say, except so: a value that is an asm's result begins its life there.
+struct GlobalBase { const __attribute__((address_space(1))) uint8_t *p; };
+__device__ __forceinline__ GlobalBase global_base(const uint8_t *p) {
+  uint64_t a = (uint64_t)p;
+  asm volatile("" : "+s"(a));
+  GlobalBase b;
+  b.p = (const __attribute__((address_space(1))) uint8_t *)a;
+  return b;
+}
+__device__ __forceinline__ uint32_t load_u32(const GlobalBase &b, uint32_t off) {
+  typedef uint32_t __attribute__((aligned(1), may_alias)) u32u;
+  return *(const __attribute__((address_space(1))) u32u *)(b.p + off);
+}
 
 }  // namespace wv
 }  // namespace zd
 
 #else
 #include "wave_emu.h"  // tests/host_sim (test tooling): the same names on coroutines
+
+namespace zd {
+namespace wv {
+// global_base / load_u32 above in plain C++ (no lanes meet here: a pointer and a load of 4 bytes at any alignment)
+struct GlobalBase { const uint8_t *p; };
+inline GlobalBase global_base(const uint8_t *p) { return GlobalBase{p}; }
+inline uint32_t load_u32(const GlobalBase &b, uint32_t off) { return load_u32_le(b.p + off); }
+}  // namespace wv
+}  // namespace zd
 #endif
