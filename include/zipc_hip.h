@@ -502,6 +502,23 @@ int zipc_hip_debug_chain_links(zipc_hip_ctx *ctx, const void *d_src_arena, const
                                size_t n_streams, size_t max_src_len, size_t total_src_len, int which, void *d_links,
                                size_t links_cap, void *d_pos_base);
 
+/* Tests only: the match finder's tables of a batch of device-resident streams.  Runs deflate_offsets, lz_chain (the
+ * kernel that orders equal hashes itself) and lz_match and nothing else, lz_match launched exactly as a deflate call of
+ * this shape at `level` (1..3) launches it, but with match_form (0: the walk chosen per tile, 1 / 2: always the first /
+ * second form) and tiles_per_group (0: by the grid) in place of ZIPC_HIP_MATCH_FORM and ZIPC_HIP_MATCH_TILES_PER_GROUP,
+ * which are read once per process.  Copied out: d_match and d_snap (records_cap 32-bit slots each, at least
+ * zipc_hip_debug_chain_positions(n_streams, total_src_len)), d_snap_used (n_streams 32-bit words) and d_pos_base
+ * (n_streams 64-bit words: every stream's first slot).  Position p of stream i is slot pos_base[i] + p: match holds the
+ * best of the first K chain candidates as dist << 9 | len (0: none), with bit 31 set where the best of the first K / 4
+ * is another one, which is then in snap; snap_used[i] is 1 iff stream i has such a position.  Both tables are filled
+ * with ZIPC_HIP_DEBUG_MATCH_POISON before the kernels run, so a slot nobody wrote shows.  The batch must fit one pass
+ * (8 GiB of source).  tests/test_gpu_match_records.py holds every record to a serial find_backref. */
+#define ZIPC_HIP_DEBUG_MATCH_POISON 0x5A5A5A5Au
+int zipc_hip_debug_match_records(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                 size_t n_streams, size_t max_src_len, size_t total_src_len, int level, int match_form,
+                                 long tiles_per_group, void *d_match, void *d_snap, size_t records_cap, void *d_snap_used,
+                                 void *d_pos_base);
+
 /* grow the context scratch up front (keeps hipMalloc out of timed regions) */
 int zipc_hip_reserve(zipc_hip_ctx *ctx, size_t n_streams, size_t max_src_len,
                      size_t total_src_len);

@@ -5,7 +5,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libhost_sim.so")
-SRCS = ["sim_inflate.cpp", "sim_deflate.cpp", "sim_chain.cpp", "sim_forms.cpp", "sim_adler.cpp", "sim_many.cpp"]
+SRCS = ["sim_inflate.cpp", "sim_deflate.cpp", "sim_chain.cpp", "sim_forms.cpp", "sim_adler.cpp", "sim_many.cpp", "sim_match.cpp"]
 
 
 def lib():
@@ -68,7 +68,21 @@ def _bind(L):
     L.sim_resolve_grid.argtypes = [C.c_int, C.c_uint32]
     L.sim_blocks_shares.restype = None
     L.sim_blocks_shares.argtypes = [u32p, u32p, C.c_uint64, u64p, u64p, u64p]
-    return bind_many(bind_adler(L))
+    L.sim_match_lane_position.restype = None
+    L.sim_match_lane_position.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    return bind_match(bind_many(bind_adler(L)))
+
+
+def bind_match(L):
+    """sim_match.cpp's reference (a library of its top half alone has no other entry points: the mutants of
+    tests/test_match_rules.py)"""
+    L.sim_match_hash4.restype = C.c_uint32
+    L.sim_match_hash4.argtypes = [C.c_char_p]
+    L.sim_match_reference.restype = None
+    L.sim_match_reference.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.sim_match_parse_reads.restype = None
+    L.sim_match_parse_reads.argtypes = [C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    return L
 
 
 def bind_many(L):
@@ -288,3 +302,51 @@ def many_plan(L, op, src_len, dst_cap, limit=None, mid_cap=None, expect_crc32=No
         out["rdescs"] = [dict(zip(RECODE_DESC_FIELDS, rd[9 * i:9 * i + 9])) for i in range(n)]
         out["inflate_descs"] = [tuple(ind[7 * i:7 * i + 7]) for i in range(n)]
     return out
+
+
+# ---- sim_match.cpp: the serial reference of the match finder, and deflate_lane.h's lz_match_position beside it
+MATCH_LEVELS = {1: (4, 1, 4), 2: (128, 32, 8), 3: (4096, 1024, 32)}  # level -> (K, Kq, good_match): level_params zd.ml:754-764
+MATCH_SLACK = 512  # zero bytes behind a stream's copy: a mutant that drops the stream-end cap reads up to 258 of them
+
+
+def _padded(data):
+    import numpy as np
+
+    buf = np.zeros(len(data) + MATCH_SLACK, np.uint8)
+    buf[:len(data)] = np.frombuffer(data, np.uint8)
+    return buf
+
+
+def match_reference(L, data, level):
+    """sim_match_reference -> (best, first): uint32 arrays over the positions 0 .. len - 4 (empty below 4 bytes)"""
+    import numpy as np
+
+    K, Kq, _ = MATCH_LEVELS[level]
+    n = max(len(data) - 3, 0)
+    best, first = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    buf = _padded(data)
+    L.sim_match_reference(buf.ctypes.data, len(data), K, Kq, best.ctypes.data, first.ctypes.data)
+    return best, first
+
+
+def match_lane_position(L, data, level):
+    """deflate_lane.h lz_match_position at every position, over sim_chain_serial's links -> (best, first)"""
+    import numpy as np
+
+    K, Kq, _ = MATCH_LEVELS[level]
+    n = max(len(data) - 3, 0)
+    best, first = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    links = np.zeros(len(data) + 8, np.uint16)
+    buf = _padded(data)
+    L.sim_chain_serial(buf.ctypes.data_as(C.c_char_p), len(data), links.ctypes.data)
+    L.sim_match_lane_position(buf.ctypes.data, len(data), links.ctypes.data, K, Kq, best.ctypes.data, first.ctypes.data)
+    return best, first
+
+
+def match_parse_reads(L, length, level, best, first):
+    """which record the lazy parse reads at every position (0 none, 1 best, 2 first, 3 comes by and reads neither)"""
+    import numpy as np
+
+    read = np.zeros(max(length - 3, 0), np.uint8)
+    L.sim_match_parse_reads(length, MATCH_LEVELS[level][2], best.ctypes.data, first.ctypes.data, read.ctypes.data)
+    return read

@@ -189,6 +189,31 @@ def debug_chain_links(ctx: Context, src, descs_dev, n_streams: int, max_src_len:
     return links, base
 
 
+MATCH_POISON = 0x5A5A5A5A  # include/zipc_hip.h ZIPC_HIP_DEBUG_MATCH_POISON
+
+
+def debug_match_records(ctx: Context, src, descs_dev, n_streams: int, max_src_len: int, total_src_len: int, level: int,
+                        match_form: int = 0, tiles_per_group: int = 0):
+    """Tests only (include/zipc_hip.h zipc_hip_debug_match_records): lz_match's tables of a device-resident batch after
+    deflate_offsets, lz_chain and lz_match alone, lz_match launched as a deflate call of this shape launches it under
+    that match_form / tiles_per_group: (match, snap, snap_used, pos_base) as int32, int32, int32 and int64 cuda tensors;
+    slots nobody wrote hold MATCH_POISON."""
+    import torch
+
+    _sync_torch(src)
+    cap = int(lib().zipc_hip_debug_chain_positions(n_streams, total_src_len))
+    match = torch.empty(cap, dtype=torch.int32, device=src.device)
+    snap = torch.empty(cap, dtype=torch.int32, device=src.device)
+    used = torch.empty(n_streams, dtype=torch.int32, device=src.device)
+    base = torch.empty(n_streams, dtype=torch.int64, device=src.device)
+    torch.cuda.current_stream(src.device).synchronize()
+    ctx.check(lib().zipc_hip_debug_match_records(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), n_streams, max_src_len,
+                                                 total_src_len, level, match_form, tiles_per_group, match.data_ptr(),
+                                                 snap.data_ptr(), cap, used.data_ptr(), base.data_ptr()))
+    ctx.synchronize()
+    return match, snap, used, base
+
+
 def checksum_device(ctx: Context, buf, want_crc32=True, want_adler32=True):
     """(crc32, adler32) of a uint8 cuda tensor, computed on the device."""
     import torch

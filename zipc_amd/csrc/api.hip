@@ -454,6 +454,20 @@ int zipc_hip_debug_chain_links(zipc_hip_ctx *ctx, const void *d_src_arena, const
   return ZIPC_HIP_OK;
 }
 
+int zipc_hip_debug_match_records(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, size_t n_streams,
+                                 size_t max_src_len, size_t total_src_len, int level, int match_form, long tiles_per_group,
+                                 void *d_match, void *d_snap, size_t records_cap, void *d_snap_used, void *d_pos_base) {
+  if (!ctx || !d_descs || !d_match || !d_snap || !d_snap_used || !d_pos_base || level < 1 || level > 3 || match_form < 0 || match_form > 2 ||
+      tiles_per_group < 0 || n_streams == 0 || n_streams > 0x7FFFFFFFull || max_src_len > MAX_STREAM_LEN)
+    return ZIPC_HIP_ERR_INVALID_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->ensure(ctx->deflate_scratch, deflate_scratch_bytes(n_streams, max_src_len, total_src_len, level, zd::tuning())));
+  HIP_TRY(ctx, zd::debug_match_records(ctx, (const uint8_t *)d_src_arena, (const StreamDesc *)d_descs, n_streams, max_src_len, total_src_len,
+                                       level, match_form, tiles_per_group, (uint32_t *)d_match, (uint32_t *)d_snap, records_cap,
+                                       (uint32_t *)d_snap_used, (uint64_t *)d_pos_base));
+  return ZIPC_HIP_OK;
+}
+
 int zipc_hip_reserve(zipc_hip_ctx *ctx, size_t n_streams, size_t max_src_len, size_t total_src_len) {
   if (!ctx) return ZIPC_HIP_ERR_INVALID_ARG;
   HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -123,6 +123,11 @@ bool xchg_order_probe(zipc_hip_ctx *ctx);
 hipError_t debug_chain_links(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *d_descs, size_t n, size_t max_src_len,
                              size_t total_src_len, int which, uint16_t *d_links, size_t links_cap, uint64_t *d_pos_base);
 size_t debug_chain_positions(size_t n, size_t total_src_len);
+// deflate.hip (tests): lz_match's tables of a batch after deflate_offsets, lz_chain_kernel and lz_match alone, the latter
+// launched as the pipeline launches it under that match_form and tiles_per_group
+hipError_t debug_match_records(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *d_descs, size_t n, size_t max_src_len,
+                               size_t total_src_len, int level, int match_form, long tiles_per_group, uint32_t *d_match,
+                               uint32_t *d_snap, size_t records_cap, uint32_t *d_snap_used, uint64_t *d_pos_base);
 // deflate.hip: the pipeline itself (the scratch it needs: deflate_scratch.h deflate_scratch_bytes)
 hipError_t launch_deflate(zipc_hip_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst,
                           const StreamDesc *d_descs, StreamResult *d_results, size_t n_streams,

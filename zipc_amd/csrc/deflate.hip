@@ -2721,6 +2721,57 @@ size_t debug_chain_positions(size_t n, size_t total_src_len) {
   return (size_t)P;
 }
 
+// lz_match over one slice of m streams: which kernel, its grid and the groups a workgroup takes are the forms' (forms.h
+// deflate_forms / deflate_slice_forms).  The ONE launch site: the pipeline's (launch_deflate_group) and the tests' entry
+// below both come through here.
+static void launch_lz_match(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *dd, const DeflateScratch &Q, size_t m,
+                            const DeflateForms &F, const DeflateSliceForms &L, int match_form) {
+  const int K = F.K;
+  if (!L.match_window)
+    ZD_LAUNCH(ctx, "lz_match", lz_match_kernel, dim3((unsigned)L.match_grid), dim3(MATCH_THREADS), 0,
+              d_src, dd, Q, (uint32_t)m, (uint32_t)F.cps, K, K / 4);
+  else
+    ZD_LAUNCH(ctx, "lz_match", lz_match_window_kernel, dim3((unsigned)L.match_grid), dim3(MATCHW_THREADS),
+              0, d_src, dd, Q, (uint32_t)m, (uint32_t)F.tps, (uint32_t)F.tpg, (uint32_t)L.gpw, K, K / 4, match_form);
+}
+
+// Tests only (zipc_hip_debug_match_records): deflate_offsets, lz_chain and lz_match of a batch and nothing behind them, and
+// the matcher's tables copied out -- match[], snap[], snap_used[] and the streams' position bases -- so that a test can hold
+// every record of every position to a serial find_backref (zd.ml:1176-1201), visited by the parse or not.  The links are the
+// ordering kernel's (exact without the hardware probe).  match_form and tiles_per_group stand in for the two environment
+// switches, which are read once per process: the forms are computed from a copy of tuning() with them set, and the launch
+// is the pipeline's own (launch_lz_match).  One group, one slice, on ctx->cur.  match[] and snap[] are filled with
+// MATCH_DEBUG_POISON first -- no record looks like it: a distance is at most 2^15, so bits 25..30 are never set -- and the
+// links with zero.
+constexpr uint32_t MATCH_DEBUG_POISON = 0x5A5A5A5Au;
+hipError_t debug_match_records(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *d_descs, size_t n, size_t max_src_len,
+                               size_t total_src_len, int level, int match_form, long tiles_per_group, uint32_t *d_match,
+                               uint32_t *d_snap, size_t records_cap, uint32_t *d_snap_used, uint64_t *d_pos_base) {
+  Tuning t = tuning();
+  t.match_form = match_form;
+  t.match_tiles_per_group = tiles_per_group;
+  size_t per_group, group_total;
+  deflate_grouping(n, max_src_len, total_src_len, t, per_group, group_total);
+  if (per_group != n) return hipErrorInvalidValue;  // one group
+  const DeflateForms F = deflate_forms(n, max_src_len, total_src_len, level, t, false, 1);  // (no exchange chain, one slice)
+  if (F.grid_too_large || F.slices != 1) return hipErrorInvalidValue;
+  DeflateScratch S = carve(ctx->deflate_scratch.p, n, total_src_len, level);
+  if (S.cap_positions > records_cap) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(S.prev, 0, S.cap_positions * 2, ctx->cur);
+  if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)S.match, (int)MATCH_DEBUG_POISON, S.cap_positions, ctx->cur);
+  if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)S.snap, (int)MATCH_DEBUG_POISON, S.cap_positions, ctx->cur);
+  if (e != hipSuccess) return e;
+  ZD_LAUNCH(ctx, "deflate_offsets", deflate_offsets_kernel, dim3(1), dim3(1024), 0, d_descs, (uint32_t)n, S, (uint64_t)max_src_len);
+  ZD_LAUNCH(ctx, "lz_chain", lz_chain_kernel, dim3((unsigned)n), dim3(CHAIN_THREADS), 0, d_src, d_descs, S);
+  launch_lz_match(ctx, d_src, d_descs, S, n, F, deflate_slice_forms(F, n), t.match_form);
+  e = hipMemcpyAsync(d_match, S.match, S.cap_positions * 4, hipMemcpyDeviceToDevice, ctx->cur);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_snap, S.snap, S.cap_positions * 4, hipMemcpyDeviceToDevice, ctx->cur);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_snap_used, S.snap_used, n * 4, hipMemcpyDeviceToDevice, ctx->cur);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_pos_base, S.pos_base, n * 8, hipMemcpyDeviceToDevice, ctx->cur);
+  if (e == hipSuccess) e = hipGetLastError();
+  return e;
+}
+
 // The parse-segment scratch (ctx->parse_scratch): the block plans, then the ParseSegs arrays, each on a 256-byte boundary.
 // Carves them from base and returns the end: from 0, that is the size to allocate -- ONE layout for the size and the pointers.
 static uintptr_t carve_parse_scratch(uintptr_t base, size_t n_plans, size_t n_slots, size_t tiles, size_t seg_syms,
@@ -2817,7 +2868,7 @@ static hipError_t launch_deflate_group(zipc_hip_ctx *ctx, const uint8_t *d_src, 
     check_k = check_k > fit ? (fit ? fit : 1) : check_k;
     ctx->chain_checked = true;
   }
-  const int good_match = F.good_match, K = F.K;
+  const int good_match = F.good_match;
   hipError_t slice_err = hipSuccess;
   // The pipeline of a slice of the group's streams: the slices share the scratch arrays (one
   // scan above gave every stream its base) and the error word, and differ in where their
@@ -2848,12 +2899,7 @@ static hipError_t launch_deflate_group(zipc_hip_ctx *ctx, const uint8_t *d_src, 
       const hipError_t ce = chain_check_enqueue(ctx, d_src, dd, Q, check_k < m ? check_k : m, max_src_len, ctx->chain_check_host);
       if (ce != hipSuccess) slice_err = ce;
     }
-    if (!L.match_window)
-      ZD_LAUNCH(ctx, "lz_match", lz_match_kernel, dim3((unsigned)L.match_grid), dim3(MATCH_THREADS), 0,
-                d_src, dd, Q, (uint32_t)m, (uint32_t)F.cps, K, K / 4);
-    else
-      ZD_LAUNCH(ctx, "lz_match", lz_match_window_kernel, dim3((unsigned)L.match_grid), dim3(MATCHW_THREADS),
-                0, d_src, dd, Q, (uint32_t)m, (uint32_t)F.tps, (uint32_t)F.tpg, (uint32_t)L.gpw, K, K / 4, tuning().match_form);
+    launch_lz_match(ctx, d_src, dd, Q, m, F, L, tuning().match_form);
     if (F.segmented) {
       ParseSegs G = segs;
       const size_t o = lo;  // the slice's segment slots: ParseSegs::slot counts streams from the slice's first (Q.pos_base is the slice's too)

@@ -23,9 +23,11 @@ struct Tuning {
   long parse_seg;              // ZIPC_HIP_PARSE_SEG       positions per parse segment (default 0: by stream length, 4096-16384).
                                //                          test_gpu_fuzz (test_long_mixed_streams_bounded), test_gpu_parity
   long match_tiles_per_group;  // ZIPC_HIP_MATCH_TILES_PER_GROUP  consecutive tiles per lz_match workgroup (default 0: by the grid).
-                               //                          test_gpu_fuzz
+                               //                          test_gpu_fuzz; test_gpu_match_records sets the field itself, per call
+                               //                          (zipc_hip_debug_match_records), and holds every record to a serial reference
   int match_form;              // ZIPC_HIP_MATCH_FORM      0 (default): lz_match's walk chosen per tile; 1 / 2: always the first / second
-                               //                          form.  test_gpu_fuzz, test_gpu_parity "match-form-1" / "match-form-2"
+                               //                          form.  test_gpu_fuzz, test_gpu_parity "match-form-1" / "match-form-2";
+                               //                          test_gpu_match_records likewise: all three forms in one process
   size_t deflate_group_bytes;  // ZIPC_HIP_DEFLATE_GROUP_BYTES  source bytes per pass through the scratch (default 8 GiB; the tests: a
                                //                          few streams).  test_gpu_fuzz
   long slices, slice_min;      // ZIPC_HIP_SLICES, ZIPC_HIP_SLICE_MIN  a batch cut into slices on side queues (default 0: two slices of at
