@@ -343,7 +343,7 @@ inline std::vector<size_t> inflate_blocks_groups(const StreamDesc *sds, const st
 }
 
 // ---------------------------------------------------------------------------------
-// sizing: streams of at least BLOCKS_MIN_SRC bytes by the block path's first half (inflate.hip inflate_size_by_blocks: find,
+// sizing: streams of at least BLOCKS_MIN_SRC bytes by the block path's first half (inflate.hip launch_inflate_size_blocks: find,
 // dry, chain -- and a head walk for the one check the dry runs leave out; the verdict's rule: inflate_blocks.h)
 // A stream the path takes at all.  There is no destination, so no capacity to go by: the source's length alone (dst_off and
 // dst_cap are not looked at, as in every sizing form).  A descriptor with a flag bit that is an argument error is the one

@@ -1607,7 +1607,7 @@ __global__ void inflate_blocks_result_kernel(const BlocksJob *__restrict__ jobs,
   r.status = ST_OK; r.checksum = 0; r.out_len = jobs[j].out_len;
   results[jobs[j].stream] = r;
 }
-// ---- sizing by blocks (inflate_size_by_blocks): the head and the verdict; inflate_blocks.h has the argument
+// ---- sizing by blocks (launch_inflate_size_blocks, inflate_size_blocks_group): the head and the verdict; inflate_blocks.h has the argument
 // The head: a wave per picked stream from bit 0 and output position 0, the one-wave sizing kernel's checks (a distance
 // against the true position among them), up to the first block end at 32768 bytes and more (inflate_wave HEAD).
 // streams[j]: the stream's descriptor; heads[j]: what the wave found.  Like inflate_size_kernel it has no arena but the source.
@@ -1927,162 +1927,198 @@ static int inflate_huge_stream(zipc_hip_ctx *ctx, const void *d_src_arena, void 
   return ZIPC_HIP_OK;
 }
 
-// Streams of at least BLOCKS_MIN_SRC bytes by a wave per block (inflate.hip: find, dry, explore, chain, token, resolve;
-// Adler-32 block by block as the reference updates it; CRC-32 is the caller's pass over the output).  The streams of
-// a call go through every step side by side -- the kernels' grids have them as their second dimension -- and the
-// host reads the counts of all of them back at once between the steps (three or four times a group, not per stream).
+// what BlocksRun::front tells its caller
+struct BlocksFront {
+  bool through = false;         // false: it stopped early -- no stream had a candidate, or there was no room for the span slots
+  bool explored = false;        // an explore round ran (the counts its chain made have not been read back)
+  std::vector<uint32_t> alive;  // the streams, as indices of jobs, that blocks_chained did not drop
+};
+// A group of a call's streams on the block path: their jobs, the host's copy of their counts, their share of
+// ctx->blocks_scratch and what the launches were handed.  The decode (inflate_blocks_group) and the sizing
+// (inflate_size_blocks_group) each have one in their frame and send it through front().  The streams of a group go
+// through every step side by side -- the kernels' grids have them as their second dimension -- and the host reads the
+// counts of all of them back at once between the steps.
+// (the BLOCKS_* limits, which streams go that way and in which groups: forms.h; every length, threshold and offset below: inflate_blocks.h)
+struct BlocksRun {
+  zipc_hip_ctx *const ctx;
+  const size_t nj;
+  const uint64_t stride;  // bytes of input between two explorers
+  std::vector<BlocksJob> jobs;
+  std::vector<FindCounts> fc;
+  FindCounts *d_counts = nullptr;
+  BlocksJob *d_jobs = nullptr;
+  // a launch's streams: the jobs still on their way, as the kernels index them by blockIdx.y.  The lists are the source of
+  // asynchronous copies from pageable memory: they stay until the group is through -- the run lives in the group
+  // function's frame and goes behind that function's final hipStreamSynchronize
+  std::deque<std::vector<BlocksJob>> handed;
+  std::vector<size_t> at;
+
+  BlocksRun(zipc_hip_ctx *c, size_t n) : ctx(c), nj(n), stride(tuning().explore_stride), jobs(n), fc(n) {}
+  // the jobs of streams[0 .. nj) and their lists in ctx->blocks_scratch (false: no room for the lists -- the group leaves
+  // the streams to their one waves, which need none, and returns ZIPC_HIP_OK)
+  bool set_up(const StreamDesc *sds, const uint32_t *streams) {
+    for (size_t j = 0; j < nj; j++) jobs[j] = blocks_job(streams[j], sds[streams[j]].src_len, stride);
+    if (ctx->ensure(ctx->blocks_scratch, carve_blocks_scratch(0, jobs, d_counts, d_jobs)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    carve_blocks_scratch((uintptr_t)ctx->blocks_scratch.p, jobs, d_counts, d_jobs);
+    return true;
+  }
+  hipError_t read_counts() {
+    const hipError_t e = hipMemcpyAsync(fc.data(), d_counts, nj * sizeof(FindCounts), hipMemcpyDeviceToHost, ctx->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
+  }
+  hipError_t hand(const std::vector<uint32_t> &which) {
+    std::vector<BlocksJob> &v = handed.emplace_back();
+    for (uint32_t j : which) v.push_back(jobs[j]);
+    return hipMemcpyAsync(d_jobs, v.data(), v.size() * sizeof(BlocksJob), hipMemcpyHostToDevice, ctx->stream);
+  }
+  // the span decoder's index, a slot per wave of a launch: every stream's waves behind those of the one before
+  // (false: no room for it -- the streams are left to their one waves, which need 2304 bytes each)
+  bool span_slots(const std::vector<uint32_t> &which) {
+    if (ctx->ensure(ctx->inflate_scratch, blocks_span_slots(jobs, which, at)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    for (size_t k = 0; k < which.size(); k++) jobs[which[k]].span = (uint16_t *)((uint8_t *)ctx->inflate_scratch.p + at[k]);
+    return true;
+  }
+  template <class Need> unsigned widest(const std::vector<uint32_t> &which, Need need) const {
+    unsigned w = 1;
+    for (uint32_t j : which) { const unsigned x = (unsigned)need(jobs[j], j); if (x > w) w = x; }
+    return w;
+  }
+
+  // The block path's first half, from the find to the chain, on ctx->cur: the counts cleared, find headers, find lengths,
+  // [the counts read back and the streams without candidates dropped: blocks_found], dry run, sort, chain (walk 0), the
+  // counts read back; and for the streams whose chain came to a block nobody listed (blocks_chained): explorers from
+  // there on (blocks_explore_waves), sort, then the chain again (walk 1), which now walks what is still missing itself.
+  // The counts of that second walk stay on the device: a caller that wants them reads them.
+  // dst: the destination arena, or null -- the sizing's, which has none (no kernel here goes through it: see there).
+  int front(const uint8_t *src, uint8_t *dst, const StreamDesc *dd, const StreamDesc *sds, BlocksFront &f) {
+    std::vector<uint32_t> &alive = f.alive;
+    std::vector<uint32_t> keep;
+    alive.resize(nj);
+    for (size_t j = 0; j < nj; j++) alive[j] = (uint32_t)j;
+    const unsigned ny = (unsigned)nj;
+
+    HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, nj * sizeof(FindCounts), ctx->stream));
+    HIP_TRY(ctx, hand(alive));
+    ZD_LAUNCH(ctx, "inflate_find_headers", inflate_find_headers_kernel,
+              dim3(widest(alive, [&](const BlocksJob &J, uint32_t) { return (sds[J.stream].src_len + 1023) / 1024; }), ny), dim3(256), 0, src, dd,
+              (const BlocksJob *)d_jobs);
+    ZD_LAUNCH(ctx, "inflate_find_lengths", inflate_find_lengths_kernel,
+              dim3(widest(alive, [](const BlocksJob &J, uint32_t) { return (J.first_cap + 63u) / 64u; }), ny), dim3(64), 0, src, dd,
+              (const BlocksJob *)d_jobs);
+    if (blocks_read_candidates(nj, jobs[0].cand_cap)) {
+      HIP_TRY(ctx, read_counts());
+      for (uint32_t j : alive)
+        if (blocks_found(fc[j], jobs[j])) { jobs[j].n = fc[j].n_cand; keep.push_back(j); }
+      alive.swap(keep);
+      if (alive.empty()) return ZIPC_HIP_OK;
+    } else {
+      jobs[0].n = jobs[0].cand_cap;
+    }
+    if (!span_slots(alive)) return ZIPC_HIP_OK;
+    HIP_TRY(ctx, hand(alive));
+    const unsigned na = (unsigned)alive.size();
+    const unsigned dry_waves = widest(alive, [](const BlocksJob &J, uint32_t) { return J.n; });
+    ZD_LAUNCH(ctx, "inflate_blocks_dry", inflate_blocks_dry_kernel, dim3(dry_waves, na), dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs);
+    ZD_LAUNCH(ctx, "inflate_sort_blocks", inflate_sort_blocks_kernel, dim3((dry_waves + 255u) / 256u, na), dim3(256), 0, (const BlocksJob *)d_jobs);
+    ZD_LAUNCH(ctx, "inflate_chain", inflate_chain_kernel, dim3(1, na), dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs, 0);
+    HIP_TRY(ctx, read_counts());
+    keep.clear();
+    std::vector<uint32_t> lost;  // streams whose chain came to a block nobody listed
+    for (uint32_t j : alive) {
+      const BlocksChained v = blocks_chained(fc[j], jobs[j]);
+      if (v == BLOCKS_LOST) lost.push_back(j);
+      if (v != BLOCKS_DROPPED) keep.push_back(j);
+    }
+    alive.swap(keep);
+    if (!lost.empty()) {
+      for (uint32_t j : lost) blocks_explore_waves(fc[j], jobs[j], sds[jobs[j].stream].src_len, stride);
+      if (!span_slots(lost)) return ZIPC_HIP_OK;
+      HIP_TRY(ctx, hand(lost));
+      const unsigned nl = (unsigned)lost.size();
+      ZD_LAUNCH(ctx, "inflate_explore", inflate_explore_kernel, dim3(widest(lost, [](const BlocksJob &J, uint32_t) { return J.n; }), nl), dim3(64), 0,
+                src, dst, dd, (const BlocksJob *)d_jobs, (uint32_t)(stride * 8u));
+      ZD_LAUNCH(ctx, "inflate_sort_blocks", inflate_sort_blocks_kernel,
+                dim3(widest(lost, [](const BlocksJob &J, uint32_t) { return (J.rec_cap + 255u) / 256u; }), nl), dim3(256), 0, (const BlocksJob *)d_jobs);
+      ZD_LAUNCH(ctx, "inflate_chain", inflate_chain_kernel, dim3(1, nl), dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs, 1);
+      f.explored = true;
+    }
+    f.through = true;
+    return ZIPC_HIP_OK;
+  }
+};
+
+// Streams of at least BLOCKS_MIN_SRC bytes by a wave per block: the front above, then token, resolve and gather (Adler-32
+// block by block as the reference updates it; CRC-32 is the caller's pass over the output), the counts read back three or
+// four times a group, not per stream.
 // handled[i]: stream i went that way (its result is in d_results); else it is left to inflate_batch_kernel -- a stream
 // that is not a chain of dynamic blocks behind its first block, anything the dry run or the chain did not like: the
 // one-wave kernel owns the reference's messages.  It SYNCHRONISES the context's stream.  ZIPC_HIP_INFLATE_BLOCKS=0
 // turns it off.
-// (the BLOCKS_* limits, which streams go that way and in which groups: forms.h; every length, threshold and offset below: inflate_blocks.h)
 static int inflate_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, uint8_t *dst, const StreamDesc *dd, StreamResult *d_results,
                                 const StreamDesc *sds, const uint32_t *streams, size_t nj, int crc_op, uint8_t *handled) {
-  const uint64_t stride = tuning().explore_stride;  // bytes of input between two explorers
   const bool adler = crc_op == ZIPC_HIP_CRC_ADLER32 || crc_op == ZIPC_HIP_CRC_ADLER32_RFC1950;
-  std::vector<BlocksJob> jobs(nj);
-  for (size_t j = 0; j < nj; j++) jobs[j] = blocks_job(streams[j], sds[streams[j]].src_len, stride);
-  FindCounts *d_counts;
-  BlocksJob *d_jobs;
-  if (ctx->ensure(ctx->blocks_scratch, carve_blocks_scratch(0, jobs, d_counts, d_jobs)) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }  // (no room for the lists: the streams' one waves need none)
-  carve_blocks_scratch((uintptr_t)ctx->blocks_scratch.p, jobs, d_counts, d_jobs);
-  std::vector<FindCounts> fc(nj);
-  auto read_counts = [&]() -> hipError_t {
-    const hipError_t e = hipMemcpyAsync(fc.data(), d_counts, nj * sizeof(FindCounts), hipMemcpyDeviceToHost, ctx->stream);
-    return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
-  };
-  // a launch's streams: the jobs still on their way, as the kernels index them by blockIdx.y (the lists handed to
-  // the copies stay until the group is through)
-  std::deque<std::vector<BlocksJob>> handed;
-  auto hand = [&](const std::vector<uint32_t> &which) -> hipError_t {
-    std::vector<BlocksJob> &v = handed.emplace_back();
-    for (uint32_t j : which) v.push_back(jobs[j]);
-    return hipMemcpyAsync(d_jobs, v.data(), v.size() * sizeof(BlocksJob), hipMemcpyHostToDevice, ctx->stream);
-  };
-  // the span decoder's index, a slot per wave of a launch: every stream's waves behind those of the one before
-  // (false: no room for it -- the streams are left to their one waves, which need 2304 bytes each)
-  std::vector<size_t> at;
-  auto span_slots = [&](const std::vector<uint32_t> &which) {
-    if (ctx->ensure(ctx->inflate_scratch, blocks_span_slots(jobs, which, at)) != hipSuccess) { (void)hipGetLastError(); return false; }
-    for (size_t k = 0; k < which.size(); k++) jobs[which[k]].span = (uint16_t *)((uint8_t *)ctx->inflate_scratch.p + at[k]);
-    return true;
-  };
-  auto widest = [&](const std::vector<uint32_t> &which, auto need) {
-    unsigned w = 1;
-    for (uint32_t j : which) { const unsigned x = (unsigned)need(jobs[j], j); if (x > w) w = x; }
-    return w;
-  };
-  std::vector<uint32_t> alive(nj), keep;
-  for (size_t j = 0; j < nj; j++) alive[j] = (uint32_t)j;
-  const unsigned ny = (unsigned)nj;
-
-  HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, nj * sizeof(FindCounts), ctx->stream));
-  HIP_TRY(ctx, hand(alive));
-  ZD_LAUNCH(ctx, "inflate_find_headers", inflate_find_headers_kernel,
-            dim3(widest(alive, [&](const BlocksJob &J, uint32_t) { return (sds[J.stream].src_len + 1023) / 1024; }), ny), dim3(256), 0, src, dd,
-            (const BlocksJob *)d_jobs);
-  ZD_LAUNCH(ctx, "inflate_find_lengths", inflate_find_lengths_kernel,
-            dim3(widest(alive, [](const BlocksJob &J, uint32_t) { return (J.first_cap + 63u) / 64u; }), ny), dim3(64), 0, src, dd,
-            (const BlocksJob *)d_jobs);
-  if (blocks_read_candidates(nj, jobs[0].cand_cap)) {
-    HIP_TRY(ctx, read_counts());
-    keep.clear();
-    for (uint32_t j : alive)
-      if (blocks_found(fc[j], jobs[j])) { jobs[j].n = fc[j].n_cand; keep.push_back(j); }
-    alive.swap(keep);
-    if (alive.empty()) return ZIPC_HIP_OK;
-  } else {
-    jobs[0].n = jobs[0].cand_cap;
-  }
-  if (!span_slots(alive)) return ZIPC_HIP_OK;
-  HIP_TRY(ctx, hand(alive));
-  unsigned na = (unsigned)alive.size();
-  const unsigned dry_waves = widest(alive, [](const BlocksJob &J, uint32_t) { return J.n; });
-  ZD_LAUNCH(ctx, "inflate_blocks_dry", inflate_blocks_dry_kernel, dim3(dry_waves, na), dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs);
-  ZD_LAUNCH(ctx, "inflate_sort_blocks", inflate_sort_blocks_kernel, dim3((dry_waves + 255u) / 256u, na), dim3(256), 0, (const BlocksJob *)d_jobs);
-  ZD_LAUNCH(ctx, "inflate_chain", inflate_chain_kernel, dim3(1, na), dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs, 0);
-  HIP_TRY(ctx, read_counts());
-  keep.clear();
-  std::vector<uint32_t> lost;  // streams whose chain came to a block nobody listed
-  for (uint32_t j : alive) {
-    const BlocksChained v = blocks_chained(fc[j], jobs[j]);
-    if (v == BLOCKS_LOST) lost.push_back(j);
-    if (v != BLOCKS_DROPPED) keep.push_back(j);
-  }
-  alive.swap(keep);
-  if (!lost.empty()) {
-    // explorers from there on, then the chain again (which now walks what is still missing itself)
-    for (uint32_t j : lost) blocks_explore_waves(fc[j], jobs[j], sds[jobs[j].stream].src_len, stride);
-    if (!span_slots(lost)) return ZIPC_HIP_OK;
-    HIP_TRY(ctx, hand(lost));
-    const unsigned nl = (unsigned)lost.size();
-    ZD_LAUNCH(ctx, "inflate_explore", inflate_explore_kernel, dim3(widest(lost, [](const BlocksJob &J, uint32_t) { return J.n; }), nl), dim3(64), 0,
-              src, dst, dd, (const BlocksJob *)d_jobs, (uint32_t)(stride * 8u));
-    ZD_LAUNCH(ctx, "inflate_sort_blocks", inflate_sort_blocks_kernel,
-              dim3(widest(lost, [](const BlocksJob &J, uint32_t) { return (J.rec_cap + 255u) / 256u; }), nl), dim3(256), 0, (const BlocksJob *)d_jobs);
-    ZD_LAUNCH(ctx, "inflate_chain", inflate_chain_kernel, dim3(1, nl), dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs, 1);
-    HIP_TRY(ctx, read_counts());
-  }
-  const TokenPlan plan = blocks_token_plan(jobs, fc, alive, sds, tuning().inflate_follow);
-  alive = plan.taken;
+  BlocksRun run(ctx, nj);
+  if (!run.set_up(sds, streams)) return ZIPC_HIP_OK;
+  BlocksFront f;
+  const int st = run.front(src, dst, dd, sds, f);
+  if (st != ZIPC_HIP_OK || !f.through) return st;
+  if (f.explored) HIP_TRY(ctx, run.read_counts());
+  const TokenPlan plan = blocks_token_plan(run.jobs, run.fc, f.alive, sds, tuning().inflate_follow);
+  std::vector<uint32_t> alive = plan.taken, keep;
   if (alive.empty()) return ZIPC_HIP_OK;
   if (ctx->ensure(ctx->tok_scratch, plan.tok_bytes) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }  // (no room for a word per byte and the lists: the streams' one waves need none)
-  for (size_t k = 0; k < alive.size(); k++) jobs[alive[k]].tok = (uint32_t *)((uint8_t *)ctx->tok_scratch.p + plan.tok_at[k]);
-  if (!span_slots(alive)) return ZIPC_HIP_OK;
-  HIP_TRY(ctx, hand(alive));
-  na = (unsigned)alive.size();
-  const unsigned out_grid = widest(alive, [](const BlocksJob &J, uint32_t) { return (J.out_len + 255u) / 256u; });
-  ZD_LAUNCH(ctx, "inflate_tok_init", inflate_tok_init_kernel, dim3(out_grid, na), dim3(256), 0, (const BlocksJob *)d_jobs);
-  ZD_LAUNCH(ctx, "inflate_blocks_token", inflate_blocks_token_kernel, dim3(widest(alive, [](const BlocksJob &J, uint32_t) { return J.n; }), na),
-            dim3(64), 0, src, dst, dd, (const BlocksJob *)d_jobs);
+  for (size_t k = 0; k < alive.size(); k++) run.jobs[alive[k]].tok = (uint32_t *)((uint8_t *)ctx->tok_scratch.p + plan.tok_at[k]);
+  if (!run.span_slots(alive)) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, run.hand(alive));
+  unsigned na = (unsigned)alive.size();
+  const unsigned out_grid = run.widest(alive, [](const BlocksJob &J, uint32_t) { return (J.out_len + 255u) / 256u; });
+  ZD_LAUNCH(ctx, "inflate_tok_init", inflate_tok_init_kernel, dim3(out_grid, na), dim3(256), 0, (const BlocksJob *)run.d_jobs);
+  ZD_LAUNCH(ctx, "inflate_blocks_token", inflate_blocks_token_kernel, dim3(run.widest(alive, [](const BlocksJob &J, uint32_t) { return J.n; }), na),
+            dim3(64), 0, src, dst, dd, (const BlocksJob *)run.d_jobs);
   const int hops0 = tuning().resolve_hops0, hops1 = tuning().resolve_hops1;
   const int rounds = resolve_rounds(hops0, hops1);
   for (int r = 0; r < rounds; r++)
-    ZD_LAUNCH(ctx, "inflate_resolve", inflate_resolve_kernel, dim3(resolve_grid(r, out_grid), na), dim3(256), 0, (const BlocksJob *)d_jobs, r, r == 0 ? hops0 : hops1);
-  ZD_LAUNCH(ctx, "inflate_gather", inflate_gather_kernel, dim3(out_grid, na), dim3(256), 0, dst, dd, (const BlocksJob *)d_jobs);
-  HIP_TRY(ctx, read_counts());
+    ZD_LAUNCH(ctx, "inflate_resolve", inflate_resolve_kernel, dim3(resolve_grid(r, out_grid), na), dim3(256), 0, (const BlocksJob *)run.d_jobs, r, r == 0 ? hops0 : hops1);
+  ZD_LAUNCH(ctx, "inflate_gather", inflate_gather_kernel, dim3(out_grid, na), dim3(256), 0, dst, dd, (const BlocksJob *)run.d_jobs);
+  HIP_TRY(ctx, run.read_counts());
   // (12 bytes of scratch per output byte: what a long stream took goes back -- a context lives as long as its thread,
   // and a 1 GiB member would pin 12 GiB per device; the stream is idle here, the gather has been waited for)
   if (ctx->tok_scratch.cap > BLOCKS_TOK_BUDGET) free_buf(ctx->tok_scratch);
   keep.clear();
   size_t n_chunks = 0;
   for (uint32_t j : alive) {
-    if (!blocks_done(fc[j], rounds)) continue;  // (the one-wave kernel writes the output again)
-    n_chunks += fc[j].n_chunks;
+    if (!blocks_done(run.fc[j], rounds)) continue;  // (the one-wave kernel writes the output again)
+    n_chunks += run.fc[j].n_chunks;
     keep.push_back(j);
   }
   alive.swap(keep);
   if (alive.empty()) return ZIPC_HIP_OK;
   na = (unsigned)alive.size();
   if (adler) {  // block by block, every block's bytes in chunks of their own
-    if (ctx->ensure(ctx->adler_sums, blocks_adler_sums(fc, alive, at)) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }  // (the one waves write output and checksum again)
-    for (size_t k = 0; k < alive.size(); k++) jobs[alive[k]].sums = (uint32_t *)((uint8_t *)ctx->adler_sums.p + at[k]);
+    if (ctx->ensure(ctx->adler_sums, blocks_adler_sums(run.fc, alive, run.at)) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }  // (the one waves write output and checksum again)
+    for (size_t k = 0; k < alive.size(); k++) run.jobs[alive[k]].sums = (uint32_t *)((uint8_t *)ctx->adler_sums.p + run.at[k]);
   }
-  HIP_TRY(ctx, hand(alive));
-  ZD_LAUNCH(ctx, "inflate_blocks_result", inflate_blocks_result_kernel, dim3((na + 63u) / 64u), dim3(64), 0, (const BlocksJob *)d_jobs, d_results, na);
+  HIP_TRY(ctx, run.hand(alive));
+  ZD_LAUNCH(ctx, "inflate_blocks_result", inflate_blocks_result_kernel, dim3((na + 63u) / 64u), dim3(64), 0, (const BlocksJob *)run.d_jobs, d_results, na);
   if (adler) {
     if (n_chunks)
-      ZD_LAUNCH(ctx, "inflate_adler_chunks", inflate_adler_chunks_kernel, dim3(widest(alive, [&](const BlocksJob &, uint32_t j) { return fc[j].n_chunks; }), na),
-                dim3(64), 0, (const uint8_t *)dst, dd, (const BlocksJob *)d_jobs);
-    ZD_LAUNCH(ctx, "inflate_adler_fold", inflate_adler_fold_kernel, dim3(1, na), dim3(64), 0, (const BlocksJob *)d_jobs,
+      ZD_LAUNCH(ctx, "inflate_adler_chunks", inflate_adler_chunks_kernel, dim3(run.widest(alive, [&](const BlocksJob &, uint32_t j) { return run.fc[j].n_chunks; }), na),
+                dim3(64), 0, (const uint8_t *)dst, dd, (const BlocksJob *)run.d_jobs);
+    ZD_LAUNCH(ctx, "inflate_adler_fold", inflate_adler_fold_kernel, dim3(1, na), dim3(64), 0, (const BlocksJob *)run.d_jobs,
               crc_op == ZIPC_HIP_CRC_ADLER32_RFC1950 ? 1 : 0, d_results);
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the lists handed to the copies go with this frame)
-  for (uint32_t j : alive) { handled[jobs[j].stream] = 1; ctx->last_inflate_blocks += jobs[j].n_blocks; }
+  for (uint32_t j : alive) { handled[run.jobs[j].stream] = 1; ctx->last_inflate_blocks += run.jobs[j].n_blocks; }
   return ZIPC_HIP_OK;
 }
 
-// which of a call's streams go by blocks, group by group; *n_handled: how many did
-// h_descs: the caller's own host copy of the descriptors (the many-stream host forms have one), or null: they are read
-// back from the device, which waits for everything the stream holds -- the host forms feed sub-batch g + 1 while g's
-// kernels run, and a read-back per sub-batch (before the model below had even said whether any stream goes by blocks:
-// for an archive of equal members none does) put the host behind every sub-batch's copies and kernels.
-static int inflate_by_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
-                             zipc_hip_stream_result *d_results, size_t n_streams, int crc_op, std::vector<StreamDesc> &sds,
-                             std::vector<uint8_t> &handled, size_t *n_handled, const StreamDesc *h_descs) {
-  *n_handled = 0;
-  handled.assign(n_streams, 0);
-  if (!zd::tuning().inflate_blocks) return ZIPC_HIP_OK;
+// a call's descriptors on the host, for the decode and the sizing by blocks.  h_descs: the caller's own host copy (the
+// many-stream host forms have one), or null: they are read back from the device, which waits for everything the stream
+// holds -- the host forms feed sub-batch g + 1 while g's kernels run, and a read-back per sub-batch (before the model had
+// even said whether any stream goes by blocks: for an archive of equal members none does) put the host behind every
+// sub-batch's copies and kernels.
+static int fetch_descs(zipc_hip_ctx *ctx, const zipc_hip_stream_desc *d_descs, size_t n_streams, const StreamDesc *h_descs,
+                       std::vector<StreamDesc> &sds) {
   if (h_descs) {
     sds.assign(h_descs, h_descs + n_streams);
   } else {
@@ -2090,6 +2126,17 @@ static int inflate_by_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, void *d
     HIP_TRY(ctx, hipMemcpyAsync(sds.data(), d_descs, n_streams * sizeof(StreamDesc), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
+  return ZIPC_HIP_OK;
+}
+
+// which of a call's streams go by blocks, group by group; *n_handled: how many did (h_descs: fetch_descs)
+static int inflate_by_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                             zipc_hip_stream_result *d_results, size_t n_streams, int crc_op, std::vector<StreamDesc> &sds,
+                             std::vector<uint8_t> &handled, size_t *n_handled, const StreamDesc *h_descs) {
+  *n_handled = 0;
+  handled.assign(n_streams, 0);
+  if (!zd::tuning().inflate_blocks) return ZIPC_HIP_OK;
+  if (const int st = fetch_descs(ctx, d_descs, n_streams, h_descs, sds)) return st;
   const std::vector<uint32_t> picked = inflate_blocks_pick(sds.data(), n_streams);
   size_t begin = 0;
   for (size_t end : inflate_blocks_groups(sds.data(), picked)) {
@@ -2155,11 +2202,10 @@ int launch_inflate_size(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_h
   return ZIPC_HIP_OK;
 }
 
-// A group of a sizing call's long streams by the block path's first half: find, dry, sort, chain (explore, sort, chain for
-// a chain that got lost) -- the launches of inflate_blocks_group in its order, over `dd`, the library's copy of the
-// descriptors with dst_off 0 and dst_cap MAX_STREAM_LEN (the chain's room is then min(limit, MAX_STREAM_LEN), and
-// dst_arena + dst_off, which IM_DRY forms and never goes through, is null) -- with the head beside them on a queue of
-// its own, and the verdict behind both.  No tok[], token run, resolve, gather or Adler kernels, no destination.
+// A group of a sizing call's long streams by the front alone, over `dd`, the library's copy of the descriptors with dst_off 0
+// and dst_cap MAX_STREAM_LEN (the chain's room is then min(limit, MAX_STREAM_LEN), and dst_arena + dst_off, which IM_DRY
+// forms and never goes through, is null) -- with the head beside it on a queue of its own, and the verdict behind both.
+// No tok[], token run, resolve, gather or Adler kernels, no destination.
 // No IM_DRY path loads or stores through the destination: inflate_wave's literal stores, wave_copy and the strided turn's
 // are im_stores(MODE), wave_match is IM_REAL / IM_TOKEN, the queue of deferred copies is filled by IM_REAL alone (wide_turn;
 // lane_match_commit's may_queue), so the service that fills it never runs, PH_REQ_ADLER is entered with crc_adler, which is
@@ -2168,105 +2214,36 @@ int launch_inflate_size(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_h
 // sized[stream]: blocks of what sized it, 0: left to the one wave.  SYNCHRONISES the context's stream.
 static int inflate_size_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, const StreamDesc *dd, StreamResult *d_results,
                                      const StreamDesc *sds, const uint32_t *streams, size_t nj, uint32_t *sized) {
-  const uint64_t stride = tuning().explore_stride;
-  std::vector<BlocksJob> jobs(nj);
-  for (size_t j = 0; j < nj; j++) jobs[j] = blocks_job(streams[j], sds[streams[j]].src_len, stride);
-  FindCounts *d_counts;
-  BlocksJob *d_jobs;
+  BlocksRun run(ctx, nj);
   // (no room for the lists, or for the heads: the streams' one waves need none)
-  if (ctx->ensure(ctx->blocks_scratch, carve_blocks_scratch(0, jobs, d_counts, d_jobs)) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }
-  carve_blocks_scratch((uintptr_t)ctx->blocks_scratch.p, jobs, d_counts, d_jobs);
+  if (!run.set_up(sds, streams)) return ZIPC_HIP_OK;
   const SizeHeadScratch hs = size_head_scratch(nj);
   if (ctx->ensure(ctx->size_head, hs.bytes + nj * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }
   uint8_t *hb = (uint8_t *)ctx->size_head.p;
   BlockEnd *d_heads = (BlockEnd *)(hb + hs.heads);
   uint32_t *d_streams = (uint32_t *)(hb + hs.streams), *d_sized = (uint32_t *)(hb + hs.bytes);
-  uint8_t *null_dst = nullptr;
-  std::vector<FindCounts> fc(nj);
-  auto read_counts = [&]() -> hipError_t {
-    const hipError_t e = hipMemcpyAsync(fc.data(), d_counts, nj * sizeof(FindCounts), hipMemcpyDeviceToHost, ctx->stream);
-    return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
-  };
-  std::deque<std::vector<BlocksJob>> handed;
-  auto hand = [&](const std::vector<uint32_t> &which) -> hipError_t {
-    std::vector<BlocksJob> &v = handed.emplace_back();
-    for (uint32_t j : which) v.push_back(jobs[j]);
-    return hipMemcpyAsync(d_jobs, v.data(), v.size() * sizeof(BlocksJob), hipMemcpyHostToDevice, ctx->stream);
-  };
-  std::vector<size_t> at;
-  auto span_slots = [&](const std::vector<uint32_t> &which) {
-    if (ctx->ensure(ctx->inflate_scratch, blocks_span_slots(jobs, which, at)) != hipSuccess) { (void)hipGetLastError(); return false; }
-    for (size_t k = 0; k < which.size(); k++) jobs[which[k]].span = (uint16_t *)((uint8_t *)ctx->inflate_scratch.p + at[k]);
-    return true;
-  };
-  auto widest = [&](const std::vector<uint32_t> &which, auto need) {
-    unsigned w = 1;
-    for (uint32_t j : which) { const unsigned x = (unsigned)need(jobs[j], j); if (x > w) w = x; }
-    return w;
-  };
-  std::vector<uint32_t> all(nj), alive, keep;
-  for (size_t j = 0; j < nj; j++) all[j] = (uint32_t)j;
-  alive = all;
   const unsigned ny = (unsigned)nj;
 
-  HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, nj * sizeof(FindCounts), ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_streams, streams, nj * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-  // the head depends on nothing the other steps make: on a queue beside them (every path from here goes through the join)
+  // the head depends on nothing the front makes: on a queue beside it (every path from here goes through the join)
   HIP_TRY(ctx, ctx->fork(2));
   ctx->use_slice_stream(1);
   ZD_LAUNCH(ctx, "inflate_size_head", inflate_size_head_kernel, dim3(ny), dim3(64), 0, src, dd, (const uint32_t *)d_streams, d_heads,
             (uint32_t)nj, (uint16_t *)(hb + hs.span));
   ctx->use_slice_stream(0);
-  auto steps = [&]() -> int {
-    HIP_TRY(ctx, hand(alive));
-    ZD_LAUNCH(ctx, "inflate_find_headers", inflate_find_headers_kernel,
-              dim3(widest(alive, [&](const BlocksJob &J, uint32_t) { return (sds[J.stream].src_len + 1023) / 1024; }), ny), dim3(256), 0, src, dd,
-              (const BlocksJob *)d_jobs);
-    ZD_LAUNCH(ctx, "inflate_find_lengths", inflate_find_lengths_kernel,
-              dim3(widest(alive, [](const BlocksJob &J, uint32_t) { return (J.first_cap + 63u) / 64u; }), ny), dim3(64), 0, src, dd,
-              (const BlocksJob *)d_jobs);
-    if (blocks_read_candidates(nj, jobs[0].cand_cap)) {
-      HIP_TRY(ctx, read_counts());
-      keep.clear();
-      for (uint32_t j : alive)
-        if (blocks_found(fc[j], jobs[j])) { jobs[j].n = fc[j].n_cand; keep.push_back(j); }
-      alive.swap(keep);
-      if (alive.empty()) return ZIPC_HIP_OK;
-    } else {
-      jobs[0].n = jobs[0].cand_cap;
-    }
-    if (!span_slots(alive)) return ZIPC_HIP_OK;
-    HIP_TRY(ctx, hand(alive));
-    const unsigned na = (unsigned)alive.size();
-    const unsigned dry_waves = widest(alive, [](const BlocksJob &J, uint32_t) { return J.n; });
-    ZD_LAUNCH(ctx, "inflate_blocks_dry", inflate_blocks_dry_kernel, dim3(dry_waves, na), dim3(64), 0, src, null_dst, dd, (const BlocksJob *)d_jobs);
-    ZD_LAUNCH(ctx, "inflate_sort_blocks", inflate_sort_blocks_kernel, dim3((dry_waves + 255u) / 256u, na), dim3(256), 0, (const BlocksJob *)d_jobs);
-    ZD_LAUNCH(ctx, "inflate_chain", inflate_chain_kernel, dim3(1, na), dim3(64), 0, src, null_dst, dd, (const BlocksJob *)d_jobs, 0);
-    HIP_TRY(ctx, read_counts());
-    std::vector<uint32_t> lost;  // streams whose chain came to a block nobody listed
-    for (uint32_t j : alive)
-      if (blocks_chained(fc[j], jobs[j]) == BLOCKS_LOST) lost.push_back(j);
-    if (!lost.empty()) {
-      for (uint32_t j : lost) blocks_explore_waves(fc[j], jobs[j], sds[jobs[j].stream].src_len, stride);
-      if (!span_slots(lost)) return ZIPC_HIP_OK;  // (their chains stay "not ok")
-      HIP_TRY(ctx, hand(lost));
-      const unsigned nl = (unsigned)lost.size();
-      ZD_LAUNCH(ctx, "inflate_explore", inflate_explore_kernel, dim3(widest(lost, [](const BlocksJob &J, uint32_t) { return J.n; }), nl), dim3(64), 0,
-                src, null_dst, dd, (const BlocksJob *)d_jobs, (uint32_t)(stride * 8u));
-      ZD_LAUNCH(ctx, "inflate_sort_blocks", inflate_sort_blocks_kernel,
-                dim3(widest(lost, [](const BlocksJob &J, uint32_t) { return (J.rec_cap + 255u) / 256u; }), nl), dim3(256), 0, (const BlocksJob *)d_jobs);
-      ZD_LAUNCH(ctx, "inflate_chain", inflate_chain_kernel, dim3(1, nl), dim3(64), 0, src, null_dst, dd, (const BlocksJob *)d_jobs, 1);
-    }
-    return ZIPC_HIP_OK;
-  };
-  const int st = steps();
+  // (where the front stopped, or whom it dropped, is not asked: the verdict below says it.  The counts of a second chain
+  // walk are not read back either: the verdict reads them on the device)
+  BlocksFront f;
+  const int st = run.front(src, nullptr, dd, sds, f);
   const hipError_t je = ctx->join(2);
   if (st != ZIPC_HIP_OK) { (void)hipStreamSynchronize(ctx->stream); return st; }
   HIP_TRY(ctx, je);
-  // the verdict over every stream of the group: one the steps dropped has chain_ok 0 (the counts were cleared, or its
+  // the verdict over every stream of the group: one the front dropped has chain_ok 0 (the counts were cleared, or its
   // chain said so) and is sized only by a head that saw the final block
-  HIP_TRY(ctx, hand(all));
-  ZD_LAUNCH(ctx, "inflate_size_verdict", inflate_size_verdict_kernel, dim3((ny + 63u) / 64u), dim3(64), 0, (const BlocksJob *)d_jobs,
+  std::vector<uint32_t> all(nj);
+  for (size_t j = 0; j < nj; j++) all[j] = (uint32_t)j;
+  HIP_TRY(ctx, run.hand(all));
+  ZD_LAUNCH(ctx, "inflate_size_verdict", inflate_size_verdict_kernel, dim3((ny + 63u) / 64u), dim3(64), 0, (const BlocksJob *)run.d_jobs,
             (const BlockEnd *)d_heads, d_results, d_sized, (uint32_t)nj);
   std::vector<uint32_t> got(nj);
   HIP_TRY(ctx, hipMemcpyAsync(got.data(), d_sized, nj * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -2279,7 +2256,7 @@ static int inflate_size_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, cons
 // group, then inflate_size_kernel's wave for every stream that was not sized that way -- any error, a limit exceeded, a
 // chain that is not chain_ok, no candidates, lists too long, no scratch to be had: that kernel owns every message, as
 // inflate_batch_kernel does for the decode.  The block path reports no error status of its own.
-// h_descs: the caller's host copy of the descriptors, or null: they are read back.  SYNCHRONISES the context's stream
+// h_descs: fetch_descs.  SYNCHRONISES the context's stream
 // (ZIPC_HIP_INFLATE_BLOCKS=0, or a call without a long stream: launch_inflate_size and nothing else).
 int launch_inflate_size_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
                                size_t n_streams, const StreamDesc *h_descs) {
@@ -2288,13 +2265,7 @@ int launch_inflate_size_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, const
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!tuning().inflate_blocks || n_streams > BLOCKS_MAX_STREAMS) return launch_inflate_size(ctx, d_src_arena, d_descs, d_results, n_streams);
   std::vector<StreamDesc> sds;
-  if (h_descs) {
-    sds.assign(h_descs, h_descs + n_streams);
-  } else {
-    sds.resize(n_streams);
-    HIP_TRY(ctx, hipMemcpyAsync(sds.data(), d_descs, n_streams * sizeof(StreamDesc), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  if (const int st = fetch_descs(ctx, d_descs, n_streams, h_descs, sds)) return st;
   const std::vector<uint32_t> picked = size_blocks_pick(sds.data(), n_streams);
   if (picked.empty()) return launch_inflate_size(ctx, d_src_arena, d_descs, d_results, n_streams);
   // the descriptors every kernel of this call runs with: sizing is "dst_cap = MAX_STREAM_LEN", and the caller's dst_off

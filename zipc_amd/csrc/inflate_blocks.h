@@ -1,4 +1,4 @@
-// inflate_blocks.h -- what inflate by a wave per block decides between its launches (inflate.hip inflate_blocks_group), free
+// inflate_blocks.h -- what inflate by a wave per block decides between its launches (inflate.hip BlocksRun::front, inflate_blocks_group), free
 // of HIP like forms.h, which has the way into that path: the lengths of a stream's lists, the ONE layout of their scratch, what
 // the host makes of every read-back of the counts, the plan of the token run.  tests/test_host_sim.py pins it row by row.
 #pragma once
@@ -150,7 +150,7 @@ inline size_t blocks_adler_sums(const std::vector<FindCounts> &fc, const std::ve
   return blocks_shares(which, 12, [&](uint32_t j) { return fc[j].n_chunks; }, at) + 12;
 }
 
-// ---- sizing by blocks (inflate.hip inflate_size_by_blocks): find, dry, chain as above, no token run, and a HEAD
+// ---- sizing by blocks (inflate.hip inflate_size_blocks_group): find, dry, chain as above, no token run, and a HEAD
 // Why the answer is exact.  The chain starts at bit 0 and only steps from a block's true end bit to a record that begins at
 // exactly that bit; every record is a real dry decode from its bit with every check of the decoder except the distance
 // against the output position; the chain applies the limit and MAX_STREAM_LEN to the running sum.  So chain_ok means: every
