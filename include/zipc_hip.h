@@ -490,6 +490,37 @@ int zipc_hip_recode_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, co
 int zipc_hip_checksum_device(zipc_hip_ctx *ctx, const void *d_buf, size_t len,
                              int want_crc32, int want_adler32, uint32_t *d_out);
 
+/* CRC-32 and Adler-32 of MANY ranges of one device arena per call, ragged: range i is d_arena[off, off + len).  All
+ * pointers are device pointers; the work is enqueued on the context's stream and not synchronised (growing the
+ * context's scratch may synchronise, as everywhere), and nothing is read back.
+ * For every OK range, crc32 and adler32 are what zipc_hip_checksum_device gives for the same bytes with the same
+ * context flavour (zipc_hip_set_adler_rfc1950); an empty range gives crc32 = 0, adler32 = 1; a checksum not asked for
+ * is 0.  Ranges may overlap, repeat, touch, be empty, start at any byte and be of any length the arena holds (no 4 GiB
+ * limit per range).  A range that lies outside [0, arena_len), or whose end overflows 64 bits, reports
+ * ZIPC_HIP_ERR_INVALID_ARG in its own result with both checksums 0, and none of its bytes is read.
+ * total_len: the sum of len over the call, an upper bound.  It sizes grids and scratch and is checked on the device: if
+ * the OK ranges sum to more, EVERY result is ZIPC_HIP_ERR_INVALID_ARG and no byte of the arena is read.
+ * The call itself fails with ZIPC_HIP_ERR_INVALID_ARG for a null ctx / d_ranges / d_results, a null d_arena with
+ * arena_len > 0, both selectors 0, or where n_ranges or total_len / 32768 + n_ranges exceeds 0x7FFFFFFF;
+ * n_ranges == 0 is OK and enqueues nothing.
+ * The work is one pass over the ranges' bytes by one workgroup per 32 KiB segment THAT EXISTS (a grid of
+ * total_len / 32768 + n_ranges workgroups, whatever the longest range), between a plan and two finishes: four kernel
+ * launches whatever n_ranges is.  Scratch, all in the context and sized from the declared numbers alone:
+ * total_len / 32768 + n_ranges words of CRC partials, total_len / 5552 + n_ranges pairs of Adler-32 chunk sums (zeroed
+ * per call), 12 bytes per range of plan (csrc/checksum_ranges.h has every rule). */
+typedef struct { uint64_t off, len; } zipc_hip_range;                                   /* 16 bytes */
+typedef struct { uint32_t status, crc32, adler32, reserved; } zipc_hip_checksum_result; /* 16 bytes */
+int zipc_hip_checksum_batch(zipc_hip_ctx *ctx, const void *d_arena, size_t arena_len,
+                            const zipc_hip_range *d_ranges, zipc_hip_checksum_result *d_results,
+                            size_t n_ranges, size_t total_len, int want_crc32, int want_adler32);
+/* The same for streams held in HOST memory, through the pipeline of the other _many forms (gather into pinned memory,
+ * copy in, kernels, results back) with nothing but the 16-byte results coming back: results[i] is the result of
+ * src[i][0 .. src_len[i]).  Like the other _many forms: results[] (host memory) is defined on every return, bad
+ * arguments included (every entry then carries the call's status and no checksum), and no C++ exception crosses the
+ * boundary.  The call fails with ZIPC_HIP_ERR_INVALID_ARG for a null src[i] with src_len[i] > 0 or both selectors 0. */
+int zipc_hip_checksum_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len,
+                           int want_crc32, int want_adler32, zipc_hip_checksum_result *results);
+
 /* Tests only: the hash-chain links (zipc_deflate.ml:1150-1152, insert_hash: per position the distance to the previous
  * position of equal hash, 0 beyond 32768) of a batch of device-resident streams as ONE of the library's two chain
  * kernels makes them -- which = 0: by ordered LDS exchange (ZIPC_HIP_ERR_HIP where the context's probe failed), 1: by

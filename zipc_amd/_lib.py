@@ -54,6 +54,14 @@ class RecodeResult(C.Structure):
                 ("stage", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Range(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint64)]
+
+
+class ChecksumResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("crc32", C.c_uint32), ("adler32", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -111,6 +119,8 @@ SYMBOLS = [
     ("zipc_hip_recode_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int]),
     ("zipc_hip_recode_many", C.c_int, [_P, _SZ, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("zipc_hip_checksum_device", C.c_int, [_P, _P, _SZ, C.c_int, C.c_int, _P]),
+    ("zipc_hip_checksum_batch", C.c_int, [_P, _P, _SZ, _P, _P, _SZ, _SZ, C.c_int, C.c_int]),
+    ("zipc_hip_checksum_many", C.c_int, [_P, _SZ, _P, _P, C.c_int, C.c_int, _P]),
     ("zipc_hip_reserve", C.c_int, [_P, _SZ, _SZ, _SZ]),
 ]
 

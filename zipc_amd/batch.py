@@ -1,4 +1,4 @@
-"""Device-resident batch forms (zipc_hip_inflate_batch / _deflate_batch / _checksum_device).
+"""Device-resident batch forms (zipc_hip_inflate_batch / _deflate_batch / _checksum_device / _checksum_batch).
 
 torch is used only as the owner of device memory (uint8 arenas, descriptor and
 result arrays); the work itself is enqueued by libzipc_hip.so on the context's
@@ -9,7 +9,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import CRC_NOP, OK, STREAM_EXPECT_CRC32, STREAM_HAS_LIMIT, Context, lib
+import ctypes as C
+
+from ._lib import CRC_NOP, OK, STREAM_EXPECT_CRC32, STREAM_HAS_LIMIT, ChecksumResult, Context, lib
 
 DESC_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("dst_off", "<u8"),
                        ("dst_cap", "<u8"), ("limit", "<u8"), ("flags", "<u4"),
@@ -23,6 +25,10 @@ RECODE_DESC_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("mid_off"
 RECODE_RESULT_DTYPE = np.dtype([("status", "<u4"), ("checksum", "<u4"), ("out_len", "<u8"), ("mid_len", "<u8"),
                                 ("stage", "<u4"), ("reserved", "<u4")])
 assert RECODE_DESC_DTYPE.itemsize == 64 and RECODE_RESULT_DTYPE.itemsize == 32
+# zipc_hip_range / zipc_hip_checksum_result
+RANGE_DTYPE = np.dtype([("off", "<u8"), ("len", "<u8")])
+CHECKSUM_RESULT_DTYPE = np.dtype([("status", "<u4"), ("crc32", "<u4"), ("adler32", "<u4"), ("reserved", "<u4")])
+assert RANGE_DTYPE.itemsize == 16 and CHECKSUM_RESULT_DTYPE.itemsize == 16
 
 
 def make_descs(src_off, src_len, dst_off, dst_cap, limit=None) -> np.ndarray:
@@ -229,6 +235,55 @@ def checksum_device(ctx: Context, buf, want_crc32=True, want_adler32=True):
     return int(v[0]), int(v[1])
 
 
+def make_ranges(off, length) -> np.ndarray:
+    """zipc_hip_range records: range i is arena[off[i], off[i] + length[i])"""
+    r = np.zeros(len(off), dtype=RANGE_DTYPE)
+    r["off"], r["len"] = off, length
+    return r
+
+
+def checksum_results_from_device(t) -> np.ndarray:
+    return t.cpu().numpy().view(CHECKSUM_RESULT_DTYPE).copy()
+
+
+def checksum_batch(ctx: Context, arena, ranges_dev, results_dev, n_ranges: int, total_len: int, want_crc32=True,
+                   want_adler32=True, arena_len=None, sync: bool = True):
+    """zipc_hip_checksum_batch: CRC-32 and / or Adler-32 of n_ranges ranges of `arena` (a uint8 cuda tensor), ragged, in
+    one call; ranges_dev / results_dev: uint8 cuda tensors of RANGE_DTYPE / CHECKSUM_RESULT_DTYPE records; total_len: the
+    sum of the ranges' lengths, or more.  A range outside the arena reports INVALID_ARG in its own result."""
+    if sync:
+        _sync_torch(arena)
+    st = lib().zipc_hip_checksum_batch(ctx.handle, arena.data_ptr(), arena.numel() if arena_len is None else arena_len,
+                                       ranges_dev.data_ptr(), results_dev.data_ptr(), n_ranges, total_len,
+                                       int(want_crc32), int(want_adler32))
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def checksum_many(ctx: Context, streams, want_crc32=True, want_adler32=True, check: bool = True) -> np.ndarray:
+    """zipc_hip_checksum_many: the checksums of host-resident streams (bytes-like objects; None stands for a null
+    pointer) as CHECKSUM_RESULT_DTYPE records, through the pipeline of the other many-stream forms.  check=False: the
+    call's status is returned beside the results instead of raised."""
+    n = len(streams)
+    keep = [None if s is None else (s if isinstance(s, bytes) else bytes(s)) for s in streams]
+    src = (C.c_void_p * max(n, 1))(*[None if b is None else C.cast(C.c_char_p(b), C.c_void_p) for b in keep])
+    lens = (C.c_size_t * max(n, 1))(*[0 if b is None else len(b) for b in keep])
+    return checksum_many_raw(ctx, n, src, lens, want_crc32, want_adler32, check)
+
+
+def checksum_many_raw(ctx: Context, n, src, lens, want_crc32=True, want_adler32=True, check: bool = True):
+    """checksum_many over ctypes arrays of pointers and lengths as they are"""
+    res = (ChecksumResult * max(n, 1))()
+    C.memset(res, 0xEE, C.sizeof(res))
+    st = lib().zipc_hip_checksum_many(ctx.handle, n, src, lens, int(want_crc32), int(want_adler32), res)
+    out = np.frombuffer(bytes(res), dtype=CHECKSUM_RESULT_DTYPE)[:n].copy()
+    if check:
+        ctx.check(st)
+        return out
+    return st, out
+
+
 def reserve(ctx: Context, n_streams: int, max_src_len: int, total_src_len: int):
     ctx.check(lib().zipc_hip_reserve(ctx.handle, n_streams, max_src_len, total_src_len))
 
@@ -265,5 +320,6 @@ def compact_descs(results: np.ndarray, descs: np.ndarray, dst_cap_of_out, limit_
 __all__ = ["DESC_DTYPE", "RESULT_DTYPE", "RECODE_DESC_DTYPE", "RECODE_RESULT_DTYPE", "make_descs", "make_recode_descs", "to_device",
            "results_from_device", "recode_results_from_device", "recode_batch",
            "inflate_batch", "deflate_batch", "inflate_size_batch", "zlib_size_batch", "inflate_size_blocks_batch", "zlib_size_blocks_batch", "zlib_decompress_batch", "zlib_compress_batch", "checksum_device", "reserve",
+           "RANGE_DTYPE", "CHECKSUM_RESULT_DTYPE", "make_ranges", "checksum_results_from_device", "checksum_batch", "checksum_many",
            "deflate_bound", "zlib_bound",
            "uniform_layout", "compact_descs", "OK"]

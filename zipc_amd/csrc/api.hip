@@ -224,6 +224,14 @@ int crc32_pass(zipc_hip_ctx *ctx, const uint8_t *base, int mode, const StreamDes
   HIP_TRY(ctx, crc32_finish_launch(ctx, mode, d_descs, d_results, n_ranges, single_len, max_len, partials, d_single_out));
   return ZIPC_HIP_OK;
 }
+// zipc_hip_checksum_batch's scratch, from the declared numbers alone: the plan (its call-wide word in 256 bytes, then
+// 8 + 4 bytes per range), segs_bound partials, chunks_bound pairs of chunk sums
+int checksum_ranges_reserve(zipc_hip_ctx *ctx, size_t n_ranges, size_t total_len, int want_adler32) {
+  HIP_TRY(ctx, ctx->ensure(ctx->ranges_plan, 256 + n_ranges * (sizeof(uint64_t) + sizeof(uint32_t))));
+  HIP_TRY(ctx, ctx->ensure(ctx->crc_partials, (size_t)ranges_segs_bound(total_len, n_ranges) * sizeof(uint32_t)));
+  if (want_adler32) HIP_TRY(ctx, ctx->ensure(ctx->adler_sums, (size_t)ranges_chunks_bound(total_len, n_ranges) * sizeof(uint2)));
+  return ZIPC_HIP_OK;
+}
 }  // namespace zd
 
 extern "C" {
@@ -300,6 +308,7 @@ void zipc_hip_destroy(zipc_hip_ctx *ctx) {
   for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
   free_buf(ctx->io_src); free_buf(ctx->io_dst); free_buf(ctx->io_desc); free_buf(ctx->io_res);
   free_buf(ctx->io_pack_off);
+  free_buf(ctx->ranges_plan); free_buf(ctx->io_ranges);
   free_buf(ctx->io_small); free_buf(ctx->crc_partials); free_buf(ctx->crc_nib); free_buf(ctx->adler_sums);
   free_buf(ctx->deflate_scratch); free_buf(ctx->parse_scratch);
   free_buf(ctx->inflate_scratch);
@@ -554,6 +563,48 @@ int zipc_hip_checksum_device(zipc_hip_ctx *ctx, const void *d_buf, size_t len, i
               n_chunks, per, R, amb, ADLER_AMB_CAP, d_out + 1);
     HIP_TRY(ctx, hipGetLastError());
   }
+  return ZIPC_HIP_OK;
+}
+
+// The ragged pass (checksum_ranges.h has the rules, checksum.hip the kernels): plan, one pass over the bytes, two finishes
+int zipc_hip_checksum_batch(zipc_hip_ctx *ctx, const void *d_arena, size_t arena_len, const zipc_hip_range *d_ranges,
+                            zipc_hip_checksum_result *d_results, size_t n_ranges, size_t total_len, int want_crc32,
+                            int want_adler32) {
+  if (!ctx || !d_ranges || !d_results || (!d_arena && arena_len) || (!want_crc32 && !want_adler32)) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (n_ranges > 0x7FFFFFFFull || ranges_segs_bound(total_len, n_ranges) > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (n_ranges == 0) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int st = checksum_ranges_reserve(ctx, n_ranges, total_len, want_adler32);
+  if (st) return st;
+  const uint32_t n = (uint32_t)n_ranges;
+  const uint64_t segs_bound = ranges_segs_bound(total_len, n_ranges), chunks_bound = ranges_chunks_bound(total_len, n_ranges);
+  RangesPlan P;
+  P.call = (RangesCall *)ctx->ranges_plan.p;
+  P.chunk_base = (uint64_t *)((uint8_t *)ctx->ranges_plan.p + 256);
+  P.seg_base = (uint32_t *)(P.chunk_base + n_ranges);
+  const Range *ranges = (const Range *)d_ranges;
+  RangeResult *results = (RangeResult *)d_results;
+  uint32_t *partials = (uint32_t *)ctx->crc_partials.p;
+  uint2 *sums = (uint2 *)ctx->adler_sums.p;
+  ZD_LAUNCH(ctx, "checksum_plan", checksum_plan_kernel, dim3(1), dim3(RANGES_PLAN_TILE), 0, ranges, n, (uint64_t)arena_len,
+            (uint64_t)total_len, P, results, sums, want_adler32 ? chunks_bound : (uint64_t)0);
+  HIP_TRY(ctx, hipGetLastError());
+  // Adler-32 alone runs the fused pass too and leaves the CRC partials unused (there is no chunk-list kernel for a batch)
+  if (want_adler32) {
+    ZD_LAUNCH(ctx, "crc32_adler_ranges", crc32_adler_ranges_kernel, dim3((unsigned)segs_bound), dim3(256), 0, (const uint8_t *)d_arena,
+              ranges, n, P, (const uint32_t *)ctx->crc_nib.p, partials, sums);
+  } else {
+    ZD_LAUNCH(ctx, "crc32_ranges", crc32_ranges_kernel, dim3((unsigned)segs_bound), dim3(256), 0, (const uint8_t *)d_arena, ranges, n,
+              P, (const uint32_t *)ctx->crc_nib.p, partials);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  if (want_crc32)
+    ZD_LAUNCH(ctx, "crc32_finish_ranges", crc32_finish_ranges_kernel, dim3((unsigned)((n_ranges + 3) / 4)), dim3(256), 0, ranges, n, P,
+              ctx->crc_consts, (const uint32_t *)partials, results);
+  if (want_adler32)
+    ZD_LAUNCH(ctx, "adler_finish_ranges", adler_finish_ranges_kernel, dim3((unsigned)((n_ranges + 255) / 256)), dim3(256), 0, ranges, n,
+              P, (const uint2 *)sums, ctx->adler_rfc1950 ? 1 : 0, results);
+  HIP_TRY(ctx, hipGetLastError());
   return ZIPC_HIP_OK;
 }
 

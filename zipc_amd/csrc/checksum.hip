@@ -66,12 +66,13 @@ __device__ __forceinline__ void build_crc_tables(uint32_t (*T)[256], int t) {
 // never inside one.  A thread sums its 8 units (S1 = sum b, S2 = sum (end - i) b, two dot products per word),
 // splits them at the boundary if its piece holds one, and the wave adds what it has of at most three chunks
 // to `adler_sums` (zeroed by the caller; integer adds: any order gives the same sums).
+// The body: segment `seg` of the `nseg` of the range of `len` bytes at p (seg < nseg, uniform per workgroup); the
+// segment's raw CRC goes to *partial.  Which range and segment a workgroup has, and where its partial lies, is its
+// caller's: crc32_segment below for the rectangular grids, crc32_ranges_kernel for the ragged one.
 template <bool ADLER>
-__device__ __forceinline__ void crc32_segment(
-    const uint8_t *__restrict__ base, int mode, const StreamDesc *__restrict__ descs,
-    const StreamResult *__restrict__ results, uint64_t single_off, uint64_t single_len,
-    uint32_t segs_per_range, const uint32_t *__restrict__ nib, uint32_t *__restrict__ partials,
-    uint32_t *__restrict__ adler_sums, uint64_t n_chunks) {
+__device__ __forceinline__ void crc32_segment_body(const uint8_t *__restrict__ p, uint64_t len, uint32_t seg, uint64_t nseg,
+                                                   const uint32_t *__restrict__ nib, uint32_t *__restrict__ partial,
+                                                   uint32_t *__restrict__ adler_sums, uint64_t n_chunks) {
   __shared__ uint32_t T[4][256];
   static_assert(8 * GF2_NIB_WORDS == 4 * CRC_THREADS, "one 16-byte load per thread");
   __shared__ __attribute__((aligned(16))) uint8_t stage[CRC_THREADS * CRC_PIECE_STRIDE];
@@ -81,19 +82,12 @@ __device__ __forceinline__ void crc32_segment(
   uint32_t *N = (uint32_t *)stage;
   uint32_t *wave_part = (uint32_t *)(stage + 8 * GF2_NIB_WORDS * 4);
   const int t = threadIdx.x;
-  const uint32_t range = blockIdx.x / segs_per_range;
-  const uint32_t seg = blockIdx.x % segs_per_range;
-  uint64_t off, len;
-  get_range(mode, range, descs, results, single_off, single_len, off, len);
-  const uint64_t nseg = (len + CRC_SEG - 1) / CRC_SEG;
-  if (seg >= nseg) return;  // uniform per workgroup
   build_crc_tables(T, t);
 
   // right-aligned piece grid: `pad` virtual zero bytes in front of the range;
   // seg0 = range position of the segment's first byte (negative inside the pad)
   const uint64_t pad = nseg * CRC_SEG - len;
   const int64_t seg0 = (int64_t)((uint64_t)seg * CRC_SEG) - (int64_t)pad;
-  const uint8_t *p = base + off;
   constexpr int UNITS = CRC_SEG / 16 / CRC_THREADS;  // 16-byte units per thread
   u32x4 v[UNITS];
   if (len >= 16) {
@@ -189,7 +183,7 @@ __device__ __forceinline__ void crc32_segment(
   if (t == 0) {
     const uint32_t a = gf2_mul_nib(wave_part[0], N + 6 * GF2_NIB_WORDS) ^ wave_part[1];
     const uint32_t b = gf2_mul_nib(wave_part[2], N + 6 * GF2_NIB_WORDS) ^ wave_part[3];
-    partials[(uint64_t)range * segs_per_range + seg] = gf2_mul_nib(a, N + 7 * GF2_NIB_WORDS) ^ b;
+    *partial = gf2_mul_nib(a, N + 7 * GF2_NIB_WORDS) ^ b;
   }
   if constexpr (ADLER) {
     if (cut == 8u) { A1 = s1; A2 = s2; }
@@ -217,6 +211,22 @@ __device__ __forceinline__ void crc32_segment(
     const uint64_t kc = k0 + (ln >> 1);
     if (ln < 6u && kc < n_chunks && mine_v) atomicAdd(adler_sums + 2 * kc + (ln & 1u), mine_v);
   }
+}
+
+// workgroup -> (range, segment) of a rectangular grid: n_ranges x segs_per_range workgroups and as many partials
+template <bool ADLER>
+__device__ __forceinline__ void crc32_segment(
+    const uint8_t *__restrict__ base, int mode, const StreamDesc *__restrict__ descs,
+    const StreamResult *__restrict__ results, uint64_t single_off, uint64_t single_len,
+    uint32_t segs_per_range, const uint32_t *__restrict__ nib, uint32_t *__restrict__ partials,
+    uint32_t *__restrict__ adler_sums, uint64_t n_chunks) {
+  const uint32_t range = blockIdx.x / segs_per_range;
+  const uint32_t seg = blockIdx.x % segs_per_range;
+  uint64_t off, len;
+  get_range(mode, range, descs, results, single_off, single_len, off, len);
+  const uint64_t nseg = (len + CRC_SEG - 1) / CRC_SEG;
+  if (seg >= nseg) return;  // uniform per workgroup
+  crc32_segment_body<ADLER>(base + off, len, seg, nseg, nib, partials + ((uint64_t)range * segs_per_range + seg), adler_sums, n_chunks);
 }
 
 __global__ __launch_bounds__(CRC_THREADS, 4) void crc32_segments_kernel(
@@ -529,6 +539,131 @@ __global__ __launch_bounds__(CHAIN_THREADS_A) void adler_replay_kernel(const uin
   ReplayState st;
   for (uint32_t i = 0; i < n_amb; i++) adler_replay_step(st, r_k[i], r_res[i], r_C[i], r_pc[i], r_prev[i] != 0);
   out[0] = adler_replay_final(st, n_chunks, per, run_res, run_a, run_last_hi, R.s1_after);
+}
+
+// ---- many ranges of one arena, ragged (zipc_hip_checksum_batch) -----------------------------------------------------
+// The rectangular grid above is n_ranges x segments(longest range): ten thousand short ranges beside one long one are
+// almost only empty workgroups.  Here a plan first gives every range a run of the partials and of the chunk sums as long
+// as IT needs (two exclusive scans), and the segment pass is one workgroup per segment that exists: the grid is the
+// bound total_len / 32 KiB + n_ranges, and a workgroup finds its range by bisection of the bases.  Every index, bound and
+// verdict below is checksum_ranges.h's; tests/checksum_ranges_sim runs the same functions as loops on the host.
+static_assert(RANGES_SEG_BYTES == CRC_SEG, "checksum_ranges.h");
+static_assert(RANGES_FINISH_LANES == 64, "a wave per range");
+
+// One workgroup: tiles of RANGES_PLAN_TILE ranges, a range per thread, an inclusive scan of the three counts in LDS and
+// a carry from tile to tile.  Then the call-wide word, and every result's first state: the verdict (or INVALID_ARG for
+// all of a bad call) and no checksum.  It also zeroes the call's n_sums pairs of chunk sums (none where no Adler-32 is
+// asked for): the segment pass adds into them, and a kernel in front of it in the queue is an order the pass can rely on.
+__global__ __launch_bounds__(RANGES_PLAN_TILE) void checksum_plan_kernel(const Range *__restrict__ ranges, uint32_t n_ranges,
+                                                                         uint64_t arena_len, uint64_t total_len, RangesPlan P,
+                                                                         RangeResult *__restrict__ results, uint2 *__restrict__ sums,
+                                                                         uint64_t n_sums) {
+  __shared__ RangeCounts sh[RANGES_PLAN_TILE];
+  const uint32_t t = threadIdx.x;
+  for (uint64_t k = t; k < n_sums; k += RANGES_PLAN_TILE) sums[k] = make_uint2(0u, 0u);
+  RangeCounts carry{0, 0, 0};
+  for (uint64_t t0 = 0; t0 < n_ranges; t0 += RANGES_PLAN_TILE) {  // (uniform: every thread takes every tile)
+    const uint64_t i = t0 + t;
+    RangeCounts mine{0, 0, 0};
+    uint32_t verdict = ST_OK;
+    if (i < n_ranges) {
+      const Range r = ranges[i];
+      mine = range_counts(r, arena_len);
+      verdict = range_verdict(r, arena_len);
+    }
+    sh[t] = mine;
+    __syncthreads();
+    for (uint32_t o = 1; o < RANGES_PLAN_TILE; o <<= 1) {
+      RangeCounts u{0, 0, 0};
+      if (t >= o) u = sh[t - o];
+      __syncthreads();
+      if (t >= o) sh[t] = ranges_counts_add(u, sh[t]);
+      __syncthreads();
+    }
+    const RangeCounts before = t ? ranges_counts_add(carry, sh[t - 1]) : carry;
+    if (i < n_ranges) {
+      P.seg_base[i] = ranges_seg_base(before);
+      P.chunk_base[i] = ranges_chunk_base(before);
+      results[i].status = verdict;
+    }
+    carry = ranges_counts_add(carry, sh[RANGES_PLAN_TILE - 1]);
+    __syncthreads();  // (the next tile overwrites sh)
+  }
+  const RangesCall call = ranges_call_word(carry, total_len);
+  if (t == 0) *P.call = call;
+  for (uint64_t i = t; i < n_ranges; i += RANGES_PLAN_TILE) {  // (i = t0 + t: the thread that wrote the verdict reads it)
+    RangeResult r;
+    r.status = ranges_status(call, results[i].status);
+    r.crc32 = r.adler32 = r.reserved = 0;
+    results[i] = r;
+  }
+}
+
+// workgroup -> (range, segment) of the ragged grid.  ADLER: the chunk sums go to the range's own run of `sums`; each
+// range has its own chunk grid (first chunk = len mod 5552), and crc32_segment_body's argument that a chunk boundary
+// falls between two 16-byte units holds per range: both grids are congruent to THAT range's len.
+template <bool ADLER>
+__device__ __forceinline__ void crc32_ranges(const uint8_t *__restrict__ arena, const Range *__restrict__ ranges, uint32_t n_ranges,
+                                             const RangesPlan &P, const uint32_t *__restrict__ nib, uint32_t *__restrict__ partials,
+                                             uint2 *__restrict__ sums) {
+  const RangesCall call = *P.call;
+  const uint32_t w = blockIdx.x;
+  if (ranges_wg_idle(call, w)) return;  // (uniform per workgroup, like every return here)
+  const RangeWork k = ranges_work(P.seg_base, P.chunk_base, n_ranges, w);
+  if (k.range >= n_ranges) return;  // (never: w < total_segs)
+  const Range r = ranges[k.range];
+  const uint64_t nseg = range_segs(r.len);
+  if (k.seg >= nseg) return;  // (never: the range found is the one whose run of partials holds w)
+  crc32_segment_body<ADLER>(arena + r.off, r.len, k.seg, nseg, nib, partials + k.slot, ADLER ? (uint32_t *)(sums + k.chunk_at) : nullptr,
+                            adler_n_chunks(r.len));
+}
+__global__ __launch_bounds__(CRC_THREADS, 4) void crc32_ranges_kernel(const uint8_t *__restrict__ arena, const Range *__restrict__ ranges,
+                                                                      uint32_t n_ranges, RangesPlan P, const uint32_t *__restrict__ nib,
+                                                                      uint32_t *__restrict__ partials) {
+  crc32_ranges<false>(arena, ranges, n_ranges, P, nib, partials, nullptr);
+}
+__global__ __launch_bounds__(CRC_THREADS, 4) void crc32_adler_ranges_kernel(const uint8_t *__restrict__ arena,
+                                                                            const Range *__restrict__ ranges, uint32_t n_ranges,
+                                                                            RangesPlan P, const uint32_t *__restrict__ nib,
+                                                                            uint32_t *__restrict__ partials, uint2 *__restrict__ sums) {
+  crc32_ranges<true>(arena, ranges, n_ranges, P, nib, partials, sums);
+}
+
+// A wave per range (the batch is ragged: a workgroup of 1024 per short range would idle, a thread per long range would
+// walk thousands of partials alone): up to 16 partials by lane 0, more by a column per lane and a tree over the lanes.
+__global__ __launch_bounds__(256) void crc32_finish_ranges_kernel(const Range *__restrict__ ranges, uint32_t n_ranges, RangesPlan P,
+                                                                  CrcConsts K, const uint32_t *__restrict__ partials,
+                                                                  RangeResult *__restrict__ results) {
+  const uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63u;
+  if (i >= n_ranges || P.call->bad != 0 || results[i].status != ST_OK) return;  // (uniform per wave)
+  const uint64_t len = ranges[i].len, nseg = range_segs(len), base = P.seg_base[i];
+  uint32_t raw;
+  if (ranges_crc_by_one_lane(nseg)) {
+    if (lane != 0) return;
+    raw = ranges_crc_horner(partials, base, nseg, K.xseg);
+  } else {
+    uint32_t c = ranges_crc_column(partials, base, nseg, lane, xpow8n_tab(K, (uint64_t)CRC_SEG * RANGES_FINISH_LANES));
+    uint32_t xr = K.xseg;  // shift of one segment
+    for (uint32_t s = 1; s < RANGES_FINISH_LANES; s <<= 1) {
+      const uint32_t other = __shfl_down(c, s, 64);
+      c = ranges_crc_tree_step(c, other, xr);  // only lanes with (lane & (2 s - 1)) == 0 are used further
+      xr = gf2_mul(xr, xr);
+    }
+    if (lane != 0) return;
+    raw = c;
+  }
+  results[i].crc32 = ranges_crc_value(raw, xpow8n_tab(K, len));
+}
+
+// A lane per range: the walk over the range's chunk sums, serial per range (a long range's chunks by run, scan and
+// replay as zipc_hip_checksum_device chains them are not built for the batch).
+__global__ __launch_bounds__(256) void adler_finish_ranges_kernel(const Range *__restrict__ ranges, uint32_t n_ranges, RangesPlan P,
+                                                                  const uint2 *__restrict__ sums, int rfc,
+                                                                  RangeResult *__restrict__ results) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_ranges || P.call->bad != 0 || results[i].status != ST_OK) return;
+  results[i].adler32 = ranges_adler_walk(sums, P.chunk_base[i], ranges[i].len, rfc != 0);
 }
 
 }  // namespace zd

@@ -47,6 +47,8 @@ struct zipc_hip_ctx {
   hipStream_t copy_in = nullptr, copy_out = nullptr;  // their H2D / D2H queues (made on first use)
   Buf crc_partials, adler_sums;                   // checksum kernels
   Buf crc_nib;                                    // nibble tables of the CRC merge constants (kernels.h)
+  Buf ranges_plan;                                // the ragged checksum pass: the call-wide word, every range's bases (kernels.h RangesPlan)
+  Buf io_ranges;                                  // ... of host streams: the call's ranges in the source arena
   Buf deflate_scratch;                            // deflate pipeline (deflate.hip)
   Buf parse_scratch;                              // lz_parse by segments: their symbols, paths and verdicts (deflate.hip ParseSegs)
   Buf inflate_scratch;                            // inflate: the span decoder's index, 2304 bytes per stream
@@ -117,6 +119,9 @@ hipError_t crc32_finish_launch(zipc_hip_ctx *ctx, int mode, const StreamDesc *d_
 int crc32_pass(zipc_hip_ctx *ctx, const uint8_t *base, int mode, const StreamDesc *d_descs, StreamResult *d_results,
                size_t n_ranges, uint64_t single_off, uint64_t single_len, size_t max_len, uint32_t *d_single_out,
                size_t partials_at = 0, bool ensured = false);
+// api.hip: the scratch zipc_hip_checksum_batch takes for n_ranges ranges of total_len bytes, for a caller that wants it
+// grown before anything is in flight (a ZIPC_HIP_* status)
+int checksum_ranges_reserve(zipc_hip_ctx *ctx, size_t n_ranges, size_t total_len, int want_adler32);
 // deflate.hip: the probe behind ctx->xchg_ordered
 bool xchg_order_probe(zipc_hip_ctx *ctx);
 // deflate.hip (tests): the links one of the two chain kernels makes of a batch, and how many link slots that takes

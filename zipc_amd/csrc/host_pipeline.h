@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/zipc_hip.h"
+#include "checksum_ranges.h"  // (Range: what the checksum form hands its kernels of a stream)
 #include "forms.h"         // (BLOCKS_BATCH_MIN_DST: from where on a batch's inflate may go by blocks)
 #include "recode_rules.h"  // (recode_open: what inflate is handed of a recode's stream)
 
@@ -207,7 +208,9 @@ inline size_t many_chunks(long setting, uint64_t staged_bytes) {
 
 // what the kernels' step of a many-stream call is.  MANY_RECODE: recode.hip's launch_recode (crc_op: CRC-32); its middle
 // arena is one more buffer of the context, as large as the largest sub-batch needs
-enum ManyOp { MANY_DEFLATE = 0, MANY_INFLATE = 1, MANY_RECODE = 2 };
+// MANY_CHECKSUM: api.hip's zipc_hip_checksum_batch over the sub-batch's sources; there are no destinations (dst_cap is
+// not looked at, the destination arena is empty), and the 16-byte results are all that comes back
+enum ManyOp { MANY_DEFLATE = 0, MANY_INFLATE = 1, MANY_RECODE = 2, MANY_CHECKSUM = 3 };
 
 struct ManyPlan {
   std::vector<zd::StreamDesc> descs;  // every stream's slots: src_off / dst_off are running sums of many_slot
@@ -223,6 +226,7 @@ struct ManyPlan {
   std::vector<zd::StreamDesc> inflate_descs;
   uint64_t mid_arena = 0;
   size_t mid_total_max = 0;
+  std::vector<zd::Range> ranges;      // MANY_CHECKSUM: every stream as a range of the source arena
   size_t K() const { return cut.size() - 1; }
   // where stream i's destination slot begins; i = n: where the arena ends
   uint64_t dst_end(size_t i) const { return i < descs.size() ? descs[i].dst_off : dst_arena_end; }
@@ -242,12 +246,13 @@ inline ManyPlan plan_many(ManyOp op, size_t n, const size_t *src_len, const size
   for (size_t i = 0; i < n; i++) {
     zd::StreamDesc &d = p.descs[i];
     memset(&d, 0, sizeof d);
-    d.src_off = so; d.src_len = src_len[i]; d.dst_off = dof; d.dst_cap = dst_cap[i];
+    const size_t cap = op == MANY_CHECKSUM ? 0 : dst_cap[i];
+    d.src_off = so; d.src_len = src_len[i]; d.dst_off = dof; d.dst_cap = cap;
     if (limit) { d.limit = limit[i]; d.flags = zd::STREAM_HAS_LIMIT; }
     so += many_slot(src_len[i]);
-    dof += many_slot(dst_cap[i]);
+    if (op != MANY_CHECKSUM) dof += many_slot(cap);
     p.max_src = src_len[i] > p.max_src ? src_len[i] : p.max_src;
-    p.max_cap = dst_cap[i] > p.max_cap ? dst_cap[i] : p.max_cap;
+    p.max_cap = cap > p.max_cap ? cap : p.max_cap;
     if (op == MANY_RECODE) p.max_mid = mid_cap[i] > p.max_mid ? mid_cap[i] : p.max_mid;
   }
   p.src_arena_end = so; p.dst_arena_end = dof;
@@ -290,6 +295,10 @@ inline ManyPlan plan_many(ManyOp op, size_t n, const size_t *src_len, const size
       p.mid_arena = mo > p.mid_arena ? mo : p.mid_arena;
       p.mid_total_max = t > p.mid_total_max ? t : p.mid_total_max;
     }
+  }
+  if (op == MANY_CHECKSUM) {
+    p.ranges.resize(n);
+    for (size_t i = 0; i < n; i++) p.ranges[i] = zd::Range{p.descs[i].src_off, p.descs[i].src_len};
   }
   p.ahead = (op == MANY_INFLATE && p.max_cap >= zd::BLOCKS_BATCH_MIN_DST) || (op == MANY_RECODE && p.max_mid >= zd::BLOCKS_BATCH_MIN_DST);
   return p;

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "adler_chain.h"
+#include "checksum_ranges.h"
 #include "zd_common.h"
 
 namespace zd {
@@ -62,5 +63,25 @@ __global__ void adler_runs_a_kernel(const uint2 *__restrict__ sums, uint64_t n, 
 __global__ void adler_replay_kernel(const uint2 *__restrict__ sums, uint64_t n, uint64_t n_chunks, uint64_t per,
                                     AdlerRuns R, uint32_t *__restrict__ amb, uint32_t amb_cap,
                                     uint32_t *__restrict__ out);
+
+// ---- the ragged pass over many ranges of one arena (zipc_hip_checksum_batch; every rule: checksum_ranges.h)
+// what checksum_plan_kernel leaves in the context's scratch: the call-wide word and, per range, where its partials and
+// its chunk sums begin
+struct RangesPlan {
+  RangesCall *call;
+  uint64_t *chunk_base;
+  uint32_t *seg_base;
+};
+__global__ void checksum_plan_kernel(const Range *__restrict__ ranges, uint32_t n_ranges, uint64_t arena_len, uint64_t total_len,
+                                     RangesPlan P, RangeResult *__restrict__ results, uint2 *__restrict__ sums, uint64_t n_sums);
+__global__ void crc32_ranges_kernel(const uint8_t *__restrict__ arena, const Range *__restrict__ ranges, uint32_t n_ranges, RangesPlan P,
+                                    const uint32_t *__restrict__ nib, uint32_t *__restrict__ partials);
+__global__ void crc32_adler_ranges_kernel(const uint8_t *__restrict__ arena, const Range *__restrict__ ranges, uint32_t n_ranges,
+                                          RangesPlan P, const uint32_t *__restrict__ nib, uint32_t *__restrict__ partials,
+                                          uint2 *__restrict__ sums);
+__global__ void crc32_finish_ranges_kernel(const Range *__restrict__ ranges, uint32_t n_ranges, RangesPlan P, CrcConsts K,
+                                           const uint32_t *__restrict__ partials, RangeResult *__restrict__ results);
+__global__ void adler_finish_ranges_kernel(const Range *__restrict__ ranges, uint32_t n_ranges, RangesPlan P,
+                                           const uint2 *__restrict__ sums, int rfc, RangeResult *__restrict__ results);
 
 }  // namespace zd

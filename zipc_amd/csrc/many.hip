@@ -24,6 +24,9 @@ using namespace zd;
 using namespace zd_host;
 
 static_assert(sizeof(StreamResult) == sizeof(zipc_hip_stream_result), "result layout");
+// (the checksum form's results travel through the pipeline in the plain results' place: status on status, crc32 on
+// checksum, adler32 and reserved on out_len)
+static_assert(sizeof(zipc_hip_checksum_result) == sizeof(zipc_hip_stream_result) && sizeof(zipc_hip_range) == sizeof(Range), "checksum layouts");
 
 // ---- the way back: a sub-batch's outputs end to end, written by a kernel -------------------------------------------
 // What a sub-batch made goes into the pinned host buffer by a KERNEL's stores, one output behind the other on 16-byte
@@ -186,6 +189,8 @@ struct ManyDevice {
     PIPE_TRY(hipMemcpyAsync(ctx->io_desc.p, plan.descs.data(), n * sizeof(StreamDesc), hipMemcpyHostToDevice, ctx->copy_in));
     if (op == MANY_RECODE)
       PIPE_TRY(hipMemcpyAsync(ctx->io_rdesc.p, plan.rdescs.data(), n * sizeof(RecodeDesc), hipMemcpyHostToDevice, ctx->copy_in));
+    if (op == MANY_CHECKSUM)
+      PIPE_TRY(hipMemcpyAsync(ctx->io_ranges.p, plan.ranges.data(), n * sizeof(Range), hipMemcpyHostToDevice, ctx->copy_in));
     return ZIPC_HIP_OK;
   }
   int send(size_t g, bool first, uint64_t from, uint64_t to) {
@@ -213,6 +218,11 @@ struct ManyDevice {
       if (st == ZIPC_HIP_OK)
         PIPE_TRY(hipMemcpyAsync((RecodeResult *)ctx->pin_rres.p + lo, (const RecodeResult *)ctx->io_rres.p + lo,
                                 (hi - lo) * sizeof(RecodeResult), hipMemcpyDeviceToHost, ctx->stream));
+    } else if (op == MANY_CHECKSUM) {  // (level: the selectors, bit 0 the CRC-32's, bit 1 the Adler-32's; dr holds zipc_hip_checksum_results)
+      size_t total_g = 0;
+      for (size_t i = lo; i < hi; i++) total_g += plan.descs[i].src_len;
+      st = zipc_hip_checksum_batch(ctx, ctx->io_src.p, plan.src_arena_end, (const zipc_hip_range *)ctx->io_ranges.p + lo,
+                                   (zipc_hip_checksum_result *)dr, hi - lo, total_g, level & 1, level & 2);
     } else if (op == MANY_INFLATE) {  // (with the descriptors it has on the host: no read-back, nothing waited for unless a stream goes by blocks)
       st = launch_inflate(ctx, ctx->io_src.p, ctx->io_dst.p, dd, dr, hi - lo, plan.max_cap, crc_op, plan.descs.data() + lo, first_batch);
     } else {
@@ -285,7 +295,7 @@ static bool many_pointers_ok(const zipc_hip_ctx *ctx, size_t n, const void *cons
 // Everything is allocated before the first sub-batch is under way (growing a buffer synchronises the stream): the
 // staging arenas and their pinned mirrors, the descriptor and result tables, and what the largest sub-batch's kernels
 // need of the context's scratch.
-static int many_reserve(zipc_hip_ctx *ctx, ManyOp op, const ManyPlan &plan, int crc_op, bool packed, bool want_bytes) {
+static int many_reserve(zipc_hip_ctx *ctx, ManyOp op, const ManyPlan &plan, int level, int crc_op, bool packed, bool want_bytes) {
   const size_t n = plan.descs.size();
   HIP_TRY(ctx, ctx->ensure(ctx->io_src, plan.src_arena_end + 64));
   HIP_TRY(ctx, ctx->ensure(ctx->io_dst, plan.dst_arena_end + 64));
@@ -306,7 +316,11 @@ static int many_reserve(zipc_hip_ctx *ctx, ManyOp op, const ManyPlan &plan, int 
     st = zipc_hip_reserve(ctx, plan.n_max, plan.max_mid, plan.mid_total_max);
     if (st) return st;
   }
-  if (op == MANY_DEFLATE) {
+  if (op == MANY_CHECKSUM) {  // (level: launch()'s selectors)
+    HIP_TRY(ctx, ctx->ensure(ctx->io_ranges, n * sizeof(Range)));
+    const int st = checksum_ranges_reserve(ctx, plan.n_max, plan.total_max, level & 2);
+    if (st) return st;
+  } else if (op == MANY_DEFLATE) {
     const int st = zipc_hip_reserve(ctx, plan.n_max, plan.max_src, plan.total_max);
     if (st) return st;
   } else {
@@ -337,7 +351,7 @@ static void many_report(const ManyDevice &dev, const ManyTimes &times, double ms
   const size_t K = plan.K();
   fprintf(stderr, "zipc_hip %s_many n=%zu src_arena=%llu dst_arena=%llu ms: setup %.2f feed %.2f (of it gather %.2f) "
                   "scatter %.2f whole %.2f (threads %zu sub-batches %zu)\n",
-          dev.op == MANY_RECODE ? "recode" : dev.op == MANY_INFLATE ? "inflate" : "deflate", plan.descs.size(),
+          dev.op == MANY_CHECKSUM ? "checksum" : dev.op == MANY_RECODE ? "recode" : dev.op == MANY_INFLATE ? "inflate" : "deflate", plan.descs.size(),
           (unsigned long long)plan.src_arena_end, (unsigned long long)plan.dst_arena_end, ms_setup, times.ms_feed,
           times.ms_gather, times.ms_scatter, ms_whole, host_threads(), K);
   for (size_t g = 0; g < K; g++) {
@@ -380,7 +394,7 @@ static int many_streams(zipc_hip_ctx *ctx, ManyOp op, size_t n, const void *cons
   if (op == MANY_DEFLATE && plan.max_src > MAX_STREAM_LEN) return ZIPC_HIP_ERR_INVALID_ARG;  // (inflate reports it per stream)
   if (op == MANY_RECODE && plan.max_mid > MAX_STREAM_LEN) return ZIPC_HIP_ERR_INVALID_ARG;   // (zipc_hip_recode_batch's rule)
   const bool packed = tun.host_pack && want_bytes;  // (false: whole destination slots by the copy engine)
-  int st = many_reserve(ctx, op, plan, crc_op, packed, want_bytes);
+  int st = many_reserve(ctx, op, plan, level, crc_op, packed, want_bytes);
   if (st) return st;
   ManyDevice dev(ctx, op, plan, level, crc_op, packed, want_bytes, tun.host_timing);
   st = dev.ready();
@@ -444,6 +458,29 @@ static int recode_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, cons
     if (p.status == RESULT_UNSET) results[i] = zipc_hip_recode_result{(uint32_t)(st ? st : ZIPC_HIP_ERR_HIP), 0, 0, 0, 0, 0};  // (the pipeline never ran)
     else if (back && back[i].status == p.status && back[i].out_len == p.out_len) results[i] = back[i];
     else results[i] = zipc_hip_recode_result{p.status, 0, 0, 0, 0, 0};
+  }
+  return st;
+}
+
+// zipc_hip_checksum_many: many_streams with the ragged checksum pass as its kernels' step and nothing but results on
+// the way back.  The pipeline carries plain results: a checksum result lies in one's place (status, crc32 as checksum,
+// adler32 as out_len's low half), so the capacities it is told are 2^32 - 1 -- it takes an out_len above dst_cap for an
+// overrun -- and plan_many gives the checksum form no destination arena whatever they say.  The selectors travel as
+// `level` (bit 0: CRC-32, bit 1: Adler-32).  results[] is defined on every return.
+static int checksum_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len, int want_crc32, int want_adler32,
+                         zipc_hip_checksum_result *results) {
+  bool ok = ctx && (want_crc32 || want_adler32) && (n == 0 || (src && src_len && results));
+  for (size_t i = 0; ok && i < n; i++) ok = src[i] || !src_len[i];
+  if (!ok) return fill_results(results, n, ZIPC_HIP_ERR_INVALID_ARG);
+  if (n == 0) return ZIPC_HIP_OK;
+  const std::vector<size_t> caps(n, (size_t)0xFFFFFFFFu);
+  std::vector<zipc_hip_stream_result> plain(n, zipc_hip_stream_result{RESULT_UNSET, 0, 0});
+  const int st = many_streams(ctx, MANY_CHECKSUM, n, src, src_len, nullptr, (want_crc32 ? 1 : 0) | (want_adler32 ? 2 : 0), ZIPC_HIP_CRC_NOP,
+                              nullptr, caps.data(), plain.data(), false);
+  for (size_t i = 0; i < n; i++) {
+    const zipc_hip_stream_result &p = plain[i];
+    if (p.status == RESULT_UNSET) results[i] = zipc_hip_checksum_result{(uint32_t)(st ? st : ZIPC_HIP_ERR_HIP), 0, 0, 0};  // (the pipeline never ran)
+    else results[i] = zipc_hip_checksum_result{p.status, p.checksum, (uint32_t)p.out_len, 0};
   }
   return st;
 }
@@ -525,6 +562,10 @@ int zipc_hip_recode_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, co
                          const uint32_t *expect_crc32, const size_t *mid_cap, int level, void *const *dst, const size_t *dst_cap,
                          zipc_hip_recode_result *results) {
   return many_guarded(ctx, n, results, [&] { return recode_many(ctx, n, src, src_len, limit, expect_crc32, mid_cap, level, dst, dst_cap, results); });
+}
+int zipc_hip_checksum_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len, int want_crc32, int want_adler32,
+                           zipc_hip_checksum_result *results) {
+  return many_guarded(ctx, n, results, [&] { return checksum_many(ctx, n, src, src_len, want_crc32, want_adler32, results); });
 }
 int zipc_hip_zlib_decompress_many(zipc_hip_ctx *ctx, size_t n, const void *const *src, const size_t *src_len, const size_t *limit,
                                   void *const *dst, const size_t *dst_cap, zipc_hip_stream_result *results) {

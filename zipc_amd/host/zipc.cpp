@@ -1,6 +1,7 @@
 // zipc.cpp -- see zipc.hpp.  Row references are to /root/reference/src/zipc.ml.
 #include "zipc.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 
@@ -527,6 +528,9 @@ std::vector<std::pair<Fpath::t, Result<std::string>>> Archive::extract_all() con
   std::vector<std::pair<Fpath::t, Result<std::string>>> out;
   std::vector<zipc_deflate::ManyItem> items;
   std::vector<std::size_t> slot;  // index in out of each batched (Deflate) item
+  std::vector<zipc_deflate::ManyItem> stored;  // the stored members: their CRC-32s in one call beside the deflated batch
+  std::vector<std::size_t> stored_slot;
+  std::vector<const File *> stored_files;
   for (const auto &kv : members_) {
     const Member &m = kv.second;
     if (m.is_dir()) continue;
@@ -539,9 +543,24 @@ std::vector<std::pair<Fpath::t, Result<std::string>>> Archive::extract_all() con
       items.push_back(it);
       slot.push_back(out.size());
       out.push_back({m.path(), Result<std::string>::Error("")});
+    } else if (f.compression_().kind == compression::Stored && !f.is_encrypted() && f.start() <= f.compressed_bytes().size()) {
+      zipc_deflate::ManyItem it;  // (the bytes compressed_bytes_to_binary_string gives: substr ends with the string)
+      it.data = f.compressed_bytes().data() + f.start();
+      it.len = std::min((std::size_t)f.compressed_size(), f.compressed_bytes().size() - f.start());
+      stored.push_back(it);
+      stored_slot.push_back(out.size());
+      stored_files.push_back(&f);
+      out.push_back({m.path(), Result<std::string>::Error("")});
     } else {
-      out.push_back({m.path(), f.to_binary_string()});  // stored, encrypted, unsupported: the single-member path
+      out.push_back({m.path(), f.to_binary_string()});  // encrypted, unsupported: the single-member path
     }
+  }
+  auto crcs = zipc_deflate::crc_32_many(stored);
+  for (std::size_t k = 0; k < stored.size(); k++) {  // (File::to_binary_string's steps for a stored member)
+    auto &dst = out[stored_slot[k]].second;
+    if (!crcs[k].ok) { dst = Result<std::string>::Error(crcs[k].error); continue; }
+    auto c = zipc_deflate::Crc_32::check(stored_files[k]->decompressed_crc_32(), crcs[k].checksum);
+    dst = c.ok ? Result<std::string>::Ok(stored_files[k]->compressed_bytes_to_binary_string()) : Result<std::string>::Error(c.error);
   }
   auto res = zipc_deflate::inflate_and_crc_32_many(items);
   std::size_t k = 0;
@@ -566,6 +585,9 @@ std::vector<std::pair<Fpath::t, Result<Unit>>> Archive::test_all() const {
   std::vector<zipc_deflate::ManyItem> items;
   std::vector<std::size_t> slot;
   std::vector<const File *> files;
+  std::vector<zipc_deflate::ManyItem> stored;  // the stored members: their CRC-32s in one call beside the deflated batch
+  std::vector<std::size_t> stored_slot;
+  std::vector<const File *> stored_files;
   for (const auto &kv : members_) {
     const Member &m = kv.second;
     if (m.is_dir()) continue;
@@ -579,10 +601,25 @@ std::vector<std::pair<Fpath::t, Result<Unit>>> Archive::test_all() const {
       slot.push_back(out.size());
       files.push_back(&f);
       out.push_back({m.path(), Result<Unit>::Error("")});
+    } else if (f.compression_().kind == compression::Stored && !f.is_encrypted() && f.start() <= f.compressed_bytes().size()) {
+      zipc_deflate::ManyItem it;  // (the bytes compressed_bytes_to_binary_string gives: substr ends with the string)
+      it.data = f.compressed_bytes().data() + f.start();
+      it.len = std::min((std::size_t)f.compressed_size(), f.compressed_bytes().size() - f.start());
+      stored.push_back(it);
+      stored_slot.push_back(out.size());
+      stored_files.push_back(&f);
+      out.push_back({m.path(), Result<Unit>::Error("")});
     } else {
-      auto r = f.to_binary_string();  // stored, encrypted, unsupported: the single-member path
+      auto r = f.to_binary_string();  // encrypted, unsupported: the single-member path
       out.push_back({m.path(), r.ok ? Result<Unit>::Ok(Unit{}) : Result<Unit>::Error(r.error)});
     }
+  }
+  auto crcs = zipc_deflate::crc_32_many(stored);
+  for (std::size_t k = 0; k < stored.size(); k++) {
+    auto &dst = out[stored_slot[k]].second;
+    if (!crcs[k].ok) { dst = Result<Unit>::Error(crcs[k].error); continue; }
+    auto c = zipc_deflate::Crc_32::check(stored_files[k]->decompressed_crc_32(), crcs[k].checksum);
+    dst = c.ok ? Result<Unit>::Ok(Unit{}) : Result<Unit>::Error(c.error);
   }
   auto res = zipc_deflate::inflate_and_crc_32_many_check(items);
   for (std::size_t k = 0; k < items.size(); k++) {

@@ -421,6 +421,29 @@ std::vector<ManyResult> inflate_and_crc_32_many_check(const std::vector<ManyItem
   return out;
 }
 
+std::vector<ManyResult> crc_32_many(const std::vector<ManyItem> &items) {
+  const std::size_t n = items.size();
+  std::vector<ManyResult> out(n);
+  std::vector<const void *> src(n);
+  std::vector<std::size_t> len(n);
+  for (std::size_t i = 0; i < n; i++) {
+    src[i] = items[i].data;
+    len[i] = items[i].len;
+  }
+  std::vector<zipc_hip_checksum_result> res(n);
+  over_devices(items, [&](zipc_hip_ctx *ctx, std::size_t lo, std::size_t hi) {
+    const int st = zipc_hip_checksum_many(ctx, hi - lo, src.data() + lo, len.data() + lo, 1, 0, res.data() + lo);
+    if (st) throw std::runtime_error(std::string("zipc_hip_checksum_many: ") + message(st) + " (" + zipc_hip_last_error(ctx) + ")");
+  });
+  for (std::size_t i = 0; i < n; i++) {
+    throw_if_library_failure((int)res[i].status);
+    out[i].ok = res[i].status == ZIPC_HIP_OK;
+    out[i].checksum = res[i].crc32;
+    if (!out[i].ok) out[i].error = message((int)res[i].status);
+  }
+  return out;
+}
+
 std::vector<ManyResult> inflate_and_crc_32_many(const std::vector<ManyItem> &items) {
   const std::size_t n = items.size();
   std::vector<ManyResult> out(n);

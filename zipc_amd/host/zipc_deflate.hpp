@@ -149,6 +149,10 @@ std::vector<ManyResult> inflate_and_crc_32_many(const std::vector<ManyItem> &ite
 // ... for its verdict alone: ok / error and the CRC-32 found, value left empty -- nothing but the results comes back
 // from the device (zipc_hip_inflate_many_check: what testing an archive takes)
 std::vector<ManyResult> inflate_and_crc_32_many_check(const std::vector<ManyItem> &items);
+// Crc_32.string of every item in one go (zipc_hip_checksum_many): checksum = the CRC-32, value left empty, every item ok.
+// What an archive's STORED members take to be tested or extracted: one pass over their bytes per call, not a round trip
+// to the device per member.
+std::vector<ManyResult> crc_32_many(const std::vector<ManyItem> &items);
 
 // inflate_and_crc_32, Crc_32.check and deflate of every item in one go (zipc_hip_recode_many): what the reference's
 // `recode` does to a member (test/zipc_tool.ml:437-545, test/test.ml:58-74 redeflate_recode), with the decompressed
