@@ -424,6 +424,56 @@ int zipc_hip_zlib_size_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
                                     const zipc_hip_stream_desc *d_descs,
                                     zipc_hip_stream_result *d_results, size_t n_streams);
 
+/* Decode into ONE arena laid out on the device: size-then-decode (above) as one call, for a batch that is on the device
+ * and whose caller has no destinations of their own.  The call sizes every stream, lays the outputs end to end in
+ * d_dst_arena, decodes them there and says where each one went; nothing is read back for the layout.  All pointers are
+ * DEVICE pointers.  Of a descriptor src_off, src_len, limit and flags are read; dst_off and dst_cap are not looked at, as
+ * in the sizing forms.  The two arenas must not overlap.
+ * The layout rule (csrc/packed_layout.h):
+ *   - a stream TAKES ROOM iff it is sized ZIPC_HIP_OK (the sizing forms' checks of flags and src_len included) and its
+ *     size is at most max_out_len.  A stream sized above max_out_len reports ZIPC_HIP_ERR_INVALID_ARG, one that is not
+ *     sized OK that status; neither takes room, both report out_len 0 and dst_off 0.
+ *   - the streams that take room lie in index order: dst_off[i] = the sum over the roomed streams j < i of
+ *     align_up(out_len[j], align).  align: a power of two in 1..4096.  Every sum is 64-bit.  Padding is never written.
+ *   - a roomed stream FITS iff dst_off[i] + out_len[i] <= dst_arena_len.  One that does not reports
+ *     ZIPC_HIP_ERR_DST_TOO_SMALL with out_len 0 and the dst_off the rule gave it; nothing of it is decoded, and nothing
+ *     is written at or behind dst_arena_len.
+ *   - d_need[0], if d_need is given, receives the end (dst_off + out_len) of the last roomed stream, whether it fit or
+ *     not, and 0 if no stream took room: the arena length with which every roomed stream fits.  A caller that came up
+ *     short retries once with exactly that.
+ * The defining property: a roomed stream that fits gets status, checksum, out_len and the bytes in the arena that
+ * zipc_hip_inflate_batch gives for the same src_off, src_len, limit and flags with that dst_off, dst_cap = out_len and
+ * this call's crc_op.
+ * Launches: below max_out_len = 256 KiB the streams are sized by zipc_hip_inflate_size_batch's one launch and the whole
+ * call is enqueued on the context's stream and never synchronised (a call of ONE stream: below 40 KiB, where
+ * zipc_hip_inflate_batch's own block path begins for one stream); from 256 KiB on they are sized as
+ * zipc_hip_inflate_size_blocks_batch sizes them and decoded as zipc_hip_inflate_batch decodes from there on, and the call
+ * synchronises where those two do.  zipc_hip_last_size_blocks and zipc_hip_last_inflate_blocks say what they say after
+ * those calls.
+ * A null ctx, d_descs or d_results, a null d_dst_arena with dst_arena_len != 0, n_streams above 0x7FFFFFFF, an align that
+ * is no power of two in 1..4096, max_out_len above ZIPC_HIP_MAX_STREAM_LEN (one stored stream beyond 4 GiB is not offered
+ * here) or a crc_op outside the enum fails the call with ZIPC_HIP_ERR_INVALID_ARG.  n_streams == 0 is ZIPC_HIP_OK,
+ * enqueues nothing and does not write d_need. */
+typedef struct {            /* 32 bytes */
+  uint32_t status;    /* ZIPC_HIP_OK or the stream's own error */
+  uint32_t checksum;  /* per crc_op, as zipc_hip_inflate_batch reports it */
+  uint64_t out_len;   /* decompressed bytes at dst_off; 0 unless OK */
+  uint64_t dst_off;   /* where the stream's room begins in the destination arena; 0 if it was given none */
+  uint64_t reserved;  /* 0 */
+} zipc_hip_packed_result;
+int zipc_hip_inflate_packed_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, size_t dst_arena_len,
+                                  const zipc_hip_stream_desc *d_descs, zipc_hip_packed_result *d_results,
+                                  size_t n_streams, size_t max_out_len, size_t align, int crc_op,
+                                  uint64_t *d_need /* may be NULL */);
+/* The same for WHOLE zlib streams, through the container's open and close of zipc_hip_zlib_decompress_batch, with the
+ * context's Adler-32 flavour: a stream that fails its header check (or is shorter than 6 bytes) reports that status and
+ * takes no room; one that inflates to another Adler-32 than it says reports ZIPC_HIP_ERR_CHECKSUM with checksum = the
+ * value FOUND, out_len 0 and the dst_off it was given -- its bytes were decoded. */
+int zipc_hip_zlib_decompress_packed_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, size_t dst_arena_len,
+                                          const zipc_hip_stream_desc *d_descs, zipc_hip_packed_result *d_results,
+                                          size_t n_streams, size_t max_out_len, size_t align,
+                                          uint64_t *d_need /* may be NULL */);
+
 /* Recode on the device: every stream of the source arena -- a raw deflate stream, a ZIP member's bytes -- is inflated
  * into its room in a MIDDLE arena, its CRC-32 taken there and compared where the descriptor expects one, and what it
  * inflated to is deflated at `level` into its destination slot: Zipc_deflate.inflate_and_crc_32, Crc_32.check and

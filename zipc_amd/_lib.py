@@ -54,6 +54,11 @@ class RecodeResult(C.Structure):
                 ("stage", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class PackedResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("checksum", C.c_uint32), ("out_len", C.c_uint64), ("dst_off", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
 class Range(C.Structure):
     _fields_ = [("off", C.c_uint64), ("len", C.c_uint64)]
 
@@ -116,6 +121,8 @@ SYMBOLS = [
     ("zipc_hip_zlib_size_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_inflate_size_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_zlib_size_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
+    ("zipc_hip_inflate_packed_batch", C.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _SZ, C.c_int, _P]),
+    ("zipc_hip_zlib_decompress_packed_batch", C.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _SZ, _P]),
     ("zipc_hip_recode_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int]),
     ("zipc_hip_recode_many", C.c_int, [_P, _SZ, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("zipc_hip_checksum_device", C.c_int, [_P, _P, _SZ, C.c_int, C.c_int, _P]),

@@ -25,6 +25,9 @@ RECODE_DESC_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("mid_off"
 RECODE_RESULT_DTYPE = np.dtype([("status", "<u4"), ("checksum", "<u4"), ("out_len", "<u8"), ("mid_len", "<u8"),
                                 ("stage", "<u4"), ("reserved", "<u4")])
 assert RECODE_DESC_DTYPE.itemsize == 64 and RECODE_RESULT_DTYPE.itemsize == 32
+# zipc_hip_packed_result
+PACKED_RESULT_DTYPE = np.dtype([("status", "<u4"), ("checksum", "<u4"), ("out_len", "<u8"), ("dst_off", "<u8"), ("reserved", "<u8")])
+assert PACKED_RESULT_DTYPE.itemsize == 32
 # zipc_hip_range / zipc_hip_checksum_result
 RANGE_DTYPE = np.dtype([("off", "<u8"), ("len", "<u8")])
 CHECKSUM_RESULT_DTYPE = np.dtype([("status", "<u4"), ("crc32", "<u4"), ("adler32", "<u4"), ("reserved", "<u4")])
@@ -158,6 +161,47 @@ def zlib_size_blocks_batch(ctx: Context, src, descs_dev, results_dev, n_streams:
     st = lib().zipc_hip_zlib_size_blocks_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
     ctx.check(st)
     ctx.synchronize()
+
+
+def packed_results_from_device(t) -> np.ndarray:
+    return t.cpu().numpy().view(PACKED_RESULT_DTYPE).copy()
+
+
+def _packed_args(dst, dst_arena_len, need_dev):
+    return (dst.data_ptr() if dst is not None else None, dst.numel() if dst_arena_len is None else dst_arena_len,
+            need_dev.data_ptr() if need_dev is not None else None)
+
+
+def inflate_packed_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, max_out_len: int, align: int = 1,
+                         crc_op: int = CRC_NOP, need_dev=None, dst_arena_len=None, sync: bool = True):
+    """zipc_hip_inflate_packed_batch: every raw deflate stream of `src` is sized, given room in `dst` by the layout rule of
+    include/zipc_hip.h (in index order, lengths padded to `align`) and inflated there, in one call; results_dev: a uint8
+    cuda tensor of PACKED_RESULT_DTYPE records (status, checksum, out_len and the dst_off the stream was given);
+    need_dev: None, or a cuda tensor of 8 bytes that receives the arena length with which every stream fits;
+    dst_arena_len: the arena's length where it is not the whole of `dst`.  dst_off / dst_cap of the descriptors are not
+    looked at.  Below max_out_len = 256 KiB the call only enqueues."""
+    if sync:
+        _sync_torch(src)
+    d, dlen, need = _packed_args(dst, dst_arena_len, need_dev)
+    st = lib().zipc_hip_inflate_packed_batch(ctx.handle, src.data_ptr(), d, dlen, descs_dev.data_ptr(), results_dev.data_ptr(),
+                                             n_streams, max_out_len, align, crc_op, need)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def zlib_decompress_packed_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, max_out_len: int, align: int = 1,
+                                 need_dev=None, dst_arena_len=None, sync: bool = True):
+    """zipc_hip_zlib_decompress_packed_batch: the same for whole zlib streams (the context's Adler-32 flavour): a header
+    failure takes no room, a checksum mismatch reports the value found, no bytes and the dst_off it was given."""
+    if sync:
+        _sync_torch(src)
+    d, dlen, need = _packed_args(dst, dst_arena_len, need_dev)
+    st = lib().zipc_hip_zlib_decompress_packed_batch(ctx.handle, src.data_ptr(), d, dlen, descs_dev.data_ptr(),
+                                                     results_dev.data_ptr(), n_streams, max_out_len, align, need)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
 
 
 def recode_results_from_device(t) -> np.ndarray:
@@ -320,6 +364,7 @@ def compact_descs(results: np.ndarray, descs: np.ndarray, dst_cap_of_out, limit_
 __all__ = ["DESC_DTYPE", "RESULT_DTYPE", "RECODE_DESC_DTYPE", "RECODE_RESULT_DTYPE", "make_descs", "make_recode_descs", "to_device",
            "results_from_device", "recode_results_from_device", "recode_batch",
            "inflate_batch", "deflate_batch", "inflate_size_batch", "zlib_size_batch", "inflate_size_blocks_batch", "zlib_size_blocks_batch", "zlib_decompress_batch", "zlib_compress_batch", "checksum_device", "reserve",
+           "PACKED_RESULT_DTYPE", "inflate_packed_batch", "zlib_decompress_packed_batch", "packed_results_from_device",
            "RANGE_DTYPE", "CHECKSUM_RESULT_DTYPE", "make_ranges", "checksum_results_from_device", "checksum_batch", "checksum_many",
            "deflate_bound", "zlib_bound",
            "uniform_layout", "compact_descs", "OK"]

@@ -1,6 +1,6 @@
 // api.hip -- the C ABI of include/zipc_hip.h, all of it but the many-stream host forms (many.hip): the context and its
 // scratch, tuning(), the CRC-32 pass and the checksum launches, the batch forms as argument checks around the launchers
-// of deflate.hip, inflate.hip, zlib.hip and recode.hip (ctx.h), and the one-stream host forms.
+// of deflate.hip, inflate.hip, zlib.hip, recode.hip and packed.hip (ctx.h), and the one-stream host forms.
 //
 // Host forms stage one stream through device scratch and run the same kernels as
 // the batch forms (a batch of one).  Nothing here computes on the CPU: with no
@@ -14,6 +14,7 @@
 #include <vector>
 #include "ctx.h"
 #include "deflate_scratch.h"
+#include "packed_layout.h"
 #include "recode_rules.h"
 #include "tuning.h"
 #include "zlib_container.h"
@@ -25,6 +26,7 @@ static_assert(sizeof(zipc_hip_stream_result) == sizeof(StreamResult), "result la
 static_assert(ZIPC_HIP_BLOCKS_MIN_SRC == BLOCKS_MIN_SRC, "forms.h");
 static_assert(sizeof(zipc_hip_recode_desc) == sizeof(RecodeDesc) && sizeof(RecodeDesc) == 64, "recode desc layout");
 static_assert(sizeof(zipc_hip_recode_result) == sizeof(RecodeResult) && sizeof(RecodeResult) == 32, "recode result layout");
+static_assert(sizeof(zipc_hip_packed_result) == sizeof(PackedResult) && sizeof(PackedResult) == 32, "packed result layout");
 static_assert(ZIPC_HIP_STREAM_EXPECT_CRC32 == STREAM_EXPECT_CRC32 && ZIPC_HIP_ERR_CHECKSUM == ST_CHECKSUM, "recode constants");
 
 // ---- context internals -------------------------------------------------------
@@ -318,6 +320,7 @@ void zipc_hip_destroy(zipc_hip_ctx *ctx) {
   free_buf(ctx->size_descs); free_buf(ctx->size_head); free_buf(ctx->size_rest);
   free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre);
   free_buf(ctx->recode_descs); free_buf(ctx->recode_res); free_buf(ctx->recode_verdicts);
+  free_buf(ctx->packed_descs); free_buf(ctx->packed_res); free_buf(ctx->packed_verdicts);
   free_buf(ctx->io_mid); free_buf(ctx->io_rdesc); free_buf(ctx->io_rres);
   free_buf(ctx->stored_list);
   free_buf(ctx->chain_check_links);
@@ -764,6 +767,28 @@ int zipc_hip_zlib_size_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena, 
   st = launch_inflate_size_blocks(ctx, d_src_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, d_results, n_streams, nullptr);
   if (st) return st;
   return launch_zlib_close_size(ctx, d_results, n_streams);
+}
+
+// ---- decode into one arena laid out on the device (packed_layout.h has the rules; packed.hip the two kernels and the sequence) --
+
+int zipc_hip_inflate_packed_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, size_t dst_arena_len,
+                                  const zipc_hip_stream_desc *d_descs, zipc_hip_packed_result *d_results, size_t n_streams,
+                                  size_t max_out_len, size_t align, int crc_op, uint64_t *d_need) {
+  if (!ctx || !d_descs || !d_results) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (const uint32_t st = packed_call_status(d_dst_arena == nullptr, dst_arena_len, n_streams, max_out_len, align, crc_op)) return (int)st;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  return launch_inflate_packed(ctx, d_src_arena, d_dst_arena, dst_arena_len, d_descs, d_results, n_streams, max_out_len, align, crc_op,
+                               d_need, false);
+}
+
+int zipc_hip_zlib_decompress_packed_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, size_t dst_arena_len,
+                                          const zipc_hip_stream_desc *d_descs, zipc_hip_packed_result *d_results, size_t n_streams,
+                                          size_t max_out_len, size_t align, uint64_t *d_need) {
+  if (!ctx || !d_descs || !d_results) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (const uint32_t st = packed_call_status(d_dst_arena == nullptr, dst_arena_len, n_streams, max_out_len, align, zlib_crc_op(ctx))) return (int)st;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  return launch_inflate_packed(ctx, d_src_arena, d_dst_arena, dst_arena_len, d_descs, d_results, n_streams, max_out_len, align,
+                               zlib_crc_op(ctx), d_need, true);
 }
 
 int zipc_hip_zlib_compress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,

@@ -58,6 +58,7 @@ struct zipc_hip_ctx {
   Buf size_descs, size_head, size_rest;                      // sizing by blocks: the call's descriptors with no destination (dst_off 0, dst_cap the longest stream's), the heads' results and span slots, the one-wave results of the streams left
   Buf zlib_descs, zlib_pre;                       // the zlib batch forms: the descriptors the codec runs with, the container checks' verdicts (zlib.hip)
   Buf recode_descs, recode_res, recode_verdicts;  // the recode forms: the descriptors inflate, then deflate run with, their results, what is known of a stream between the steps (recode.hip)
+  Buf packed_descs, packed_res, packed_verdicts;  // the packed decode forms: the descriptors inflate runs with, the sizing pass's results and then inflate's, the layout's verdicts (packed.hip)
   Buf io_mid, io_rdesc, io_rres;                  // ... of host streams: the middle arena of a sub-batch, the call's recode descriptors and results
   Buf pin_rres;                                   // ... the results as they come back (pinned)
   Buf chain_check_links;                          // lz_chain's run-time check: the links the exchange kernel made of a batch's first streams
@@ -160,6 +161,14 @@ int recode_reserve(zipc_hip_ctx *ctx, size_t n);
 int launch_recode(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_mid_arena, void *d_dst_arena, const RecodeDesc *d_descs,
                   RecodeResult *d_results, StreamResult *d_plain, size_t n, size_t max_mid_cap, size_t total_mid_cap, int level,
                   const StreamDesc *h_inflate_descs, bool first_of_call);
+// packed.hip: zipc_hip_inflate_packed_batch / zipc_hip_zlib_decompress_packed_batch behind their argument checks (a ZIPC_HIP_*
+// status): (zlib: open ->) the sizing pass packed_layout.h names -> layout -> inflate -> close on ctx->stream; crc_op: the
+// caller's, or zlib_crc_op's.  packed_reserve: its scratch for n streams, for a caller that wants it grown before anything
+// is in flight
+int packed_reserve(zipc_hip_ctx *ctx, size_t n);
+int launch_inflate_packed(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, size_t dst_arena_len,
+                          const zipc_hip_stream_desc *d_descs, zipc_hip_packed_result *d_results, size_t n, size_t max_out_len,
+                          size_t align, int crc_op, uint64_t *d_need, bool zlib);
 // zlib.hip: the checksum the zlib forms of this context ask the codec for, and the container's kernels around the codec's
 // (a ZIPC_HIP_* status each): open leaves the codec's descriptors in ctx->zlib_descs and the checks' verdicts in ctx->zlib_pre
 int zlib_crc_op(const zipc_hip_ctx *ctx);
