@@ -306,7 +306,20 @@ typedef struct zipc_hip_stream_result_s {
 /* max_dst_cap: upper bound of dst_cap over the batch (sizes the CRC-32 pass). A stream
  * whose output is longer than that reports ZIPC_HIP_ERR_INVALID_ARG in its result when a
  * CRC-32 is asked for (its checksum would cover only a part). A descriptor with src_len or
- * dst_cap above ZIPC_HIP_MAX_STREAM_LEN reports ZIPC_HIP_ERR_INVALID_ARG in its own result. */
+ * dst_cap above ZIPC_HIP_MAX_STREAM_LEN reports ZIPC_HIP_ERR_INVALID_ARG in its own result.
+ * dst_cap, the room of a stream -- the same in every form the library takes (a wave per stream, a wave per block) and in
+ * every call that inflates (the host forms, the zlib forms, zipc_hip_inflate_packed_batch, zipc_hip_recode_batch with its
+ * mid_cap): nothing is written in front of dst_off or behind dst_off + dst_cap, whatever the status.  Bytes between
+ * out_len (or limit) and dst_cap may be written.  A stream that inflates to N bytes fits iff N <= R, R = min(limit,
+ * dst_cap) (no limit: dst_cap); one that does not fit reports, with out_len 0 (what lies in its room is
+ * unspecified):
+ *     limit     dst_cap     status when R < N
+ *     none      R           ZIPC_HIP_ERR_DST_TOO_SMALL
+ *     R         R           ZIPC_HIP_ERR_SIZE_EXCEEDED
+ *     R         above R     ZIPC_HIP_ERR_SIZE_EXCEEDED
+ *     above N   R           ZIPC_HIP_ERR_DST_TOO_SMALL
+ * (a limit in R < limit < N with dst_cap = R: ZIPC_HIP_ERR_SIZE_EXCEEDED where the symbol that does not fit ends behind
+ * the limit, else ZIPC_HIP_ERR_DST_TOO_SMALL).  tests/test_gpu_inflate_room.py holds every form to this with guard bytes. */
 int zipc_hip_inflate_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
                            const zipc_hip_stream_desc *d_descs,
                            zipc_hip_stream_result *d_results, size_t n_streams,

@@ -49,48 +49,8 @@ sys.path.insert(0, util.GOLDEN)
 import inflate_rules as R  # noqa: E402
 
 # a case's items: (name, stream, the plain bytes or None for a stream that is not valid, whether zlib made it)
-LETTERS = b"abcdefghijklmn"
-# litlen lengths: 14 letters of 4 bits, then one symbol each of 4 .. 14 bits and two of 15 (a complete code)
-LL = [0] * 285
-for _c in LETTERS:
-    LL[_c] = 4
-for _sym, _n in ((258, 4), (259, 5), (261, 6), (262, 7), (263, 8), (257, 9), (ord("o"), 10), (ord("p"), 11), (ord("q"), 12),
-                 (ord("r"), 13), (256, 14), (284, 15), (ord("s"), 15)):
-    LL[_sym] = _n
-assert sum(2.0 ** -n for n in LL if n) == 1.0
-DL_LONG = [i + 1 for i in range(14)] + [0] * 14 + [15, 15]  # distance symbol 28 (13 extra bits): a 15-bit code
-assert sum(2.0 ** -n for n in DL_LONG if n) == 1.0
-
-
-class _Block:
-    """one final dynamic block in LL and the given distance lengths, written symbol by symbol"""
-
-    def __init__(self, dl):
-        self.w, self.out = R.Writer(), R.Out()
-        R.emit_block(self.w, self.out, R.dynamic([], ll=LL, dl=dl, eob=False), True)
-        rev = lambda code, n: (int(format(code, "0%db" % n)[::-1], 2), n)
-        self.lc = {s: rev(*c) for s, c in R.canonical(LL).items()}
-        self.dc = {s: rev(*c) for s, c in R.canonical(dl).items()}
-
-    def lits(self, data):
-        f, lc = self.w.field, self.lc
-        for b in data:
-            f(*lc[b])
-        self.out.b += data
-
-    def match(self, length, dist):
-        """-> the bit the match's first code starts at"""
-        at = self.w.pos
-        ls, le = R.len_sym(length)
-        ds, de = R.dist_sym(dist)
-        self.w.field(*self.lc[ls]); self.w.field(le, R.LEXT[ls - 257])
-        self.w.field(*self.dc[ds]); self.w.field(de, R.DEXT[ds])
-        self.out.match(length, dist)
-        return at
-
-    def done(self):
-        self.w.field(*self.lc[256])
-        return self.w.bytes(), (None if self.out.bad else bytes(self.out.b))
+# (the 4-bit-letter code and the block writer live in tests/inflate_room_cases.py, which builds on them too)
+from inflate_room_cases import DL_LONG, LETTERS, LL, Block as _Block  # noqa: E402,F401
 
 
 def _letters(r, n):

@@ -429,7 +429,8 @@ def header_fuzz_streams(seed, n_random, n_flips):
 
 def gpu_inflate_batch(ctx, streams, caps, has_limit, limits, crc_op):
     """One inflate_batch launch over `streams` through the C ABI: [(status, bytes, checksum)].
-    limits[i] is the ?decompressed_size of stream i where has_limit[i]; caps[i] its dst_cap."""
+    limits[i] is the ?decompressed_size of stream i where has_limit[i]; caps[i] its dst_cap.  The destination is poisoned,
+    and what lies between a stream's room and the next stream's is asserted to be poison still."""
     import numpy as np
     import torch
 
@@ -452,6 +453,9 @@ def gpu_inflate_batch(ctx, streams, caps, has_limit, limits, crc_op):
     batch.inflate_batch(ctx, src, dst, batch.to_device(descs, dev), d_res, n, max(caps), crc_op)
     res = batch.results_from_device(d_res)
     out = dst.cpu().numpy()
+    for i in range(n):  # [dst_off + cap, next dst_off): nothing is written behind a stream's room, whatever its status
+        behind = out[int(dst_off[i]) + caps[i]:int(dst_off[i]) + slots[i]]
+        assert (behind == 0xA5).all(), ("stream %d of %d wrote behind its dst_cap of %d" % (i, n, caps[i]), int((behind != 0xA5).sum()))
     return [(int(res["status"][i]), out[int(dst_off[i]):int(dst_off[i]) + int(res["out_len"][i])].tobytes(),
              int(res["checksum"][i])) for i in range(n)]
 

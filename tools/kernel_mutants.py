@@ -25,6 +25,8 @@ the host models, in child processes: tests/test_host_sim.py::test_inflate_lane_m
 
 The mutants of the Adler-32 chunk chain (ADLER_MUTANTS, zipc_amd/csrc/adler_chain.h) are killed on the CPU only:
 tests/test_adler_chain_sim.py::test_adler_chain_mutants_are_killed.
+The mutants of inflate's room (ROOM_MUTANTS: where a stream's bytes may go) are killed on the CPU only, and are never built
+for the GPU: tests/test_inflate_room_rules.py::test_room_mutants_are_killed.
 The coder_choose mutants are killed on the CPU: tests/test_host_sim.py::test_coder_choose_mutants_are_killed.
 Each text must occur exactly once in its file, so a change of the kernels cannot quietly make a mutant a no-op.
 """
@@ -159,6 +161,36 @@ MANY_PLAN_MUTANTS = [
     ("slot_without_its_gap", "host_pipeline.h", "return (len + 255) / 256 * 256 + 256;", "return (len + 255) / 256 * 256;", "slots"),
     ("mid_off_runs_on", "host_pipeline.h", "uint64_t mo = 0;", "uint64_t mo = p.mid_arena;", "recode_mid_arena"),
     ("six_from_two_gib", "host_pipeline.h", "staged_bytes >= ((uint64_t)1 << 30)", "staged_bytes >= ((uint64_t)1 << 31)", "count_at_a_gib"),
+]
+# (name, file, text, replacement, killer): one-line mutants of inflate's ROOM -- where a stream's bytes may go and when it
+# is refused for want of room -- killed on the CPU only, by tests/test_inflate_room_rules.py::test_room_mutants_are_killed:
+# each is built into a host model of its own and run in a child process over the items of tests/inflate_room_cases.py.
+# killer: (the host model's mode, the item that must fail), or ("equivalent", why): no item may fail in any mode.
+# THESE MUTANTS WRITE OUT OF THEIR ROOM BY DESIGN (up to 15 bytes; the test's 64-byte guards hold that inside its own
+# buffer).  They are never built into a GPU library: they are in no list that --build or a GPU run reads, and must not be.
+# Each runs in the ONE mode its entry names: the two literal mutants leave out_pos one past cap_min, and the wide turn's
+# `cap_min - out_pos` would then wrap (its child would write all over its heap) -- "plain" decodes symbol by symbol.
+ROOM_MUTANTS = [
+    ("lane_copy_gate_without_its_8", "inflate_lane.h", "(uint64_t)pos + len + 8 <= hard_cap", "(uint64_t)pos + len <= hard_cap",
+     ("plain", "lane/L9_d8_g0/R=79/limit R, cap R")),
+    ("span_flush_quad_over_the_tail", "inflate_span.h", "if (i + 16u <= tile_len) {", "if (i < tile_len) {", ("span_a", "span/skewed_k5_d17/R=10220/no limit, cap R")),
+    ("lane_literal_at_cap_min", "inflate_lane.h", "\n      if (d.out_pos >= d.cap_min) { d.overflow(",
+     "\n      if (d.out_pos > d.cap_min) { d.overflow(", ("plain", "literal_last/n20000/R=19999/no limit, cap R")),
+    ("lane_fixed_literal_at_cap_min", "inflate_lane.h", "\n    if (d.out_pos >= d.cap_min) { d.overflow(",
+     "\n    if (d.out_pos > d.cap_min) { d.overflow(", ("plain", "literal_last/n1/R=0/no limit, cap R")),
+    ("lane_match_to_cap_min_refused", "inflate_lane.h",
+     "if ((uint64_t)d.out_pos + length > d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return SYM_STOP; }",
+     "if ((uint64_t)d.out_pos + length >= d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return SYM_STOP; }",
+     ("plain", "lane/L3_d1_g0/R=73/limit R, cap R")),
+    ("lane_stored_to_cap_min_refused", "inflate_lane.h",
+     "if ((uint64_t)d.out_pos + length > d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return true; }",
+     "if ((uint64_t)d.out_pos + length >= d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return true; }",
+     ("plain", "stored/len16_behind0/R=16/limit R, cap R")),
+    ("cap_min_from_hard_cap_alone", "inflate_lane.h", "d.cap_min = d.limit < d.hard_cap ? d.limit : d.hard_cap;", "d.cap_min = d.hard_cap;",
+     ("plain", "lane/L9_d8_g5/R=83/limit R, cap R+40")),
+    ("span_far_pass_ungated", "inflate_span.h", "if (out_pos + 32u <= hard_cap && wv::any(has_far != 0u)) {", "if (wv::any(has_far != 0u)) {",
+     ("equivalent", "the gate keeps 16-byte LOADS of far sources inside the room; the pass stores into the tile (LDS) only, and what it "
+                    "does not fetch the rounds behind it copy: the host model, whose guards are readable, gives the same bytes")),
 ]
 # what runs against each GPU mutant: the vectors under the default form, then under every override (one process each)
 TESTS = "tests/test_gpu_parity.py"
