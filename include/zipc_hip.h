@@ -487,6 +487,70 @@ int zipc_hip_zlib_decompress_packed_batch(zipc_hip_ctx *ctx, const void *d_src_a
                                           size_t n_streams, size_t max_out_len, size_t align,
                                           uint64_t *d_need /* may be NULL */);
 
+/* Deflate into ONE arena laid out on the device: the counterpart of the packed decode forms above, for a batch that is on
+ * the device and whose caller wants the compressed streams contiguous -- an archive's body, bytes for a wire, the input
+ * of another kernel -- without reading n results back, laying offsets out on the host and running n copies.  All pointers
+ * are DEVICE pointers.  Of a descriptor src_off, src_len and flags are read (flags as zipc_hip_deflate_batch, or for the
+ * zlib form zipc_hip_zlib_compress_batch, treats them); dst_off and dst_cap are not looked at.  The two arenas must not
+ * overlap.
+ * Staging: nobody knows a deflate output's size in advance, so every stream is deflated into a staging slot in the
+ * context's scratch -- zipc_hip_deflate_bound(src_len) bytes (the zlib form: zipc_hip_zlib_bound(src_len)), the slots on
+ * 16-byte boundaries in index order, their offsets from a scan on the device -- and copied from there.  That scratch is
+ * sized from n_streams and total_src_len alone: zipc_hip_deflate_packed_bound(n_streams, total_src_len, 16) bytes (the zlib
+ * form: the zlib helper's) beside deflate's own, and 88 bytes per stream of descriptors, results and plan.
+ * Declared sizes: zipc_hip_deflate_batch's device-side check of max_src_len and total_src_len applies, and the stage step
+ * makes it itself before any slot is used (the slots are sized from it): if a stream is longer than max_src_len or the
+ * sum of src_len exceeds total_src_len, EVERY result is ZIPC_HIP_ERR_INVALID_ARG with out_len 0 and dst_off 0, need is 0,
+ * nothing is staged and nothing is written to the destination.  A descriptor with src_len above ZIPC_HIP_MAX_STREAM_LEN
+ * counts in neither: it is ZIPC_HIP_ERR_INVALID_ARG in its own result only.
+ * The layout rule (csrc/deflate_packed.h; the packed decode forms' rule with "deflated OK" in the place of "sized OK"):
+ *   - a stream TAKES ROOM iff its deflate result is ZIPC_HIP_OK.  One that is not OK reports that status (with the
+ *     checksum zipc_hip_deflate_batch reports beside it), out_len 0 and dst_off 0, and takes no room.
+ *   - the streams that take room lie in index order: dst_off[i] = the sum over the roomed streams j < i of
+ *     align_up(out_len[j], align).  align: a power of two in 1..4096.  Every sum is 64-bit.  Padding is never written.
+ *   - a roomed stream FITS iff dst_off[i] + out_len[i] <= dst_arena_len.  One that does not reports
+ *     ZIPC_HIP_ERR_DST_TOO_SMALL with out_len 0 and the dst_off the rule gave it; none of its bytes is written.  Its
+ *     checksum is what zipc_hip_deflate_batch reports with that status: the CRC-32 of the source with
+ *     ZIPC_HIP_CRC_CRC32, else 0.
+ *   - d_need[0], if d_need is given, receives the end (dst_off + out_len) of the last roomed stream, whether it fit or
+ *     not, and 0 if no stream took room: the arena length with which every roomed stream fits.
+ * The suffix property: offsets never fall with the index and neither do the ends of the roomed streams, so the roomed
+ * streams that do not fit are exactly those from the first one that does not fit onwards.  A caller that came up short
+ * keeps every stream in front of that one and re-runs only the streams from it on, into an arena of need - its dst_off
+ * bytes (its dst_off is a multiple of align, so the second call's offsets continue the first's): a retry of the whole
+ * batch would cost a whole deflate, not a cheap sizing pass.
+ * The defining property: a roomed stream that fits gets the status, checksum, out_len and the bytes at dst_off that
+ * zipc_hip_deflate_batch (the zlib form: zipc_hip_zlib_compress_batch) gives for the same source, level and crc_op with
+ * dst_cap equal to the bound.  Nothing is written in front of d_dst_arena, at or behind dst_arena_len, or outside
+ * [dst_off, dst_off + out_len) of a stream that fits.
+ * The bound helpers (host arithmetic only) return an arena length with which every stream fits:
+ *     total_src_len + 6 * (total_src_len / 65534) + 14 * n_streams + (align - 1) * n_streams      (zlib: + 6 * n_streams)
+ * which follows from zipc_hip_deflate_bound(len) = len + 6 * (len / 65534 + 1) + 8: the floors of the streams sum to at
+ * most the floor of the total, and a stream's padding is below align.
+ * Launches: a stage step (one workgroup: the check, the slots, the descriptors deflate runs with), zipc_hip_deflate_batch's
+ * (zipc_hip_zlib_compress_batch's) own kernels over the slots, a layout step (one workgroup), a ragged device-to-device
+ * copy by one workgroup per 32 KiB segment that exists on a grid of staging bytes / 32768 + n_streams, and a close, a lane
+ * per stream.  The call is enqueued on the context's stream; it synchronises only where zipc_hip_deflate_batch does
+ * (growing the context's scratch, and the check of a context's first batch).
+ * A null ctx, d_descs or d_results, a null d_dst_arena with dst_arena_len != 0, n_streams above 0x7FFFFFFF, a copy grid
+ * bound above 0x7FFFFFFF, an align that is no power of two in 1..4096, a level outside 0..3, a crc_op outside the enum or
+ * max_src_len above ZIPC_HIP_MAX_STREAM_LEN fails the call with ZIPC_HIP_ERR_INVALID_ARG.  n_streams == 0 is ZIPC_HIP_OK,
+ * enqueues nothing and does not write d_need. */
+size_t zipc_hip_deflate_packed_bound(size_t n_streams, size_t total_src_len, size_t align);
+size_t zipc_hip_zlib_compress_packed_bound(size_t n_streams, size_t total_src_len, size_t align);
+int zipc_hip_deflate_packed_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, size_t dst_arena_len,
+                                  const zipc_hip_stream_desc *d_descs, zipc_hip_packed_result *d_results,
+                                  size_t n_streams, size_t max_src_len, size_t total_src_len, int level, int crc_op,
+                                  size_t align, uint64_t *d_need /* may be NULL */);
+/* The same with every stream a WHOLE zlib stream in the arena (the container's open and close of
+ * zipc_hip_zlib_compress_batch around the slots, the context's Adler-32 flavour): out_len counts the six container
+ * bytes, checksum is the Adler-32, and a flag bit other than ZIPC_HIP_STREAM_HAS_LIMIT is ZIPC_HIP_ERR_INVALID_ARG in
+ * the stream's own result. */
+int zipc_hip_zlib_compress_packed_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, size_t dst_arena_len,
+                                        const zipc_hip_stream_desc *d_descs, zipc_hip_packed_result *d_results,
+                                        size_t n_streams, size_t max_src_len, size_t total_src_len, int level,
+                                        size_t align, uint64_t *d_need /* may be NULL */);
+
 /* Recode on the device: every stream of the source arena -- a raw deflate stream, a ZIP member's bytes -- is inflated
  * into its room in a MIDDLE arena, its CRC-32 taken there and compared where the descriptor expects one, and what it
  * inflated to is deflated at `level` into its destination slot: Zipc_deflate.inflate_and_crc_32, Crc_32.check and

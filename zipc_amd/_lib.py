@@ -123,6 +123,10 @@ SYMBOLS = [
     ("zipc_hip_zlib_size_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_inflate_packed_batch", C.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _SZ, C.c_int, _P]),
     ("zipc_hip_zlib_decompress_packed_batch", C.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _SZ, _P]),
+    ("zipc_hip_deflate_packed_bound", _SZ, [_SZ, _SZ, _SZ]),
+    ("zipc_hip_zlib_compress_packed_bound", _SZ, [_SZ, _SZ, _SZ]),
+    ("zipc_hip_deflate_packed_batch", C.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _SZ, C.c_int, C.c_int, _SZ, _P]),
+    ("zipc_hip_zlib_compress_packed_batch", C.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P]),
     ("zipc_hip_recode_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int]),
     ("zipc_hip_recode_many", C.c_int, [_P, _SZ, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("zipc_hip_checksum_device", C.c_int, [_P, _P, _SZ, C.c_int, C.c_int, _P]),

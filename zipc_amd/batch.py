@@ -204,6 +204,44 @@ def zlib_decompress_packed_batch(ctx: Context, src, dst, descs_dev, results_dev,
         ctx.synchronize()
 
 
+def deflate_packed_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, max_src_len: int, total_src_len: int,
+                         level: int, crc_op: int = CRC_NOP, align: int = 1, need_dev=None, dst_arena_len=None, sync: bool = True):
+    """zipc_hip_deflate_packed_batch: every stream of `src` is deflated at `level` into a staging slot of the context's
+    scratch, given room in `dst` by the layout rule of include/zipc_hip.h (in index order, lengths padded to `align`) and
+    copied there, in one call; results_dev: a uint8 cuda tensor of PACKED_RESULT_DTYPE records (status, checksum, out_len
+    and the dst_off the stream was given); need_dev: None, or a cuda tensor of 8 bytes that receives the arena length with
+    which every stream fits; dst_arena_len: the arena's length where it is not the whole of `dst`.  dst_off / dst_cap of
+    the descriptors are not looked at.  An arena of deflate_packed_bound(n_streams, total_src_len, align) always fits."""
+    if sync:
+        _sync_torch(src)
+    d, dlen, need = _packed_args(dst, dst_arena_len, need_dev)
+    st = lib().zipc_hip_deflate_packed_batch(ctx.handle, src.data_ptr(), d, dlen, descs_dev.data_ptr(), results_dev.data_ptr(),
+                                             n_streams, max_src_len, total_src_len, level, crc_op, align, need)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def zlib_compress_packed_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, max_src_len: int, total_src_len: int,
+                               level: int, align: int = 1, need_dev=None, dst_arena_len=None, sync: bool = True):
+    """zipc_hip_zlib_compress_packed_batch: the same with every stream a whole zlib stream in `dst` (the context's Adler-32
+    flavour): out_len counts the six container bytes, checksum is the Adler-32."""
+    if sync:
+        _sync_torch(src)
+    d, dlen, need = _packed_args(dst, dst_arena_len, need_dev)
+    st = lib().zipc_hip_zlib_compress_packed_batch(ctx.handle, src.data_ptr(), d, dlen, descs_dev.data_ptr(), results_dev.data_ptr(),
+                                                   n_streams, max_src_len, total_src_len, level, align, need)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def deflate_packed_bound(n_streams: int, total_src_len: int, align: int = 1, zlib: bool = False) -> int:
+    """zipc_hip_deflate_packed_bound / zipc_hip_zlib_compress_packed_bound: an arena length with which every stream fits"""
+    f = lib().zipc_hip_zlib_compress_packed_bound if zlib else lib().zipc_hip_deflate_packed_bound
+    return f(n_streams, total_src_len, align)
+
+
 def recode_results_from_device(t) -> np.ndarray:
     return t.cpu().numpy().view(RECODE_RESULT_DTYPE).copy()
 
@@ -365,6 +403,7 @@ __all__ = ["DESC_DTYPE", "RESULT_DTYPE", "RECODE_DESC_DTYPE", "RECODE_RESULT_DTY
            "results_from_device", "recode_results_from_device", "recode_batch",
            "inflate_batch", "deflate_batch", "inflate_size_batch", "zlib_size_batch", "inflate_size_blocks_batch", "zlib_size_blocks_batch", "zlib_decompress_batch", "zlib_compress_batch", "checksum_device", "reserve",
            "PACKED_RESULT_DTYPE", "inflate_packed_batch", "zlib_decompress_packed_batch", "packed_results_from_device",
+           "deflate_packed_batch", "zlib_compress_packed_batch", "deflate_packed_bound",
            "RANGE_DTYPE", "CHECKSUM_RESULT_DTYPE", "make_ranges", "checksum_results_from_device", "checksum_batch", "checksum_many",
            "deflate_bound", "zlib_bound",
            "uniform_layout", "compact_descs", "OK"]

@@ -13,6 +13,7 @@
 #include <new>
 #include <vector>
 #include "ctx.h"
+#include "deflate_packed.h"
 #include "deflate_scratch.h"
 #include "packed_layout.h"
 #include "recode_rules.h"
@@ -321,6 +322,8 @@ void zipc_hip_destroy(zipc_hip_ctx *ctx) {
   free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre);
   free_buf(ctx->recode_descs); free_buf(ctx->recode_res); free_buf(ctx->recode_verdicts);
   free_buf(ctx->packed_descs); free_buf(ctx->packed_res); free_buf(ctx->packed_verdicts);
+  free_buf(ctx->dpacked_staging); free_buf(ctx->dpacked_descs); free_buf(ctx->dpacked_res);
+  free_buf(ctx->dpacked_plan); free_buf(ctx->dpacked_verdicts);
   free_buf(ctx->io_mid); free_buf(ctx->io_rdesc); free_buf(ctx->io_rres);
   free_buf(ctx->stored_list);
   free_buf(ctx->chain_check_links);
@@ -803,6 +806,37 @@ int zipc_hip_zlib_compress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, voi
                               max_src_len, total_src_len, level, zlib_crc_op(ctx));
   if (st) return st;
   return launch_zlib_close(ctx, d_dst_arena, d_descs, d_results, n_streams, 1, level);
+}
+
+// ---- deflate into one arena laid out on the device (deflate_packed.h has the rules; deflate_packed.hip the four kernels and the sequence) --
+
+size_t zipc_hip_deflate_packed_bound(size_t n_streams, size_t total_src_len, size_t align) {
+  return (size_t)dpacked_arena_bound(n_streams, total_src_len, align, false);
+}
+size_t zipc_hip_zlib_compress_packed_bound(size_t n_streams, size_t total_src_len, size_t align) {
+  return (size_t)dpacked_arena_bound(n_streams, total_src_len, align, true);
+}
+
+int zipc_hip_deflate_packed_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, size_t dst_arena_len,
+                                  const zipc_hip_stream_desc *d_descs, zipc_hip_packed_result *d_results, size_t n_streams,
+                                  size_t max_src_len, size_t total_src_len, int level, int crc_op, size_t align, uint64_t *d_need) {
+  if (!ctx || !d_descs || !d_results) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (const uint32_t st = dpacked_call_status(d_dst_arena == nullptr, dst_arena_len, n_streams, max_src_len, total_src_len, level, crc_op, align, false))
+    return (int)st;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  return launch_deflate_packed(ctx, d_src_arena, d_dst_arena, dst_arena_len, d_descs, d_results, n_streams, max_src_len, total_src_len, level,
+                               crc_op, align, d_need, false);
+}
+
+int zipc_hip_zlib_compress_packed_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, size_t dst_arena_len,
+                                        const zipc_hip_stream_desc *d_descs, zipc_hip_packed_result *d_results, size_t n_streams,
+                                        size_t max_src_len, size_t total_src_len, int level, size_t align, uint64_t *d_need) {
+  if (!ctx || !d_descs || !d_results) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (const uint32_t st = dpacked_call_status(d_dst_arena == nullptr, dst_arena_len, n_streams, max_src_len, total_src_len, level, zlib_crc_op(ctx), align, true))
+    return (int)st;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  return launch_deflate_packed(ctx, d_src_arena, d_dst_arena, dst_arena_len, d_descs, d_results, n_streams, max_src_len, total_src_len, level,
+                               zlib_crc_op(ctx), align, d_need, true);
 }
 
 // zlib_decompress src/zipc_deflate.ml:720-740 (start = 0): the container's six bytes on the

@@ -59,6 +59,8 @@ struct zipc_hip_ctx {
   Buf zlib_descs, zlib_pre;                       // the zlib batch forms: the descriptors the codec runs with, the container checks' verdicts (zlib.hip)
   Buf recode_descs, recode_res, recode_verdicts;  // the recode forms: the descriptors inflate, then deflate run with, their results, what is known of a stream between the steps (recode.hip)
   Buf packed_descs, packed_res, packed_verdicts;  // the packed decode forms: the descriptors inflate runs with, the sizing pass's results and then inflate's, the layout's verdicts (packed.hip)
+  Buf dpacked_staging, dpacked_descs, dpacked_res;  // the packed encode forms: the staging arena of the slots, the descriptors deflate runs with, its results (deflate_packed.hip)
+  Buf dpacked_plan, dpacked_verdicts;             // ... the call-wide word, the stage's statuses and the segment bases; the layout's verdicts
   Buf io_mid, io_rdesc, io_rres;                  // ... of host streams: the middle arena of a sub-batch, the call's recode descriptors and results
   Buf pin_rres;                                   // ... the results as they come back (pinned)
   Buf chain_check_links;                          // lz_chain's run-time check: the links the exchange kernel made of a batch's first streams
@@ -169,6 +171,14 @@ int packed_reserve(zipc_hip_ctx *ctx, size_t n);
 int launch_inflate_packed(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, size_t dst_arena_len,
                           const zipc_hip_stream_desc *d_descs, zipc_hip_packed_result *d_results, size_t n, size_t max_out_len,
                           size_t align, int crc_op, uint64_t *d_need, bool zlib);
+// deflate_packed.hip: zipc_hip_deflate_packed_batch / zipc_hip_zlib_compress_packed_batch behind their argument checks (a
+// ZIPC_HIP_* status): stage -> (zlib: open ->) deflate (-> zlib close) -> layout -> copy -> close on ctx->stream; crc_op: the
+// caller's, or zlib_crc_op's.  dpacked_reserve: its scratch beside deflate's own for n streams of total_src_len bytes, for
+// a caller that wants it grown before anything is in flight
+int dpacked_reserve(zipc_hip_ctx *ctx, size_t n, size_t total_src_len, bool zlib);
+int launch_deflate_packed(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, size_t dst_arena_len,
+                          const zipc_hip_stream_desc *d_descs, zipc_hip_packed_result *d_results, size_t n, size_t max_src_len,
+                          size_t total_src_len, int level, int crc_op, size_t align, uint64_t *d_need, bool zlib);
 // zlib.hip: the checksum the zlib forms of this context ask the codec for, and the container's kernels around the codec's
 // (a ZIPC_HIP_* status each): open leaves the codec's descriptors in ctx->zlib_descs and the checks' verdicts in ctx->zlib_pre
 int zlib_crc_op(const zipc_hip_ctx *ctx);
