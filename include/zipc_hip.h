@@ -659,6 +659,19 @@ size_t zipc_hip_debug_chain_positions(size_t n_streams, size_t total_src_len);
 int zipc_hip_debug_chain_links(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
                                size_t n_streams, size_t max_src_len, size_t total_src_len, int which, void *d_links,
                                size_t links_cap, void *d_pos_base);
+/* Tests only: the same links as ANY of the four chain forms makes them, launched by the pipeline's own launch site.
+ * chain (csrc/forms.h ChainKernel): 0 ordered LDS exchange, a workgroup per stream; 1 the same by segments of a stream;
+ * 2 the kernel that orders equal hashes itself, a workgroup per stream; 3 the same by segments.  seg_positions, for the
+ * two forms by segments: 0 for the segment size a deflate call of this shape gets (whole streams where it gets no
+ * segments), else one of the sizes the launch rules can produce -- 32768, 65536 or 131072 for chain 3, 98304 << k for
+ * chain 1; anything else is ZIPC_HIP_ERR_INVALID_ARG.  The whole-stream forms ignore it.  chain 0 or 1 on a context whose
+ * probe failed reports ZIPC_HIP_ERR_HIP.  d_links, links_cap and d_pos_base as above, but every slot is filled with
+ * ZIPC_HIP_DEBUG_LINK_POISON before the kernels run: no link exceeds 32768, so a slot nobody wrote shows.
+ * tests/test_gpu_chain_links.py holds every link of every form to a serial insert_hash. */
+#define ZIPC_HIP_DEBUG_LINK_POISON 0xFFFFu
+int zipc_hip_debug_chain_links_form(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                    size_t n_streams, size_t max_src_len, size_t total_src_len, int chain,
+                                    size_t seg_positions, void *d_links, size_t links_cap, void *d_pos_base);
 
 /* Tests only: the match finder's tables of a batch of device-resident streams.  Runs deflate_offsets, lz_chain (the
  * kernel that orders equal hashes itself) and lz_match and nothing else, lz_match launched exactly as a deflate call of

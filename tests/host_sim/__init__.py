@@ -32,10 +32,6 @@ def _bind(L):
     L.sim_huff_lengths.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.sim_crc_advance.restype = C.c_uint32
     L.sim_crc_advance.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
-    L.sim_chain.restype = None
-    L.sim_chain.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]
-    L.sim_chain_serial.restype = None
-    L.sim_chain_serial.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p]
     tun = C.POINTER(C.c_longlong)
     L.sim_deflate_grouping.restype = None
     L.sim_deflate_grouping.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, tun, C.POINTER(C.c_uint64)]
@@ -44,6 +40,8 @@ def _bind(L):
     L.sim_deflate_forms.restype = None
     L.sim_deflate_forms.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, tun, C.c_int, C.c_uint64, C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint64)]
+    L.sim_chain_seg_known.restype = C.c_int
+    L.sim_chain_seg_known.argtypes = [C.c_int, C.c_uint64]
     L.sim_inflate_blocks_gate.restype = C.c_int
     L.sim_inflate_blocks_gate.argtypes = [C.c_uint64, C.c_uint64]
     L.sim_inflate_few_streams.restype = C.c_int
@@ -70,7 +68,24 @@ def _bind(L):
     L.sim_blocks_shares.argtypes = [u32p, u32p, C.c_uint64, u64p, u64p, u64p]
     L.sim_match_lane_position.restype = None
     L.sim_match_lane_position.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    return bind_match(bind_many(bind_adler(L)))
+    return bind_chain(bind_match(bind_many(bind_adler(L))))
+
+
+def bind_chain(L):
+    """sim_chain.cpp's entry points (a library of that file alone has no others: the mutants of tests/test_chain_rules.py)"""
+    L.sim_chain.restype = None
+    L.sim_chain.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]
+    L.sim_chain_segments.restype = None
+    L.sim_chain_segments.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.sim_chain_serial.restype = None
+    L.sim_chain_serial.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p]
+    L.sim_chain_ref_hash4.restype = C.c_uint32
+    L.sim_chain_ref_hash4.argtypes = [C.c_char_p]
+    L.sim_chain_reference.restype = None
+    L.sim_chain_reference.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p]
+    L.sim_chain_xchg_segments.restype = None
+    L.sim_chain_xchg_segments.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32]
+    return L
 
 
 def bind_match(L):
@@ -350,3 +365,31 @@ def match_parse_reads(L, length, level, best, first):
     read = np.zeros(max(length - 3, 0), np.uint8)
     L.sim_match_parse_reads(length, MATCH_LEVELS[level][2], best.ctypes.data, first.ctypes.data, read.ctypes.data)
     return read
+
+
+# ---- sim_chain.cpp: the serial reference of the hash-chain links, and the models of the four chain forms beside it
+LINK_POISON = 0xFFFF  # include/zipc_hip.h ZIPC_HIP_DEBUG_LINK_POISON: no link exceeds 32768
+
+
+def chain_links(L, data, model="reference", seg_positions=0, seed=1):
+    """a stream's links by `model` -- "reference" (sim_chain_reference), "serial" (sim_chain_serial), "peel" (the model of
+    lz_chain_kernel, by segments where seg_positions is not 0) or "xchg" (the exchange kernel's, the same) -- as a uint16
+    array with one slot per BYTE, filled with LINK_POISON first: the slots of the last three bytes, and all of a stream
+    shorter than 4, must still hold it"""
+    import numpy as np
+
+    links = np.full(len(data) + 8, LINK_POISON, np.uint16)
+    if model == "reference":
+        L.sim_chain_reference(data, len(data), links.ctypes.data)
+    elif model == "serial":
+        L.sim_chain_serial(data, len(data), links.ctypes.data)
+    elif model == "peel" and seg_positions:
+        L.sim_chain_segments(data, len(data), links.ctypes.data, seed, seg_positions)
+    elif model == "peel":
+        L.sim_chain(data, len(data), links.ctypes.data, seed, C.byref(C.c_int()))
+    elif model == "xchg":
+        L.sim_chain_xchg_segments(data, len(data), links.ctypes.data, seg_positions)
+    else:
+        raise ValueError(model)
+    assert (links[len(data):] == LINK_POISON).all()
+    return links[:len(data)]

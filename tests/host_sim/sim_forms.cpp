@@ -50,6 +50,8 @@ extern "C" void sim_deflate_forms(uint64_t n, uint64_t max_src_len, uint64_t tot
   memcpy(slice, q, sizeof q);
 }
 
+extern "C" int sim_chain_seg_known(int chain, uint64_t seg_positions) { return chain_seg_known(chain, seg_positions) ? 1 : 0; }
+
 extern "C" int sim_inflate_blocks_gate(uint64_t n_streams, uint64_t max_dst_cap) { return inflate_blocks_gate(n_streams, max_dst_cap) ? 1 : 0; }
 extern "C" int sim_inflate_few_streams(uint64_t n_streams) { return inflate_few_streams(n_streams) ? 1 : 0; }
 

@@ -277,6 +277,29 @@ def debug_chain_links(ctx: Context, src, descs_dev, n_streams: int, max_src_len:
     return links, base
 
 
+LINK_POISON = 0xFFFF  # include/zipc_hip.h ZIPC_HIP_DEBUG_LINK_POISON
+CHAIN_XCHG, CHAIN_XCHG_SEGMENTS, CHAIN_PEEL, CHAIN_PEEL_SEGMENTS = 0, 1, 2, 3  # csrc/forms.h ChainKernel
+
+
+def debug_chain_links_form(ctx: Context, src, descs_dev, n_streams: int, max_src_len: int, total_src_len: int, chain: int,
+                           seg_positions: int = 0):
+    """Tests only (include/zipc_hip.h zipc_hip_debug_chain_links_form): the hash-chain links of a device-resident batch as
+    the chain form `chain` makes them (CHAIN_*; seg_positions: 0 for the shape's own segment size, else the size of a form
+    by segments), launched by the pipeline's own launch site: (links, pos_base) as an int16 and an int64 cuda tensor; slots
+    nobody wrote hold LINK_POISON."""
+    import torch
+
+    _sync_torch(src)
+    cap = int(lib().zipc_hip_debug_chain_positions(n_streams, total_src_len))
+    links = torch.empty(cap, dtype=torch.int16, device=src.device)
+    base = torch.empty(n_streams, dtype=torch.int64, device=src.device)
+    torch.cuda.current_stream(src.device).synchronize()
+    ctx.check(lib().zipc_hip_debug_chain_links_form(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), n_streams, max_src_len,
+                                                    total_src_len, chain, seg_positions, links.data_ptr(), cap, base.data_ptr()))
+    ctx.synchronize()
+    return links, base
+
+
 MATCH_POISON = 0x5A5A5A5A  # include/zipc_hip.h ZIPC_HIP_DEBUG_MATCH_POISON
 
 

@@ -469,6 +469,21 @@ int zipc_hip_debug_chain_links(zipc_hip_ctx *ctx, const void *d_src_arena, const
   return ZIPC_HIP_OK;
 }
 
+int zipc_hip_debug_chain_links_form(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, size_t n_streams,
+                                    size_t max_src_len, size_t total_src_len, int chain, size_t seg_positions, void *d_links,
+                                    size_t links_cap, void *d_pos_base) {
+  if (!ctx || !d_descs || !d_links || chain < 0 || chain > 3 || n_streams == 0 || n_streams > 0x7FFFFFFFull || max_src_len > MAX_STREAM_LEN)
+    return ZIPC_HIP_ERR_INVALID_ARG;
+  const bool by_segments = chain == zd::CHAIN_XCHG_SEGMENTS || chain == zd::CHAIN_PEEL_SEGMENTS;
+  if (by_segments && seg_positions && !zd::chain_seg_known(chain, seg_positions)) return ZIPC_HIP_ERR_INVALID_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->ensure(ctx->deflate_scratch, deflate_scratch_bytes(n_streams, max_src_len, total_src_len, ZIPC_HIP_LEVEL_DEFAULT, zd::tuning())));
+  HIP_TRY(ctx, zd::debug_chain_links_form(ctx, (const uint8_t *)d_src_arena, (const StreamDesc *)d_descs, n_streams, max_src_len, total_src_len,
+                                          chain, by_segments ? seg_positions : 0, ZIPC_HIP_DEBUG_LINK_POISON, (uint16_t *)d_links, links_cap,
+                                          (uint64_t *)d_pos_base));
+  return ZIPC_HIP_OK;
+}
+
 int zipc_hip_debug_match_records(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, size_t n_streams,
                                  size_t max_src_len, size_t total_src_len, int level, int match_form, long tiles_per_group,
                                  void *d_match, void *d_snap, size_t records_cap, void *d_snap_used, void *d_pos_base) {

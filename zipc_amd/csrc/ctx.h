@@ -131,6 +131,11 @@ bool xchg_order_probe(zipc_hip_ctx *ctx);
 hipError_t debug_chain_links(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *d_descs, size_t n, size_t max_src_len,
                              size_t total_src_len, int which, uint16_t *d_links, size_t links_cap, uint64_t *d_pos_base);
 size_t debug_chain_positions(size_t n, size_t total_src_len);
+// deflate.hip (tests): the links any of the four chain forms (forms.h ChainKernel) makes of a batch, through the pipeline's
+// own launch_lz_chain, over links filled with `fill`; seg_positions: 0 for the shape's own, else one the forms can produce
+hipError_t debug_chain_links_form(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *d_descs, size_t n, size_t max_src_len,
+                                  size_t total_src_len, int chain, size_t seg_positions, uint16_t fill, uint16_t *d_links,
+                                  size_t links_cap, uint64_t *d_pos_base);
 // deflate.hip (tests): lz_match's tables of a batch after deflate_offsets, lz_chain_kernel and lz_match alone, the latter
 // launched as the pipeline launches it under that match_form and tiles_per_group
 hipError_t debug_match_records(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *d_descs, size_t n, size_t max_src_len,

@@ -2689,31 +2689,85 @@ __global__ __launch_bounds__(64) void deflate_stored_kernel(const uint8_t *__res
 }
 
 // ---------------------------------------------------------------------------------
-// Tests only (zipc_hip_debug_chain_links): the hash-chain links of a batch as ONE of the two kernels makes them -- by
-// ordered LDS exchange (which = 0) or by the kernel that orders equal hashes itself (1) -- copied out with the streams'
-// position bases, so that a test can require the two to be equal over whole batches (insert_hash, zd.ml:1150-1152: the
-// exchange kernel's order rests on a property of the hardware that only a probe vouches for).  The scratch is zeroed
-// first: what no kernel writes compares equal.
-hipError_t debug_chain_links(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *d_descs, size_t n, size_t max_src_len,
-                             size_t total_src_len, int which, uint16_t *d_links, size_t links_cap, uint64_t *d_pos_base) {
+// lz_chain over one slice of m streams: which of the four kernels, its grid and its segment size are the forms' (forms.h
+// deflate_forms / deflate_slice_forms).  The ONE launch site: the pipeline's (launch_deflate_group) and the tests' entries
+// below all come through here.
+static void launch_lz_chain(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *dd, const DeflateScratch &Q, size_t m,
+                            const DeflateForms &F, const DeflateSliceForms &L) {
+  (void)m;  // (the grid is the slice's: L.chain_grid)
+  switch (L.chain) {
+  case CHAIN_XCHG_SEGMENTS:
+    ZD_LAUNCH(ctx, "lz_chain", lz_chain_xchg_segments_kernel, dim3((unsigned)L.chain_grid), dim3(64 * XCHG_WAVES), 0, d_src, dd, Q,
+              (uint32_t)F.xsegs, (uint32_t)F.xseg);
+    break;
+  case CHAIN_XCHG:
+    ZD_LAUNCH(ctx, "lz_chain", lz_chain_xchg_kernel, dim3((unsigned)L.chain_grid), dim3(64 * XCHG_WAVES), 0, d_src, dd, Q);
+    break;
+  case CHAIN_PEEL_SEGMENTS:
+    ZD_LAUNCH(ctx, "lz_chain", lz_chain_segments_kernel, dim3((unsigned)L.chain_grid), dim3(CHAIN_THREADS), 0, d_src, dd,
+              Q, (uint32_t)F.csegs, (uint32_t)F.chain_seg);
+    break;
+  case CHAIN_PEEL:
+    ZD_LAUNCH(ctx, "lz_chain", lz_chain_kernel, dim3((unsigned)L.chain_grid), dim3(CHAIN_THREADS), 0, d_src, dd, Q);
+    break;
+  }
+}
+
+// Tests only (zipc_hip_debug_chain_links_form, zipc_hip_debug_chain_links): the hash-chain links of a batch as ONE of the four
+// chain forms makes them (chain: forms.h ChainKernel), launched through launch_lz_chain, copied out with the streams' position
+// bases -- so that a test can hold every link of every form to a serial insert_hash (zd.ml:1150-1152), and require the
+// exchange kernel and the ordering kernel to be equal over whole batches (the exchange kernel's order rests on a property of
+// the hardware that only a probe vouches for).  seg_positions: 0 for what deflate_forms gives a call of this shape with that
+// chain (a whole-stream form where it gives no segments), else the segment size of a form by segments -- one of those the
+// forms can produce, or hipErrorInvalidValue; the whole-stream forms ignore it.  One group, on ctx->cur.  The links are
+// filled with `fill` (16 bits) first: what no kernel writes still holds it.
+hipError_t debug_chain_links_form(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *d_descs, size_t n, size_t max_src_len,
+                                  size_t total_src_len, int chain, size_t seg_positions, uint16_t fill, uint16_t *d_links,
+                                  size_t links_cap, uint64_t *d_pos_base) {
   size_t per_group, group_total;
   deflate_grouping(n, max_src_len, total_src_len, tuning(), per_group, group_total);
   if (per_group != n) return hipErrorInvalidValue;  // one group (a batch of up to 8 GiB)
+  const bool xchg = chain == CHAIN_XCHG || chain == CHAIN_XCHG_SEGMENTS, by_segments = chain == CHAIN_XCHG_SEGMENTS || chain == CHAIN_PEEL_SEGMENTS;
+  if (xchg && !ctx->xchg_ordered) return hipErrorNotSupported;
+  DeflateForms F = deflate_forms(n, max_src_len, total_src_len, LEVEL_DEFAULT, tuning(), xchg, 1);
+  DeflateSliceForms L = deflate_slice_forms(F, n);
+  if (by_segments && seg_positions) {
+    if (!chain_seg_known(chain, seg_positions)) return hipErrorInvalidValue;  // (the kernels' segments start on sweep and turn boundaries)
+    if (chain == CHAIN_XCHG_SEGMENTS) {
+      F.xseg = seg_positions;
+      F.xsegs = max_src_len ? (max_src_len + F.xseg - 1) / F.xseg : 1;
+      L.chain_grid = n * F.xsegs;
+    } else {
+      F.chain_seg = seg_positions;
+      F.csegs = max_src_len ? (max_src_len + F.chain_seg - 1) / F.chain_seg : 1;
+      L.chain_grid = n * F.csegs;
+    }
+    L.chain = (ChainKernel)chain;
+  } else if (by_segments) {  // the shape's own segment size; whole streams where the forms give this shape no segments
+    const size_t segs = xchg ? (F.xseg ? F.xsegs : 1) : F.csegs;
+    L.chain = segs > 1 ? (ChainKernel)chain : xchg ? CHAIN_XCHG : CHAIN_PEEL;
+    L.chain_grid = segs > 1 ? n * segs : n;
+  } else {
+    L.chain = (ChainKernel)chain;
+    L.chain_grid = n;
+  }
+  if (L.chain_grid == 0 || L.chain_grid > GRID_MAX) return hipErrorInvalidValue;
   DeflateScratch S = carve(ctx->deflate_scratch.p, n, total_src_len, LEVEL_DEFAULT);
   if (S.cap_positions > links_cap) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(S.prev, 0, S.cap_positions * 2, ctx->cur);
+  hipError_t e = hipMemsetD16Async((hipDeviceptr_t)S.prev, (unsigned short)fill, S.cap_positions, ctx->cur);
   if (e != hipSuccess) return e;
   ZD_LAUNCH(ctx, "deflate_offsets", deflate_offsets_kernel, dim3(1), dim3(1024), 0, d_descs, (uint32_t)n, S, (uint64_t)max_src_len);
-  if (which == 0) {
-    if (!ctx->xchg_ordered) return hipErrorNotSupported;
-    ZD_LAUNCH(ctx, "lz_chain", lz_chain_xchg_kernel, dim3((unsigned)n), dim3(64 * XCHG_WAVES), 0, d_src, d_descs, S);
-  } else {
-    ZD_LAUNCH(ctx, "lz_chain", lz_chain_kernel, dim3((unsigned)n), dim3(CHAIN_THREADS), 0, d_src, d_descs, S);
-  }
+  launch_lz_chain(ctx, d_src, d_descs, S, n, F, L);
   e = hipMemcpyAsync(d_links, S.prev, S.cap_positions * 2, hipMemcpyDeviceToDevice, ctx->cur);
   if (e == hipSuccess && d_pos_base) e = hipMemcpyAsync(d_pos_base, S.pos_base, n * 8, hipMemcpyDeviceToDevice, ctx->cur);
   if (e == hipSuccess) e = hipGetLastError();
   return e;
+}
+// (zipc_hip_debug_chain_links: which = 0 the exchange kernel, 1 the ordering kernel, whole streams, over zeroed links)
+hipError_t debug_chain_links(zipc_hip_ctx *ctx, const uint8_t *d_src, const StreamDesc *d_descs, size_t n, size_t max_src_len,
+                             size_t total_src_len, int which, uint16_t *d_links, size_t links_cap, uint64_t *d_pos_base) {
+  return debug_chain_links_form(ctx, d_src, d_descs, n, max_src_len, total_src_len, which == 0 ? CHAIN_XCHG : CHAIN_PEEL, 0, 0, d_links,
+                                links_cap, d_pos_base);
 }
 size_t debug_chain_positions(size_t n, size_t total_src_len) {
   uint64_t P, Bk;
@@ -2762,8 +2816,11 @@ hipError_t debug_match_records(zipc_hip_ctx *ctx, const uint8_t *d_src, const St
   if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)S.snap, (int)MATCH_DEBUG_POISON, S.cap_positions, ctx->cur);
   if (e != hipSuccess) return e;
   ZD_LAUNCH(ctx, "deflate_offsets", deflate_offsets_kernel, dim3(1), dim3(1024), 0, d_descs, (uint32_t)n, S, (uint64_t)max_src_len);
-  ZD_LAUNCH(ctx, "lz_chain", lz_chain_kernel, dim3((unsigned)n), dim3(CHAIN_THREADS), 0, d_src, d_descs, S);
-  launch_lz_match(ctx, d_src, d_descs, S, n, F, deflate_slice_forms(F, n), t.match_form);
+  const DeflateSliceForms L = deflate_slice_forms(F, n);
+  DeflateSliceForms Lc = L;  // (the links by the ordering kernel over whole streams, whatever the shape)
+  Lc.chain = CHAIN_PEEL; Lc.chain_grid = n;
+  launch_lz_chain(ctx, d_src, d_descs, S, n, F, Lc);
+  launch_lz_match(ctx, d_src, d_descs, S, n, F, L, t.match_form);
   e = hipMemcpyAsync(d_match, S.match, S.cap_positions * 4, hipMemcpyDeviceToDevice, ctx->cur);
   if (e == hipSuccess) e = hipMemcpyAsync(d_snap, S.snap, S.cap_positions * 4, hipMemcpyDeviceToDevice, ctx->cur);
   if (e == hipSuccess) e = hipMemcpyAsync(d_snap_used, S.snap_used, n * 4, hipMemcpyDeviceToDevice, ctx->cur);
@@ -2879,22 +2936,7 @@ static hipError_t launch_deflate_group(zipc_hip_ctx *ctx, const uint8_t *d_src, 
     DeflateScratch Q = S;
     Q.pos_base += lo; Q.blk_base += lo; Q.n_blocks += lo; Q.snap_used += lo;
     const StreamDesc *dd = d_descs + lo;
-    switch (L.chain) {
-    case CHAIN_XCHG_SEGMENTS:
-      ZD_LAUNCH(ctx, "lz_chain", lz_chain_xchg_segments_kernel, dim3((unsigned)L.chain_grid), dim3(64 * XCHG_WAVES), 0, d_src, dd, Q,
-                (uint32_t)F.xsegs, (uint32_t)F.xseg);
-      break;
-    case CHAIN_XCHG:
-      ZD_LAUNCH(ctx, "lz_chain", lz_chain_xchg_kernel, dim3((unsigned)L.chain_grid), dim3(64 * XCHG_WAVES), 0, d_src, dd, Q);
-      break;
-    case CHAIN_PEEL_SEGMENTS:
-      ZD_LAUNCH(ctx, "lz_chain", lz_chain_segments_kernel, dim3((unsigned)L.chain_grid), dim3(CHAIN_THREADS), 0, d_src, dd,
-                Q, (uint32_t)F.csegs, (uint32_t)F.chain_seg);
-      break;
-    case CHAIN_PEEL:
-      ZD_LAUNCH(ctx, "lz_chain", lz_chain_kernel, dim3((unsigned)L.chain_grid), dim3(CHAIN_THREADS), 0, d_src, dd, Q);
-      break;
-    }
+    launch_lz_chain(ctx, d_src, dd, Q, m, F, L);
     if (lo == 0 && check_k) {
       const hipError_t ce = chain_check_enqueue(ctx, d_src, dd, Q, check_k < m ? check_k : m, max_src_len, ctx->chain_check_host);
       if (ce != hipSuccess) slice_err = ce;

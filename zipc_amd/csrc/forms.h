@@ -121,6 +121,16 @@ enum ChainKernel : int {
   CHAIN_PEEL_SEGMENTS = 3,  // lz_chain_segments_kernel: a workgroup per chain_seg positions of a stream
 };
 
+// the segment sizes deflate_forms below can give a chain form by segments: chain_seg 32, 64 or 128 Ki, xseg 96 Ki << k
+// (zipc_hip_debug_chain_links_form launches a form by segments with no other size)
+inline bool chain_seg_known(int chain, size_t seg_positions) {
+  if (chain == CHAIN_PEEL_SEGMENTS) return seg_positions == CHAIN_SEG_MIN || seg_positions == 2 * CHAIN_SEG_MIN || seg_positions == CHAIN_SEG_MAX;
+  if (chain != CHAIN_XCHG_SEGMENTS) return false;
+  for (uint64_t x = (uint64_t)96 << 10; x <= MAX_STREAM_LEN; x *= 2)
+    if (x == seg_positions) return true;
+  return false;
+}
+
 struct DeflateForms {
   size_t n, max_src_len;
   bool grid_too_large;      // lz_match's grid does not fit: the call fails (hipErrorInvalidValue)
