@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "deflate_pipeline.h"
+#include "parse_tile.h"
 #include "tuning.h"
 
 namespace zd {
@@ -924,8 +925,11 @@ static __device__ unsigned long long zd_parse_counts[8];
 // next tile's).  br: the match the step ends with (0: the position is a literal), lits: the literals in front of it
 // (0 for a literal position), adv: the step's advance, literals + match length (1 for a literal position, 0 for a lane behind the
 // stream's end).  valid_m: the lanes whose position lies in the stream, as a mask.
+// SNAP = false, M = uint32_t: a stream without second answers (S.snap_used) -- one word a position, no best of K/4 to fetch.
+// INTERIOR: a tile of parse_tile_interior (parse_tile.h) -- every lane is in the stream and has a table entry.
+template <bool SNAP = true, bool INTERIOR = false, typename M = uint64_t>
 __device__ __forceinline__ void parse_tile_macro(int lane, uint32_t p, unsigned long long valid_m, bool has_match, uint32_t max_pos,
-                                               uint32_t len, uint64_t m_cur, uint64_t m_nxt,
+                                               uint32_t len, M m_cur, M m_nxt,
                                                const uint32_t *__restrict__ match, const uint32_t *__restrict__ snap, int good_match, uint32_t &br,
                                                uint32_t &adv, uint32_t &lits) {
   // The lanes whose lazy chain goes on are a LANE MASK (round 6).  Rounds 3-5 kept the flag as an integer in a vector
@@ -942,17 +946,21 @@ __device__ __forceinline__ void parse_tile_macro(int lane, uint32_t p, unsigned 
   //    "old" operand the compiler copies the register every turn).
   auto ballot = [](bool b) { return (unsigned long long)__builtin_amdgcn_ballot_w64(b); };
   auto mine = [](unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); };
-  const unsigned long long ok_m = has_match ? valid_m & ballot(p <= max_pos) : 0ull;
-  uint32_t pend = mine(ok_m) ? (uint32_t)m_cur : 0u;
-  unsigned long long chain_m = ok_m & ballot((pend & 0x1FF) != 0);
+  const unsigned long long ok_m = INTERIOR ? ~0ull : has_match ? valid_m & ballot(p <= max_pos) : 0ull;
+  uint32_t pend = INTERIOR ? (uint32_t)m_cur : mine(ok_m) ? (uint32_t)m_cur : 0u;
+  unsigned long long chain_m = INTERIOR ? ballot((pend & 0x1FF) != 0) : ok_m & ballot((pend & 0x1FF) != 0);
   uint32_t n_lits = 0;
   const uint32_t lenp = len - p;  // (lanes behind the end: never in chain_m)
-  const uint32_t cur_hi = (uint32_t)(m_cur >> 32), nxt_hi = (uint32_t)(m_nxt >> 32);
+  const uint32_t cur_hi = SNAP ? (uint32_t)((uint64_t)m_cur >> 32) : 0u, nxt_hi = SNAP ? (uint32_t)((uint64_t)m_nxt >> 32) : 0u;
   // one step of the lanes' lazy chains with the entry c of position j = p + ahead (zd.ml:1224-1240): which lanes take it
-  auto chain_step = [&](uint32_t c, uint32_t rem) {
+  // (room_implied: c is the table's entry of position j itself, and the match finder never lets a match pass the stream's end --
+  // its length is at most min(len - j, 258) = maxlen -- so "c is longer than pl" already says pl < maxlen: three vector
+  // instructions of a turn's twelve.  Taken in the interior form's turns; the edge form and the tail loop keep the test.)
+  auto chain_step = [&](uint32_t c, uint32_t rem, auto room_implied) {
     const uint32_t pl = pend & 0x1FF;
     const uint32_t maxlen = rem < (uint32_t)MAX_MATCH_LEN ? rem : (uint32_t)MAX_MATCH_LEN;
-    const unsigned long long take_m = chain_m & ballot(pl < maxlen) & ballot((c & 0x1FF) > pl);
+    const unsigned long long take_m = decltype(room_implied)::value ? chain_m & ballot((c & 0x1FF) > pl)
+                                                                    : chain_m & ballot(pl < maxlen) & ballot((c & 0x1FF) > pl);
     pend = mine(take_m) ? c : pend;
     unsigned long long carry_out;
     asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(n_lits), "=s"(carry_out) : "v"(n_lits), "s"(take_m));  // n_lits += take
@@ -977,27 +985,31 @@ __device__ __forceinline__ void parse_tile_macro(int lane, uint32_t p, unsigned 
     }
     uint32_t c = sh_cur;
     // best-of-K/4 only where a pending match is that long (and only where the stream has second answers at all: else hi = lo)
-    const unsigned long long want_hi = chain_m & ballot((pend & 0x1FF) >= (uint32_t)good_match);
-    if (want_hi) {
+    const unsigned long long want_hi = SNAP ? chain_m & ballot((pend & 0x1FF) >= (uint32_t)good_match) : 0ull;
+    if (SNAP && want_hi) {
       const uint32_t off = (uint32_t)lane + ahead;
       const uint32_t addr = (off & 63u) * 4u;
       const uint32_t a_hi = lane_value(addr, cur_hi), b_hi = lane_value(addr, nxt_hi);
       c = mine(want_hi) ? (off < 64u ? a_hi : b_hi) : c;
     }
-    chain_step(c, lenp - ahead);
+    chain_step(c, lenp - ahead, std::bool_constant<INTERIOR>{});
   }
   // a chain of 64 strictly growing matches and more: straight from the table
   // (kept out of the loop above: its load would make that loop wait for memory)
   while (chain_m) {
     const uint32_t j = p + ahead;
-    const uint64_t mj = mine(chain_m) && j <= max_pos ? match_pair(match, snap, j) : 0ull;
-    chain_step((pend & 0x1FF) >= (uint32_t)good_match ? (uint32_t)(mj >> 32) : (uint32_t)mj, lenp - ahead);
+    if (SNAP) {
+      const uint64_t mj = mine(chain_m) && j <= max_pos ? match_pair(match, snap, j) : 0ull;
+      chain_step((pend & 0x1FF) >= (uint32_t)good_match ? (uint32_t)(mj >> 32) : (uint32_t)mj, lenp - ahead, std::false_type{});
+    } else {
+      chain_step(mine(chain_m) && j <= max_pos ? match[j] : 0u, lenp - ahead, std::false_type{});
+    }
     ahead++;
   }
   br = pend;  // (0 where no match is pending: the lanes outside ok_m, and the positions without a match)
   lits = n_lits;
   const uint32_t step = n_lits + (pend & 0x1FF);
-  adv = mine(valid_m) ? (step ? step : 1u) : 0u;
+  adv = INTERIOR ? (step ? step : 1u) : mine(valid_m) ? (step ? step : 1u) : 0u;
 }
 
 // Streams parsed by several waves (lz_parse_spec_kernel / lz_parse_stitch_kernel / lz_parse_gather_kernel below):
@@ -1083,12 +1095,15 @@ __device__ __forceinline__ void lz_parse_wave(const uint8_t *__restrict__ src_ar
   // conditional load, and a select on the loaded value is an instruction it may place early)
   // (SNAP: the stream has positions whose best of the first K/4 is not their best of the first K -- S.snap_used -- and both
   // tables are read side by side, unconditionally like every load here; else one word a position is all there is)
-  auto load_match = [&](uint32_t tile) -> uint64_t {
+  using M = std::conditional_t<SNAP, uint64_t, uint32_t>;  // a position's answers: best of K | best of K/4 << 32, or the one word
+  auto load_match = [&](uint32_t tile) -> M {
     const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile);
     const uint32_t lo = (match + t)[lane];  // the tile's entries
-    if (!SNAP) return (uint64_t)lo | ((uint64_t)lo << 32);
-    const uint32_t second = (snap + t)[lane];
-    return (uint64_t)(lo & ~MATCH_SNAP) | ((uint64_t)((lo & MATCH_SNAP) ? second : lo) << 32);
+    if constexpr (!SNAP) return lo;
+    else {
+      const uint32_t second = (snap + t)[lane];
+      return (uint64_t)(lo & ~MATCH_SNAP) | ((uint64_t)((lo & MATCH_SNAP) ? second : lo) << 32);
+    }
   };
   // A lane's source byte travels as the 4-byte word it was loaded in and is extracted where it is used
   // (lit_byte) -- NOT loaded as a byte: a byte load is zero-extended by an instruction the compiler put at
@@ -1111,6 +1126,11 @@ __device__ __forceinline__ void lz_parse_wave(const uint8_t *__restrict__ src_ar
     const uint32_t v = lit_word(t, tcl);
     return load_u32_le((s + tcl) + v);
   };
+  // ... of a tile whose words all lie in the stream (tile + 67 <= len): the clamps are the identity
+  auto load_lit_inside = [&](uint32_t tile) -> uint32_t {
+    const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile);
+    return load_u32_le((s + t) + lane);
+  };
   auto lit_byte = [&](uint32_t raw, uint32_t tile) -> uint32_t {
     const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile);
     if (t + 67u <= len) return raw & 0xFFu;  // (wave-uniform)
@@ -1131,24 +1151,28 @@ __device__ __forceinline__ void lz_parse_wave(const uint8_t *__restrict__ src_ar
 #else
 #define ZD_PP(i) ((void)0)
 #endif
-  auto tile_step = [&](uint64_t &m_cur, uint64_t &m_nxt, uint64_t &m_nx2, uint64_t &m_nx3, uint32_t &lit_cur,
+  // Two forms, chosen per tile by parse_tile_interior (parse_tile.h; wave-uniform): the EDGE form is the general one; the
+  // INTERIOR form (in_form = std::true_type) is what is left of it where every lane lies in the stream, the look-ahead
+  // needs no clamp and no block can be cut -- all tiles of a stream but its last four and the nine in front of a cut.
+  auto tile_step = [&](auto in_form, M &m_cur, M &m_nxt, M &m_nx2, M &m_nx3, uint32_t &lit_cur,
                        uint32_t &lit_nxt, uint32_t &lit_nx2, uint32_t &lit_nx3) {
+    constexpr bool IN = decltype(in_form)::value;
 #ifdef ZD_PARSE_PHASES
     unsigned long long pp_t = __builtin_readcyclecounter();
     pp[0] += 1;
 #endif
     uint32_t Bn = B + PARSE_TILE;
     m_nx3 = load_match(Bn + 2u * PARSE_TILE);
-    lit_nx3 = load_lit(Bn + 2u * PARSE_TILE);
+    lit_nx3 = IN ? load_lit_inside(Bn + 2u * PARSE_TILE) : load_lit(Bn + 2u * PARSE_TILE);
 
     const uint32_t p = B + (uint32_t)lane;
     // (the lanes inside the stream as a mask, taken where the compare is: a ballot of a flag that comes from elsewhere goes
     // through a 0 / 1 in a vector register and a second compare)
-    const unsigned long long valid_m = __builtin_amdgcn_ballot_w64(p < len);
+    const unsigned long long valid_m = IN ? ~0ull : __builtin_amdgcn_ballot_w64(p < len);
     // macro step of every position of the tile (lz_macro_position, with the
     // following positions' matches taken from the neighbouring lanes)
     uint32_t br, adv, lits;
-    parse_tile_macro(lane, p, valid_m, has_match, max_pos, len, m_cur, m_nxt, match, snap, good_match, br, adv, lits);
+    parse_tile_macro<SNAP, IN, M>(lane, p, valid_m, has_match, max_pos, len, m_cur, m_nxt, match, snap, good_match, br, adv, lits);
     ZD_PP(1);
     const uint32_t cnt = lits + 1u;  // (of a visited lane: a literal position's one symbol, or the literals and the match)
     // J[k]: position reached after 2^k steps as a ds_bpermute address; a step that
@@ -1196,7 +1220,7 @@ __device__ __forceinline__ void lz_parse_wave(const uint8_t *__restrict__ src_ar
     // position its deferral literals -- the bytes of the next positions, taken
     // from their lanes -- then its match
     {
-      const uint32_t byte_cur = lit_byte(lit_cur, B), byte_nxt = lit_byte(lit_nxt, Bn);
+      const uint32_t byte_cur = IN ? lit_cur & 0xFFu : lit_byte(lit_cur, B), byte_nxt = IN ? lit_nxt & 0xFFu : lit_byte(lit_nxt, Bn);
       // (a ballot of a compound condition makes the compiler turn its mask into 0 / 1 in a vector register and compare that
       // again: two vector instructions; the compare's own ballot and a scalar `and` are one -- round 6, like the chains' masks)
       const unsigned long long lit_m = vis_m & __builtin_amdgcn_ballot_w64(lits != 0);  // (literals in front of a match)
@@ -1216,9 +1240,10 @@ __device__ __forceinline__ void lz_parse_wave(const uint8_t *__restrict__ src_ar
     // block cut: the first visited node that ends past blk_start + 65534
     // (a visited position is at or behind blk_start, so the test runs on 32-bit
     // distances from it; lanes that are not visited are masked out)
+    // (the interior form: no step of the tile reaches that far)
     const uint32_t rel = p - blk_start;
-    const unsigned long long cb = MODE == 0 ? vis_m & __builtin_amdgcn_ballot_w64(rel + adv > (uint32_t)MAX_BLOCK_SRC_LEN) : 0ull;
-    if (MODE == 0 && cb) {
+    const unsigned long long cb = MODE == 0 && !IN ? vis_m & __builtin_amdgcn_ballot_w64(rel + adv > (uint32_t)MAX_BLOCK_SRC_LEN) : 0ull;
+    if (MODE == 0 && !IN && cb) {
       const int c = __ffsll((long long)cb) - 1;
       uint32_t cutpos, symidx;
       if (br == 0) { cutpos = p; symidx = first; }
@@ -1253,7 +1278,7 @@ __device__ __forceinline__ void lz_parse_wave(const uint8_t *__restrict__ src_ar
     }
     ZD_PP(4);
   };
-  uint64_t ma = 0, mb = 0, mc = 0, md = 0;
+  M ma = 0, mb = 0, mc = 0, md = 0;
   uint32_t la = 0, lb = 0, lc = 0, ld = 0;
   if (len) {
     ma = load_match(B0);
@@ -1263,14 +1288,34 @@ __device__ __forceinline__ void lz_parse_wave(const uint8_t *__restrict__ src_ar
     mc = load_match(B0 + 2u * PARSE_TILE);
     lc = load_lit(B0 + 2u * PARSE_TILE);
   }
+  // The interior form is unrolled four times, the sets rotating by name.  The edge form -- a stream's last tiles, the tiles
+  // in front of a block cut, streams shorter than five tiles -- is ONE body that always takes the sets as (a, b, c, d) and
+  // moves them down afterwards, as the interior loop does where it is left in the middle of its rotation: a move waits for
+  // the loads just requested, which these few tiles can afford, and two forms four times each would double the loop's code.
+  const std::true_type interior_form;
+  const std::false_type edge_form;
+  // (parse_tile_interior as the one bound it is while the open block stays the same -- only the edge form cuts -- and with
+  // the wave's own limit folded in: a compare a tile)
+  uint32_t interior_end = 0;
+  auto interior = [&]() { return B < interior_end; };
   while (B < lim) {
-    tile_step(ma, mb, mc, md, la, lb, lc, ld);
-    if (B >= lim) break;
-    tile_step(mb, mc, md, ma, lb, lc, ld, la);
-    if (B >= lim) break;
-    tile_step(mc, md, ma, mb, lc, ld, la, lb);
-    if (B >= lim) break;
-    tile_step(md, ma, mb, mc, ld, la, lb, lc);
+    interior_end = parse_interior_end(len, blk_start, MODE == 0);
+    interior_end = interior_end < lim ? interior_end : lim;
+    if (interior()) {
+      for (;;) {
+        tile_step(interior_form, ma, mb, mc, md, la, lb, lc, ld);
+        if (!interior()) { ma = mb; mb = mc; mc = md; la = lb; lb = lc; lc = ld; break; }
+        tile_step(interior_form, mb, mc, md, ma, lb, lc, ld, la);
+        if (!interior()) { const M m0 = ma; ma = mc; mb = md; mc = m0; const uint32_t l0 = la; la = lc; lb = ld; lc = l0; break; }
+        tile_step(interior_form, mc, md, ma, mb, lc, ld, la, lb);
+        if (!interior()) { mc = mb; mb = ma; ma = md; lc = lb; lb = la; la = ld; break; }
+        tile_step(interior_form, md, ma, mb, mc, ld, la, lb, lc);
+        if (!interior()) break;
+      }
+    } else {
+      tile_step(edge_form, ma, mb, mc, md, la, lb, lc, ld);
+      ma = mb; mb = mc; mc = md; la = lb; lb = lc; lc = ld;
+    }
   }
 #ifdef ZD_PARSE_PHASES
   if (lane == 0) for (int i = 0; i < 5; i++) atomicAdd(&zd_parse_phases[i], pp[i]);
