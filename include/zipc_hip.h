@@ -690,6 +690,42 @@ int zipc_hip_debug_match_records(zipc_hip_ctx *ctx, const void *d_src_arena, con
                                  long tiles_per_group, void *d_match, void *d_snap, size_t records_cap, void *d_snap_used,
                                  void *d_pos_base);
 
+/* Tests only: zipc_hip_inflate_batch (no checksum) with the second half of the block path laid open.  Every stream that
+ * passes the length, capacity and 64x conditions of the block path is handed to it -- the cost rule that picks the k
+ * longest is the one thing bypassed; the call's gate (max_dst_cap) and ZIPC_HIP_INFLATE_BLOCKS hold as ever -- and the
+ * token run is launched by the pipeline's own launch site with
+ *   form   0: a wave per interval, the span decoder writing a match byte's source down as it is; 1: a wave per block, the span
+ *          decoder following sources as far as they are known (`follow`).  In BOTH forms the wide turn's store and wave_match
+ *          look the source's own word up, so a raw word is the byte's source or an earlier byte of the same chain of copies;
+ *          -1: whichever the call's own rule gives the stream;
+ *   hops0, hops1   the links a thread follows in the first / a later resolve round, 0: the tuning value; the number of
+ *          rounds follows from them as in the ordinary call.
+ * Anything else (form outside -1..1, hops outside 0..65536) is ZIPC_HIP_ERR_INVALID_ARG.
+ * d_tok_raw, d_tok_done: device arrays of as many 32-bit words as the destination arena has bytes.  The words of a
+ * stream that went into the token run lie at [dst_off, dst_off + out_len): tok[] copied once behind the token run (raw)
+ * and once behind the last resolve round (done) -- word i is the stream's output position byte i is a copy of, i
+ * itself for a literal.  No other word is touched.
+ * records: n_streams entries of HOST memory, one per stream.
+ * Behind the captures the call goes on as zipc_hip_inflate_batch does: gather, results, the one waves for every stream
+ * not done; status, length and bytes of every stream are the ordinary call's.
+ * tests/test_gpu_inflate_tokens.py holds every word to a serial decode. */
+#define ZIPC_HIP_DEBUG_TOKEN_ROUNDS 12
+typedef struct zipc_hip_debug_token_record {
+  uint32_t taken;        /* 1: the stream went into the token run (everything below is 0 otherwise) */
+  int32_t form;          /* the form it ran in: 0 or 1 */
+  uint32_t n_blocks;     /* blocks of its chain */
+  uint32_t n_intervals;  /* intervals of those blocks (form 0: waves of the token run) */
+  uint32_t token_bad;    /* waves that did not end as the dry run said */
+  uint32_t rounds;       /* resolve rounds launched */
+  uint32_t more[ZIPC_HIP_DEBUG_TOKEN_ROUNDS]; /* more[r], r < rounds: bytes round r left short of a literal */
+  uint32_t blocks_done;  /* 1: the block path's output stands; 0: left to the stream's one wave */
+  uint32_t reserved;
+} zipc_hip_debug_token_record;
+int zipc_hip_debug_inflate_tokens(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                  const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                                  size_t n_streams, size_t max_dst_cap, int form, int hops0, int hops1, void *d_tok_raw,
+                                  void *d_tok_done, zipc_hip_debug_token_record *records);
+
 /* grow the context scratch up front (keeps hipMalloc out of timed regions) */
 int zipc_hip_reserve(zipc_hip_ctx *ctx, size_t n_streams, size_t max_src_len,
                      size_t total_src_len);

@@ -16,6 +16,7 @@ INFLATE_RULE_CASES: name -> Case (the stream alone).  wrapped_cases(): name/wrap
 Limits are relative to what a case itself writes: a wrapper adds what comes before it.  CPU only; no GPU import.
 """
 import collections
+import functools
 import os
 import random
 import sys
@@ -63,6 +64,7 @@ FIXED_LL = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8
 FIXED_DL = [5] * 32
 
 
+@functools.lru_cache(maxsize=None)
 def len_sym(length):
     i = max(i for i, b in enumerate(LBASE) if b <= length)
     if i == 28 and length != 258:
@@ -70,6 +72,7 @@ def len_sym(length):
     return 257 + i, length - LBASE[i]
 
 
+@functools.lru_cache(maxsize=None)
 def dist_sym(dist):
     i = max(i for i, b in enumerate(DBASE) if b <= dist)
     return i, dist - DBASE[i]

@@ -30,6 +30,12 @@ def _bind(L):
                               C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
     L.sim_huff_lengths.restype = C.c_int
     L.sim_huff_lengths.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(L, "sim_inflate_token_words"):  # (a library of one file alone, as the mutants' tests build them, may lack it)
+        L.sim_inflate_token_words.restype = C.c_int
+        L.sim_inflate_token_words.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint32,
+                                              C.POINTER(C.c_uint64), C.c_void_p]
+        L.sim_inflate_token_tiles.restype = C.c_uint64
+        L.sim_inflate_token_tiles.argtypes = [C.c_void_p, C.c_uint64]
     L.sim_crc_advance.restype = C.c_uint32
     L.sim_crc_advance.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
     tun = C.POINTER(C.c_longlong)

@@ -7,6 +7,16 @@
 #include <string.h>
 #include <stdlib.h>
 #include <vector>
+// every tile the span decoder forms (inflate_span.h ZD_SPAN_TILE): the first bit of its first symbol, its first output
+// byte, its length -- lane 0's word, kept while sim_tiles_on (sim_inflate_token_tiles reads the last token run's)
+#include <stdint.h>
+#include <vector>
+static bool sim_tiles_on = false;
+static std::vector<uint64_t> sim_tiles;
+static inline void sim_tile(int lane, uint64_t bit, uint32_t pos, uint32_t len) {
+  if (sim_tiles_on && lane == 0) { sim_tiles.push_back(bit); sim_tiles.push_back(pos); sim_tiles.push_back(len); }
+}
+#define ZD_SPAN_TILE(bit, pos, len) sim_tile(lane, bit, pos, len)
 #include "../../zipc_amd/csrc/inflate_lane.h"
 #include "../../zipc_amd/csrc/inflate_span.h"
 #include "../../zipc_amd/csrc/inflate_find.h"
@@ -324,8 +334,10 @@ extern "C" int sim_inflate(const uint8_t *src, uint64_t src_len, uint8_t *dst, u
 // way wave_match does.  Then the copies are resolved -- in stream order a byte's source is final when its turn comes
 // -- and the result must be the stream's plain decode.  cut_every: spans are cut short like those of a wave that
 // leaves a block at a checkpoint (bits_cap), every so many bits.
-extern "C" int sim_inflate_token(const uint8_t *src, uint64_t src_len, uint8_t *dst, uint64_t dst_cap, int follow, int descending,
-                                 uint32_t cut_every, uint64_t *out_len) {
+// tok_out (sim_inflate_token_words): dst_cap words, tok[] as it stands BEFORE the resolve below -- what the kernel leaves to
+// inflate_resolve_kernel; null: nothing is handed back.
+static int token_model(const uint8_t *src, uint64_t src_len, uint8_t *dst, uint64_t dst_cap, int follow, int descending,
+                       uint32_t cut_every, uint64_t *out_len, uint32_t *tok_out) {
   static __attribute__((aligned(16))) uint8_t block[LDS_BYTES_PER_LANE];
   static uint16_t srcpos[SPAN_TILE];
   LaneLds L;
@@ -339,6 +351,8 @@ extern "C" int sim_inflate_token(const uint8_t *src, uint64_t src_len, uint8_t *
   lane_init(d, s);
   std::vector<uint32_t> tok(dst_cap + 1);
   for (uint64_t i = 0; i <= dst_cap; i++) tok[i] = (uint32_t)i;
+  sim_tiles.clear();
+  sim_tiles_on = tok_out != nullptr;
   auto token_match = [&](uint32_t pos, uint32_t dist, uint32_t len) {
     for (uint32_t i = 0; i < len; i++) tok[pos + i] = follow ? tok[pos - dist + (dist < len ? i % dist : i)] : pos - dist + i;
   };
@@ -392,6 +406,8 @@ extern "C" int sim_inflate_token(const uint8_t *src, uint64_t src_len, uint8_t *
     if (d.phase == PH_DONE) break;
     refill(d, L, src);
   }
+  sim_tiles_on = false;
+  if (tok_out && d.status == ST_OK) memcpy(tok_out, tok.data(), (size_t)d.out_pos * sizeof(uint32_t));
   if (d.status == ST_OK)
     for (uint32_t i = 0; i < d.out_pos; i++) {
       if (tok[i] > i) return -1;  // (a source lies before its copy)
@@ -399,6 +415,21 @@ extern "C" int sim_inflate_token(const uint8_t *src, uint64_t src_len, uint8_t *
     }
   *out_len = d.status == ST_OK ? d.out_pos : 0;
   return (int)d.status;
+}
+extern "C" int sim_inflate_token(const uint8_t *src, uint64_t src_len, uint8_t *dst, uint64_t dst_cap, int follow, int descending,
+                                 uint32_t cut_every, uint64_t *out_len) {
+  return token_model(src, src_len, dst, dst_cap, follow, descending, cut_every, out_len, nullptr);
+}
+// sim_inflate_token handing back tok[] as it stands before the model's own resolve (tests/test_token_rules.py holds every
+// word to a serial decode)
+extern "C" int sim_inflate_token_words(const uint8_t *src, uint64_t src_len, uint8_t *dst, uint64_t dst_cap, int follow, int descending,
+                                       uint32_t cut_every, uint64_t *out_len, uint32_t *tok) {
+  return token_model(src, src_len, dst, dst_cap, follow, descending, cut_every, out_len, tok);
+}
+// the tiles of the last sim_inflate_token_words run, three words each: first bit, first output byte, length -> how many there were
+extern "C" uint64_t sim_inflate_token_tiles(uint64_t *tiles, uint64_t cap) {
+  for (uint64_t i = 0; i < sim_tiles.size() && i < 3 * cap; i++) tiles[i] = sim_tiles[i];
+  return sim_tiles.size() / 3;
 }
 
 // CRC-32 combination rule used by the checksum kernels

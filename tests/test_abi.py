@@ -48,6 +48,21 @@ def test_abi_version_and_struct_layout():
     assert C.sizeof(_lib.StreamResult) == 16 == RESULT_DTYPE.itemsize
 
 
+def test_debug_inflate_tokens_is_exported_with_its_record():
+    """zipc_hip_debug_inflate_tokens (tests/test_gpu_inflate_tokens.py): the symbol, its 13 arguments, and the record's layout
+    as the header declares it (six words, ZIPC_HIP_DEBUG_TOKEN_ROUNDS counts, two words)"""
+    from zipc_amd import _lib
+    from zipc_amd.batch import TOKEN_RECORD_DTYPE
+
+    L = _lib.lib()
+    assert hasattr(L, "zipc_hip_debug_inflate_tokens")
+    assert [len(s[2]) for s in _lib.SYMBOLS if s[0] == "zipc_hip_debug_inflate_tokens"] == [13]
+    text = open(os.path.join(ROOT, "include", "zipc_hip.h")).read()
+    rounds = int(re.search(r"#define ZIPC_HIP_DEBUG_TOKEN_ROUNDS (\d+)", text).group(1))
+    assert TOKEN_RECORD_DTYPE["more"].shape == (rounds,) and TOKEN_RECORD_DTYPE.itemsize == 4 * (8 + rounds)
+    assert TOKEN_RECORD_DTYPE.names == ("taken", "form", "n_blocks", "n_intervals", "token_bad", "rounds", "more", "blocks_done", "reserved")
+
+
 def test_error_strings_are_the_references():
     from zipc_amd import _lib
 

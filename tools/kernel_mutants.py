@@ -27,6 +27,8 @@ The mutants of the Adler-32 chunk chain (ADLER_MUTANTS, zipc_amd/csrc/adler_chai
 tests/test_adler_chain_sim.py::test_adler_chain_mutants_are_killed.
 The mutants of inflate's room (ROOM_MUTANTS: where a stream's bytes may go) are killed on the CPU only, and are never built
 for the GPU: tests/test_inflate_room_rules.py::test_room_mutants_are_killed.
+The mutants of the span decoder's token form (TOKEN_MUTANTS) are killed on the CPU only, and are never built for the GPU:
+tests/test_token_rules.py::test_token_mutants_are_killed.
 The coder_choose mutants are killed on the CPU: tests/test_host_sim.py::test_coder_choose_mutants_are_killed.
 Each text must occur exactly once in its file, so a change of the kernels cannot quietly make a mutant a no-op.
 """
@@ -192,6 +194,30 @@ ROOM_MUTANTS = [
      ("equivalent", "the gate keeps 16-byte LOADS of far sources inside the room; the pass stores into the tile (LDS) only, and what it "
                     "does not fetch the rounds behind it copy: the host model, whose guards are readable, gives the same bytes")),
 ]
+# (name, file, text, replacement, killer): one-line mutants of the TOKEN parts of the span decoder (inflate_span.h: what a byte of a
+# match is written down as a copy of), killed on the CPU only and never built for the GPU, in the manner of ROOM_MUTANTS: each is
+# built into a host model of its own and run in child processes by tests/test_token_rules.py::test_token_mutants_are_killed, which
+# holds every word of tok[] to tests/token_ref.py.  killer: the stream of tests/token_cases.py whose words it must break, or
+# ("equivalent", why): it must break none.  The test prints per mutant whether the BYTES alone would have caught it.
+TOKEN_MUTANTS = [
+    ("follow_from_off_by_one", "inflate_span.h", "const uint32_t from = dp + 32768u - dist;", "const uint32_t from = dp + 32767u - dist;",
+     "len_dist_grid"),
+    ("follow_in_tile_test_strict", "inflate_span.h", "if (sp >= 32768u && (mbits[(sp - 32768u) >> 5] >> (sp & 31u)) & 1u)",
+     "if (sp > 32768u && (mbits[(sp - 32768u) >> 5] >> (sp & 31u)) & 1u)",
+     ("equivalent", "(tile_edges has sources that begin at a tile's first byte) sp == 32768 is tile position 0: not following it inside the tile leaves the byte a copy of tile byte 0, a byte of "
+                    "the same chain one link further from the literal -- a longer way, never a wrong one")),
+    ("follow_sweep_test_strict", "inflate_span.h", "v[u] = sp >= 32768u ? out_pos", "v[u] = sp > 32768u ? out_pos",
+     ("equivalent", "sp == 32768 then reads tok[out_pos], the word of tile byte 0 itself: out_pos while nobody has written it, or what "
+                    "tile byte 0 is a copy of -- the same chain either way")),
+    ("follow_wrap_dropped", "inflate_span.h", "r = r + 1u == dist ? 0u : r + 1u;", "r = r + 1u;",
+     ("equivalent", "without the wrap byte i >= dist of an overlapping match is written down as a copy of byte i - dist of the match "
+                    "itself, which is src[i] to the letter: one link more per period, the same chain")),
+    ("plain_source_not_advanced", "inflate_span.h", "tok[at + i] = from + i;", "tok[at + i] = from;", "len_dist_grid"),
+    ("follow_step_reads_the_neighbour", "inflate_span.h", "srcpos[b] = srcpos[sp - 32768u];", "srcpos[b] = srcpos[sp - 32767u];",
+     "len_dist_grid"),
+    ("follow_store_inverted", "inflate_span.h", "if (v[u] != out_pos + b) tok[out_pos + b] = v[u];",
+     "if (v[u] == out_pos + b) tok[out_pos + b] = v[u];", "len_dist_grid"),
+]
 # what runs against each GPU mutant: the vectors under the default form, then under every override (one process each)
 TESTS = "tests/test_gpu_parity.py"
 SELECT = "second_readings_vectors"
@@ -214,6 +240,14 @@ def mutated_tree(mutant, into):
     return csrc
 
 
+def makefile_units():
+    """the units zipc_amd/csrc/Makefile links into libzipc_hip.so (its SRCS line): the library does not load without one of them"""
+    m = re.search(r"^SRCS\s*:?=\s*(.+)$", open(os.path.join(CSRC, "Makefile")).read(), re.M)
+    units = [w[:-4] for w in m.group(1).split() if w.endswith(".hip")]
+    assert "inflate" in units and "deflate" in units, units
+    return units
+
+
 def build(mutant):
     """libzipc_hip.so with the mutated unit (deflate.hip, or inflate.hip for the inflate files) and the product's other
     objects -> its path"""
@@ -224,7 +258,7 @@ def build(mutant):
         csrc = mutated_tree(mutant, tmp)
         obj = os.path.join(tmp, unit + ".o")
         subprocess.run([HIPCC] + HIPFLAGS + ["-c", os.path.join(csrc, unit + ".hip"), "-o", obj], check=True)
-        others = [os.path.join(CSRC, "build", o + ".o") for o in ("api", "inflate", "checksum", "deflate") if o != unit]
+        others = [os.path.join(CSRC, "build", o + ".o") for o in makefile_units() if o != unit]
         os.makedirs(OUT, exist_ok=True)
         subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, obj] + others, check=True)
     return so

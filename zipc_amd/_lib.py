@@ -94,6 +94,7 @@ SYMBOLS = [
     ("zipc_hip_debug_chain_links_form", C.c_int, [_P, _P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P]),
     ("zipc_hip_debug_match_records", C.c_int,
      [_P, _P, _P, _SZ, _SZ, _SZ, C.c_int, C.c_int, C.c_long, _P, _P, _SZ, _P, _P]),
+    ("zipc_hip_debug_inflate_tokens", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ("zipc_hip_strerror", C.c_char_p, [C.c_int]),
     ("zipc_hip_set_profiling", C.c_int, [_P, C.c_int]),
     ("zipc_hip_set_adler_rfc1950", C.c_int, [_P, C.c_int]),

@@ -325,6 +325,29 @@ def debug_match_records(ctx: Context, src, descs_dev, n_streams: int, max_src_le
     return match, snap, used, base
 
 
+# zipc_hip_debug_token_record (include/zipc_hip.h)
+TOKEN_RECORD_DTYPE = np.dtype([("taken", "<u4"), ("form", "<i4"), ("n_blocks", "<u4"), ("n_intervals", "<u4"), ("token_bad", "<u4"),
+                               ("rounds", "<u4"), ("more", "<u4", (12,)), ("blocks_done", "<u4"), ("reserved", "<u4")])
+assert TOKEN_RECORD_DTYPE.itemsize == 80
+
+
+def debug_inflate_tokens(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, max_dst_cap: int, tok_raw, tok_done,
+                         form: int = -1, hops0: int = 0, hops1: int = 0) -> np.ndarray:
+    """Tests only (include/zipc_hip.h zipc_hip_debug_inflate_tokens): inflate_batch without a checksum, every stream that
+    fits the block path handed to it, the token run in `form` (0 by intervals, 1 following, -1 the call's own rule) and
+    the resolve rounds with hops0 / hops1 links (0: the tuning's).  tok_raw / tok_done: int32 cuda tensors of dst.numel()
+    words, written only at [dst_off, dst_off + out_len) of the streams that went into the token run: tok[] behind the
+    token run and behind the last resolve round.  Returns the records, one per stream (TOKEN_RECORD_DTYPE)."""
+    assert tok_raw.numel() >= dst.numel() and tok_done.numel() >= dst.numel() and tok_raw.element_size() == 4 and tok_done.element_size() == 4
+    _sync_torch(src)
+    rec = np.zeros(n_streams, dtype=TOKEN_RECORD_DTYPE)
+    ctx.check(lib().zipc_hip_debug_inflate_tokens(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(),
+                                                  n_streams, max_dst_cap, form, hops0, hops1, tok_raw.data_ptr(), tok_done.data_ptr(),
+                                                  rec.ctypes.data))
+    ctx.synchronize()
+    return rec
+
+
 def checksum_device(ctx: Context, buf, want_crc32=True, want_adler32=True):
     """(crc32, adler32) of a uint8 cuda tensor, computed on the device."""
     import torch

@@ -498,6 +498,19 @@ int zipc_hip_debug_match_records(zipc_hip_ctx *ctx, const void *d_src_arena, con
   return ZIPC_HIP_OK;
 }
 
+int zipc_hip_debug_inflate_tokens(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                  zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int form, int hops0, int hops1,
+                                  void *d_tok_raw, void *d_tok_done, zipc_hip_debug_token_record *records) {
+  if (!ctx || !d_descs || !d_results || !d_tok_raw || !d_tok_done || !records || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (form < -1 || form > 1 || hops0 < 0 || hops0 > 65536 || hops1 < 0 || hops1 > 65536) return ZIPC_HIP_ERR_INVALID_ARG;
+  memset(records, 0, n_streams * sizeof *records);
+  zd::BlocksDebug dbg;
+  dbg.form = form; dbg.hops0 = hops0; dbg.hops1 = hops1;
+  dbg.d_tok_raw = (uint32_t *)d_tok_raw; dbg.d_tok_done = (uint32_t *)d_tok_done;
+  dbg.records = records;
+  return launch_inflate(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, max_dst_cap, ZIPC_HIP_CRC_NOP, nullptr, true, &dbg);
+}
+
 int zipc_hip_reserve(zipc_hip_ctx *ctx, size_t n_streams, size_t max_src_len, size_t total_src_len) {
   if (!ctx) return ZIPC_HIP_ERR_INVALID_ARG;
   HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -147,10 +147,17 @@ hipError_t launch_deflate(zipc_hip_ctx *ctx, const uint8_t *d_src, uint8_t *d_ds
                           size_t max_src_len, size_t total_src_len, int level, int crc_op);
 // inflate.hip: zipc_hip_inflate_batch behind its argument checks (a ZIPC_HIP_* status).  h_descs: the caller's own host copy
 // of the descriptors, or null: the block path reads them back; first_of_call: zipc_hip_last_inflate_blocks counts from zero
-// (the many-stream host forms' sub-batches add up)
+// (the many-stream host forms' sub-batches add up).  dbg: zipc_hip_debug_inflate_tokens' wishes (tests), null for every other
+// caller: the token form (-1: blocks_follow's rule) and the hops of the first / a later resolve round (0: the tuning's), where
+// the tokens go, the records (host memory, one per stream, zeroed by the caller) -- and every stream that fits goes by blocks
+struct BlocksDebug {
+  int form, hops0, hops1;
+  uint32_t *d_tok_raw, *d_tok_done;
+  zipc_hip_debug_token_record *records;
+};
 int launch_inflate(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
                    zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op, const StreamDesc *h_descs,
-                   bool first_of_call);
+                   bool first_of_call, const BlocksDebug *dbg = nullptr);
 // inflate.hip: zipc_hip_inflate_size_batch behind its argument checks (a ZIPC_HIP_* status): inflate_size_kernel, a wave per
 // stream, one launch on ctx->cur
 int launch_inflate_size(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,

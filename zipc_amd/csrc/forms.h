@@ -295,19 +295,26 @@ inline bool inflate_blocks_gate(size_t n_streams, size_t max_dst_cap) {
          max_dst_cap >= (n_streams == 1 ? BLOCKS_MIN_SRC : BLOCKS_BATCH_MIN_DST);
 }
 
+// a stream the block path takes at all
+inline bool inflate_blocks_fits(const StreamDesc &sd) {
+  if (sd.src_len < BLOCKS_MIN_SRC || sd.src_len > BLOCKS_MAX_SRC || sd.dst_cap < 8 || sd.dst_cap > MAX_STREAM_LEN) return false;
+  // Runs (zeros, short periods: output beyond 64 x the input) are not for this path: a word of tok[] per byte of a
+  // run costs more than the run (16 MiB of zeros as zlib codes them, 4 blocks: token run 10-11 ms, the one wave
+  // 3.4-6.9), and where the reference's encoder has coded them with the fixed code, the explorers' walks never fall
+  // into step with a bit stream that has a period (64 MiB: the chain walks nearly every block itself, 65 ms).
+  return sd.dst_cap / 64 <= sd.src_len;
+}
+// every stream of a call that fits, in ascending order (zipc_hip_debug_inflate_tokens runs these: no cost rule)
+inline std::vector<uint32_t> inflate_blocks_fit(const StreamDesc *sds, size_t n_streams) {
+  std::vector<uint32_t> fit;
+  for (size_t i = 0; i < n_streams; i++)
+    if (inflate_blocks_fits(sds[i])) fit.push_back((uint32_t)i);
+  return fit;
+}
+
 // which of a call's streams go by blocks, in ascending order
 inline std::vector<uint32_t> inflate_blocks_pick(const StreamDesc *sds, size_t n_streams) {
-  std::vector<uint32_t> fit;  // the streams the block path takes at all
-  for (size_t i = 0; i < n_streams; i++) {
-    const StreamDesc &sd = sds[i];
-    if (sd.src_len < BLOCKS_MIN_SRC || sd.src_len > BLOCKS_MAX_SRC || sd.dst_cap < 8 || sd.dst_cap > MAX_STREAM_LEN) continue;
-    // Runs (zeros, short periods: output beyond 64 x the input) are not for this path: a word of tok[] per byte of a
-    // run costs more than the run (16 MiB of zeros as zlib codes them, 4 blocks: token run 10-11 ms, the one wave
-    // 3.4-6.9), and where the reference's encoder has coded them with the fixed code, the explorers' walks never fall
-    // into step with a bit stream that has a period (64 MiB: the chain walks nearly every block itself, 65 ms).
-    if (sd.dst_cap / 64 > sd.src_len) continue;
-    fit.push_back((uint32_t)i);
-  }
+  std::vector<uint32_t> fit = inflate_blocks_fit(sds, n_streams);
   // Which of them go by blocks: the one waves of a call run side by side, and a call of thousands of streams fills
   // the device with them -- its time is the longest stream's, about 15 ms per MiB of output -- while the block path
   // takes the streams' bytes one after the other, about 0.09 ms per MiB and 1 ms for a group's launches and

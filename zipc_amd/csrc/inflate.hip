@@ -2054,8 +2054,12 @@ struct BlocksRun {
 // that is not a chain of dynamic blocks behind its first block, anything the dry run or the chain did not like: the
 // one-wave kernel owns the reference's messages.  It SYNCHRONISES the context's stream.  ZIPC_HIP_INFLATE_BLOCKS=0
 // turns it off.
+static_assert(ZIPC_HIP_DEBUG_TOKEN_ROUNDS == RESOLVE_ROUNDS, "a debug record holds every round's count");
+// dbg (zipc_hip_debug_inflate_tokens; null: nothing changes): the token form and the hops in place of the tuning's, tok[]
+// of every stream of the token run copied out behind the token run and behind the last resolve round, a record per stream.
 static int inflate_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, uint8_t *dst, const StreamDesc *dd, StreamResult *d_results,
-                                const StreamDesc *sds, const uint32_t *streams, size_t nj, int crc_op, uint8_t *handled) {
+                                const StreamDesc *sds, const uint32_t *streams, size_t nj, int crc_op, uint8_t *handled,
+                                const BlocksDebug *dbg = nullptr) {
   const bool adler = crc_op == ZIPC_HIP_CRC_ADLER32 || crc_op == ZIPC_HIP_CRC_ADLER32_RFC1950;
   BlocksRun run(ctx, nj);
   if (!run.set_up(sds, streams)) return ZIPC_HIP_OK;
@@ -2063,7 +2067,7 @@ static int inflate_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, uint8_t *
   const int st = run.front(src, dst, dd, sds, f);
   if (st != ZIPC_HIP_OK || !f.through) return st;
   if (f.explored) HIP_TRY(ctx, run.read_counts());
-  const TokenPlan plan = blocks_token_plan(run.jobs, run.fc, f.alive, sds, tuning().inflate_follow);
+  const TokenPlan plan = blocks_token_plan(run.jobs, run.fc, f.alive, sds, dbg && dbg->form >= 0 ? dbg->form : tuning().inflate_follow);
   std::vector<uint32_t> alive = plan.taken, keep;
   if (alive.empty()) return ZIPC_HIP_OK;
   if (ctx->ensure(ctx->tok_scratch, plan.tok_bytes) != hipSuccess) { (void)hipGetLastError(); return ZIPC_HIP_OK; }  // (no room for a word per byte and the lists: the streams' one waves need none)
@@ -2075,15 +2079,35 @@ static int inflate_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, uint8_t *
   ZD_LAUNCH(ctx, "inflate_tok_init", inflate_tok_init_kernel, dim3(out_grid, na), dim3(256), 0, (const BlocksJob *)run.d_jobs);
   ZD_LAUNCH(ctx, "inflate_blocks_token", inflate_blocks_token_kernel, dim3(run.widest(alive, [](const BlocksJob &J, uint32_t) { return J.n; }), na),
             dim3(64), 0, src, dst, dd, (const BlocksJob *)run.d_jobs);
-  const int hops0 = tuning().resolve_hops0, hops1 = tuning().resolve_hops1;
+  // (dbg: a stream's tok[] to its words of the caller's array, at its destination's offset)
+  auto capture = [&](uint32_t *d_words) -> hipError_t {
+    for (uint32_t j : alive) {
+      const BlocksJob &J = run.jobs[j];
+      const hipError_t e = hipMemcpyAsync(d_words + sds[J.stream].dst_off, J.tok, (size_t)J.out_len * 4, hipMemcpyDeviceToDevice, ctx->stream);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  };
+  if (dbg) HIP_TRY(ctx, capture(dbg->d_tok_raw));
+  const int hops0 = dbg && dbg->hops0 ? dbg->hops0 : tuning().resolve_hops0, hops1 = dbg && dbg->hops1 ? dbg->hops1 : tuning().resolve_hops1;
   const int rounds = resolve_rounds(hops0, hops1);
   for (int r = 0; r < rounds; r++)
     ZD_LAUNCH(ctx, "inflate_resolve", inflate_resolve_kernel, dim3(resolve_grid(r, out_grid), na), dim3(256), 0, (const BlocksJob *)run.d_jobs, r, r == 0 ? hops0 : hops1);
+  if (dbg) HIP_TRY(ctx, capture(dbg->d_tok_done));
   ZD_LAUNCH(ctx, "inflate_gather", inflate_gather_kernel, dim3(out_grid, na), dim3(256), 0, dst, dd, (const BlocksJob *)run.d_jobs);
   HIP_TRY(ctx, run.read_counts());
   // (12 bytes of scratch per output byte: what a long stream took goes back -- a context lives as long as its thread,
   // and a 1 GiB member would pin 12 GiB per device; the stream is idle here, the gather has been waited for)
   if (ctx->tok_scratch.cap > BLOCKS_TOK_BUDGET) free_buf(ctx->tok_scratch);
+  if (dbg)
+    for (uint32_t j : alive) {
+      const FindCounts &c = run.fc[j];
+      zipc_hip_debug_token_record &R = dbg->records[run.jobs[j].stream];
+      R.taken = 1; R.form = run.jobs[j].follow; R.n_blocks = c.n_blocks; R.n_intervals = c.n_intervals;
+      R.token_bad = c.token_bad; R.rounds = (uint32_t)rounds;
+      for (int r = 0; r < rounds; r++) R.more[r] = c.more[r];
+      R.blocks_done = blocks_done(c, rounds) ? 1u : 0u;
+    }
   keep.clear();
   size_t n_chunks = 0;
   for (uint32_t j : alive) {
@@ -2132,16 +2156,16 @@ static int fetch_descs(zipc_hip_ctx *ctx, const zipc_hip_stream_desc *d_descs, s
 // which of a call's streams go by blocks, group by group; *n_handled: how many did (h_descs: fetch_descs)
 static int inflate_by_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
                              zipc_hip_stream_result *d_results, size_t n_streams, int crc_op, std::vector<StreamDesc> &sds,
-                             std::vector<uint8_t> &handled, size_t *n_handled, const StreamDesc *h_descs) {
+                             std::vector<uint8_t> &handled, size_t *n_handled, const StreamDesc *h_descs, const BlocksDebug *dbg = nullptr) {
   *n_handled = 0;
   handled.assign(n_streams, 0);
   if (!zd::tuning().inflate_blocks) return ZIPC_HIP_OK;
   if (const int st = fetch_descs(ctx, d_descs, n_streams, h_descs, sds)) return st;
-  const std::vector<uint32_t> picked = inflate_blocks_pick(sds.data(), n_streams);
+  const std::vector<uint32_t> picked = dbg ? inflate_blocks_fit(sds.data(), n_streams) : inflate_blocks_pick(sds.data(), n_streams);
   size_t begin = 0;
   for (size_t end : inflate_blocks_groups(sds.data(), picked)) {
     const int st = inflate_blocks_group(ctx, (const uint8_t *)d_src_arena, (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs,
-                                        (StreamResult *)d_results, sds.data(), picked.data() + begin, end - begin, crc_op, handled.data());
+                                        (StreamResult *)d_results, sds.data(), picked.data() + begin, end - begin, crc_op, handled.data(), dbg);
     if (st) return st;
     begin = end;
   }
@@ -2312,7 +2336,7 @@ int launch_inflate_size_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, const
 // zipc_hip_inflate_batch behind its argument checks (ctx.h)
 int launch_inflate(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
                    zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op, const StreamDesc *h_descs,
-                   bool first_of_call) {
+                   bool first_of_call, const BlocksDebug *dbg) {
   if (first_of_call) ctx->last_inflate_blocks = 0;  // (also for a call that never reaches the block path: "0 when the stream's one wave decoded it")
   if (n_streams == 0) return ZIPC_HIP_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2322,7 +2346,7 @@ int launch_inflate(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena
     std::vector<StreamDesc> sds;
     std::vector<uint8_t> handled;
     size_t n_handled = 0;
-    const int by = inflate_by_blocks(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, crc_op, sds, handled, &n_handled, h_descs);
+    const int by = inflate_by_blocks(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, crc_op, sds, handled, &n_handled, h_descs, dbg);
     if (by != ZIPC_HIP_OK) return by;
     if (n_handled == n_streams) {
       if (crc_op != ZIPC_HIP_CRC_CRC32) return ZIPC_HIP_OK;

@@ -487,6 +487,10 @@ ZD_WV void span_fill_by_wave(uint8_t *tile, const uint8_t *gbase, uint32_t dp, u
 #else
 #define ZD_SPAN_PH(i) do {} while (0)
 #endif
+// (tests/host_sim/sim_inflate.cpp defines it: where every tile starts -- bit of the stream, output position -- and its length)
+#ifndef ZD_SPAN_TILE
+#define ZD_SPAN_TILE(bit, pos, len) do {} while (0)
+#endif
 // MODE (inflate_lane.h IM_*): IM_DRY walks and checks the symbols and moves the position, touching neither `dst` nor a
 // tile (IM_SIZE: the same, at the stream's true output position, `dst` null); IM_TOKEN stores the literals and, for
 // every byte of a match, the output position it is a copy of in tok[]
@@ -723,6 +727,7 @@ ZD_WV int span_decode(InflateLane &d, const LaneLds &L, const uint8_t *src_strea
       break;
     }
     const uint32_t tile_len = wv::readlane(incl, n - 1u);
+    ZD_SPAN_TILE((uint64_t)in_word * 32u + tile_start_p, out_pos, tile_len);
     if (MODE == IM_DRY && ck != nullptr) {  // (the tile's start is where the tile before was checked to end, or the span's first bit)
       const uint64_t rel = (uint64_t)in_word * 32u + tile_start_p - ck->hdr_bit;
       if (ck->n < CK_MAX && rel >= (uint64_t)ck->last + CK_GAP_BITS && rel < 0xFFFFFFFFull) {
