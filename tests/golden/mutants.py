@@ -24,6 +24,8 @@ import types
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, os.path.dirname(HERE))
+from mutation import patched  # noqa: E402  (the exactly-once rule, tests/mutation.py)
 ORACLE_C = os.path.join(ROOT, "oracle", "zd_oracle.c")
 ORACLE_H = os.path.join(ROOT, "oracle", "zd_oracle.h")
 SECOND_READING = os.path.join(HERE, "zd_second_reading.py")
@@ -111,14 +113,6 @@ MUTANTS = [
             "            e.crc = adler_32_string_update(e.crc, e.src, 0, e.src_len)\n"),
            ("rand70k", "none")),
 ]
-
-
-def patched(text, old, new, where):
-    """`text` with `old` replaced by `new`; `old` must occur exactly once"""
-    n = text.count(old)
-    if n != 1:
-        raise AssertionError("%s: the mutant's text occurs %d times, not once: %r" % (where, n, old[:80]))
-    return text.replace(old, new)
 
 
 def build_oracle(m, out_dir, cc="gcc"):

@@ -1,7 +1,7 @@
 """Test-only host build of the lane-serial kernel code (see sim_*.cpp)."""
 import ctypes as C
 import os
-import subprocess
+import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libhost_sim.so")
@@ -16,8 +16,10 @@ def lib():
     deps += [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
     deps += [os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h")]
     if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-Wall",
-                               "-Wno-unknown-pragmas", "-I", HERE, "-o", LIB] + [os.path.join(HERE, s) for s in SRCS])
+        sys.path.insert(0, os.path.dirname(HERE))  # (tools/ import this package as tests.host_sim)
+        import mutation
+
+        mutation.gxx(LIB, [os.path.join(HERE, s) for s in SRCS], include=[HERE], extra=["-g", "-Wall", "-Wno-unknown-pragmas"])
     return _bind(C.CDLL(LIB))
 
 

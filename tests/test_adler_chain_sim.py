@@ -3,10 +3,8 @@ adler_runs_a / adler_replay, adler_rfc_finish) and the index grid of crc32_finis
 host model tests/host_sim/sim_adler.cpp and held against two references: the serial walk with adler_chunk_step (the
 reference's order) and checksum_cases.walk (zd.ml:175-198 restated over chunk sums in Python's integers); both against
 the oracle on bytes.  No GPU: the kernels are tests/test_gpu_checksum_chain.py's, on the same inputs."""
-import json
 import os
 import random
-import subprocess
 import sys
 import zlib
 
@@ -15,9 +13,11 @@ import pytest
 
 import checksum_cases as CC
 import host_sim
+import mutation
 import util
 
 N, P = CC.N, CC.P
+SIM_ADLER = os.path.join(host_sim.HERE, "sim_adler.cpp")
 
 
 @pytest.fixture(scope="module")
@@ -181,6 +181,44 @@ def test_rfc_finish_model_equals_zlib(sim):
 
 
 # ---- the mutation table ------------------------------------------------------------------------------------------------
+# (name, file, text, replacement, killer): one-line mutants of the Adler-32 chunk chain's arithmetic, killed on the CPU only --
+# each built into a host model of its own (tests/host_sim/sim_adler.cpp) and run in a child process by
+# test_adler_chain_mutants_are_killed below.  killer: the case of tests/checksum_cases.py
+# mutation_cases() whose result it must change, or ("equivalent", why): it must change none.
+# (The ambiguity bounds the other way -- `<=` for `<` -- only replay a chunk more: equivalent by construction, not listed.)
+ADLER_MUTANTS = [
+    ("amb_low_bound_less_1", "adler_chain.h", "return C < ADLER_BASE ||", "return C < ADLER_BASE - 1 ||",
+     ("equivalent", "|s2| <= 65520, so a chunk with C = 65520 never goes negative: the bound is one wider than it must be")),
+    ("amb_low_bound_less_2", "adler_chain.h", "return C < ADLER_BASE ||", "return C < ADLER_BASE - 2 ||", "low_bound_stays_negative_last"),
+    ("amb_mid_lower_bound_plus_1", "adler_chain.h", "(C > 0x80000000ull - ADLER_BASE &&", "(C > 0x80000000ull - ADLER_BASE + 1 &&",
+     "mid_lower_bound"),
+    ("amb_mid_upper_bound_less_1", "adler_chain.h", "C < 0x80000000ull + ADLER_BASE);", "C < 0x80000000ull + ADLER_BASE - 1);",
+     ("equivalent", "s2 >= -65520, so C = 2^31 + 65520 stays at or above 2^31: the bound is one wider than it must be")),
+    ("amb_mid_upper_bound_less_2", "adler_chain.h", "C < 0x80000000ull + ADLER_BASE);", "C < 0x80000000ull + ADLER_BASE - 2);",
+     "mid_upper_bound"),
+    ("a_term_without_225", "adler_chain.h", "hi_k ? ADLER_BASE - 225u : 0u", "hi_k ? 0u : 0u", "ff_chunks"),
+    ("hi_k_strict", "adler_chain.h", "return C >= 0x80000000ull;", "return C > 0x80000000ull;",
+     ("equivalent", "C = 2^31 is ambiguous: the chunk is replayed exactly, its a term is taken back out by the same function, "
+                    "and the branch of an ambiguous chunk is read by nobody (the next chunk takes exact_next or does not care)")),
+    ("zero_residue_negative", "adler_chain.h", "(rr == 0 ? 0 : (int32_t)rr - (int32_t)ADLER_BASE)", "((int32_t)rr - (int32_t)ADLER_BASE)",
+     "zero_behind_hi_then_mid"),
+    ("exact_at_ignored", "adler_chain.h", "k == st.exact_at ? st.exact_next : adler_signed_s2(rr, prev)", "adler_signed_s2(rr, prev)",
+     "adjacent_exact"),
+    ("prev_branch_no_walk_back", "adler_chain.h", "  while (run >= 0 && run_last_hi[run] == 0xFFFFFFFFu) run--;\n", "",
+     ("equivalent", "run (k - 1) / per holds chunk k - 1, so it is never empty: the walk back never takes a step")),
+    ("prev_branch_of_k", "adler_chain.h", "int64_t run = (int64_t)((k - 1) / per);", "int64_t run = (int64_t)(k / per);",
+     "opens_run_behind_hi"),
+    ("delta_not_carried", "adler_chain.h", "const uint32_t rr = addmod(res, st.delta);", "const uint32_t rr = addmod(res, 0u);",
+     "delta_carried"),
+    ("final_without_delta", "adler_chain.h", "(total_res + st.delta) % ADLER_BASE", "(total_res + 0u) % ADLER_BASE", "mid_upper_bound"),
+    ("final_ignores_exact_at", "adler_chain.h", "if (st.exact_at == n_chunks) final_s2", "if (false && st.exact_at == n_chunks) final_s2",
+     "low_bound_stays_negative_last"),
+    ("fallback_at_the_limit", "adler_chain.h", "n_amb > amb_cap || n_amb > replay_max", "n_amb > amb_cap || n_amb >= replay_max",
+     "replay_at_its_limit"),
+    ("per_rounded_down", "adler_chain.h", "(n_chunks + n_runs - 1) / n_runs : 1", "n_chunks / n_runs : 1", "ten_chunks_four_runs"),
+    ("rfc_chain_bytes_not_reduced", "adler_chain.h", "(nb[i] % ADLER_BASE) * c1", "nb[i] * c1",
+     ("equivalent", "a run's bytes stay below 2^37 for any length the launches take and c1 < 2^16: the 64-bit product cannot wrap")),
+]
 
 _MUTANT_CHILD = r"""
 import ctypes as C, json, os, random, sys
@@ -210,58 +248,51 @@ print(json.dumps(["random batch", out]), flush=True)
 
 
 def _run_child(so, first=()):
-    r = subprocess.run([sys.executable, "-c", _MUTANT_CHILD, so, os.path.dirname(util.HERE)] + list(first), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
-    rows = dict(json.loads(line) for line in r.stdout.decode().splitlines() if line.startswith("["))
-    return r.returncode, rows, r.stderr.decode()[-2000:]
+    rc, rows, err = mutation.run_child(_MUTANT_CHILD, so, mutation.ROOT, *first, timeout=300, every_line=True)
+    return rc, dict(rows), err
 
 
-def _build_model(csrc_dir, so):
-    """sim_adler.cpp alone against a copy of zipc_amd/csrc"""
-    src = open(os.path.join(host_sim.HERE, "sim_adler.cpp")).read()
-    inc = '#include "../../zipc_amd/csrc/adler_chain.h"'
-    assert src.count(inc) == 1
-    cpp = so[:-3] + ".cpp"
-    with open(cpp, "w") as f:
-        f.write(src.replace(inc, '#include "%s"' % os.path.join(csrc_dir, "adler_chain.h")))
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", so, cpp], check=True)
-    return so
+def _build_model(m, tmp_path):
+    """sim_adler.cpp alone against a copy of zipc_amd/csrc with the mutant `m` applied"""
+    from tools import kernel_mutants as KM
+
+    d = str(tmp_path / m[0])
+    return mutation.single_model(SIM_ADLER, "adler_chain.h", KM.mutated_tree(m, d), os.path.join(d, "mutant.so"))
+
+
+def judge(m, base, run):
+    """a mutant's child against the unmutated header's `base` -> (the cases it changed, is that as its entry says)"""
+    rc, got, _ = run
+    changed = [k for k in base if got.get(k) != base[k]]
+    return changed, mutation.verdict(m[4], [k for k in changed if k in got], crashed=rc != 0)  # (a case its child never reached kills nothing)
 
 
 def test_adler_chain_mutants_are_killed(sim, tmp_path, capsys):
-    """tools/kernel_mutants.py ADLER_MUTANTS: each one-line mutant of adler_chain.h built into a model of its own and run
+    """ADLER_MUTANTS: each one-line mutant of adler_chain.h built into a model of its own and run
     in a child process over checksum_cases.mutation_cases() (and a batch of random sequences).  A mutant must change the
     result of the case the table names (run first: rounding `per` down divides by zero in a later case, which ends that
     child, not this run); one listed as equivalent must change nothing at all.  The unmutated header gives
     the walk's value on every case, so a change is the mutant's."""
-    import concurrent.futures
-
     from tools import kernel_mutants as KM
 
     cases = CC.mutation_cases()
-    names = [m[0] for m in KM.ADLER_MUTANTS]
+    names = [m[0] for m in ADLER_MUTANTS]
     assert len(names) == len(set(names)) >= 14
-    assert all(isinstance(m[4], tuple) and m[4][0] == "equivalent" or m[4] in cases for m in KM.ADLER_MUTANTS)
+    assert all(isinstance(m[4], tuple) and m[4][0] == "equivalent" or m[4] in cases for m in ADLER_MUTANTS)
     # the unmutated header, built the same way, in a child as well
-    rc, base, err = _run_child(_build_model(KM.CSRC, str(tmp_path / "plain.so")))
+    rc, base, err = _run_child(mutation.single_model(SIM_ADLER, "adler_chain.h", KM.CSRC, str(tmp_path / "plain.so")))
     assert rc == 0, err
     for name, c in cases.items():
         want, cnt = CC.walk(c["sums"], c["length"])
         assert base[name][0] == want and cnt["low"] + cnt["mid"] >= 1, name
         assert base[name][1] == host_sim.ADLER_REPLAY, name
 
-    def build(m):
-        d = str(tmp_path / m[0])
-        return _build_model(KM.mutated_tree(m, d), os.path.join(d, "mutant.so"))
-
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
-        sos = list(ex.map(build, KM.ADLER_MUTANTS))
-        runs = list(ex.map(_run_child, sos, [[] if isinstance(m[4], tuple) else [m[4]] for m in KM.ADLER_MUTANTS]))
+    sos = mutation.build_all(lambda m: _build_model(m, tmp_path), ADLER_MUTANTS)
+    runs = mutation.build_all(lambda a: _run_child(*a), zip(sos, [[] if isinstance(m[4], tuple) else [m[4]] for m in ADLER_MUTANTS]))
     rows, bad = [], []
-    for m, (rc, got, err) in zip(KM.ADLER_MUTANTS, runs):
-        changed = [k for k in base if got.get(k) != base[k]]
-        equivalent = isinstance(m[4], tuple)
-        ok = (rc == 0 and not changed) if equivalent else (m[4] in got and got[m[4]] != base[m[4]])
-        rows.append((m[0], "equivalent" if equivalent else m[4], changed, rc))
+    for m, run in zip(ADLER_MUTANTS, runs):
+        changed, ok = judge(m, base, run)
+        rows.append((m[0], "equivalent" if isinstance(m[4], tuple) else m[4], changed, run[0]))
         if not ok:
             bad.append(m[0])
     with capsys.disabled():
@@ -271,10 +302,10 @@ def test_adler_chain_mutants_are_killed(sim, tmp_path, capsys):
             verdict = ("ok" if not changed else "CHANGED") if killer == "equivalent" else ("ok" if killer in changed else "MISSED")
             print("  %-30s %-34s %6d  %s%s" % (name, "%s %s" % (killer, verdict), len(changed), changed[0] if changed else "-",
                                                "" if rc == 0 else "  (the child then ended with %d)" % rc))
-        eq_names = [m[0] for m in KM.ADLER_MUTANTS if isinstance(m[4], tuple)]
+        eq_names = [m[0] for m in ADLER_MUTANTS if isinstance(m[4], tuple)]
         n_eq = len(eq_names)
         print("  %d of %d killed by their named case, %d equivalent, %d wrong" % (len(rows) - n_eq - len([b for b in bad if b not in eq_names]), len(rows) - n_eq, n_eq, len(bad)))
-        for m in KM.ADLER_MUTANTS:
+        for m in ADLER_MUTANTS:
             if isinstance(m[4], tuple):
                 print("  equivalent: %-30s %s" % (m[0], m[4][1]))
     assert bad == []

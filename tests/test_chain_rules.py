@@ -7,7 +7,6 @@ must change a link of a named case."""
 import concurrent.futures
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,8 +16,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import chain_cases as cc  # noqa: E402
 import host_sim  # noqa: E402
+import mutation  # noqa: E402
 
-WORKERS = min(16, os.cpu_count() or 1)
+WORKERS = mutation.workers()
 # (model, seg_positions) of every row of tests/test_gpu_chain_links.py
 FORMS = [("xchg", 0)] + [("xchg", s) for s in cc.XCHG_SEGS] + [("peel", 0)] + [("peel", s) for s in cc.PEEL_SEGS]
 
@@ -221,19 +221,16 @@ MUTANT_FORMS = {"reference": [("reference", 0)], "peel": [f for f in FORMS if f[
 def build_mutant(index, out_dir):
     name, _, old, new, _ = MUTANTS[index]
     src = open(os.path.join(HERE, "host_sim", "sim_chain.cpp")).read()
-    assert src.count(old) == 1, "%s: the line occurs %d times" % (name, src.count(old))
     path = os.path.join(out_dir, "m_%d" % index)
     with open(path + ".cpp", "w") as f:
-        f.write(src.replace(old, new))
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-I", os.path.join(HERE, "host_sim"), "-o", path + ".so",
-                           path + ".cpp"])
-    return host_sim.bind_chain(C.CDLL(path + ".so"))
+        f.write(mutation.patched(src, old, new, "sim_chain.cpp " + name))
+    so = mutation.gxx(path + ".so", [path + ".cpp"], include=[os.path.join(HERE, "host_sim")], extra=["-Wall"])
+    return host_sim.bind_chain(C.CDLL(so))
 
 
 def test_every_mutant_changes_a_link_of_a_named_case(refs, tmp_path, capsys):
     streams = list(unique_streams().values())
-    with concurrent.futures.ThreadPoolExecutor(max_workers=WORKERS) as ex:
-        libs = list(ex.map(lambda i: build_mutant(i, str(tmp_path)), range(len(MUTANTS))))
+    libs = mutation.build_all(lambda i: build_mutant(i, str(tmp_path)), range(len(MUTANTS)))
     rows, wrong = [], []
     for (name, what, _, _, why), ML in zip(MUTANTS, libs):
         changed, cases, first = 0, 0, None

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import checksum_batch_cases as BC
+import mutation
 import util  # noqa: F401  (sets sys.path through conftest)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -22,11 +23,11 @@ STATS = ("segs", "chunks", "segs_bound", "chunks_bound", "bad", "violations", "o
          "loaded", "worked")
 
 
-def _build(so, header=None):
-    cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so]
-    if header:
-        cmd.append('-DRANGES_HEADER="%s"' % header)
-    subprocess.run(cmd + [os.path.join(SIM_DIR, "sim_ranges.cpp")], check=True)
+SIM = os.path.join(SIM_DIR, "sim_ranges.cpp")
+FLAGS = dict(extra=["-Wall", "-Wno-unknown-pragmas"])
+
+
+def _bind(so):
     L = C.CDLL(so)
     L.sim_ranges_run.restype = C.c_uint64
     L.sim_ranges_run.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_int,
@@ -40,7 +41,7 @@ def _build(so, header=None):
 
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    return _build(str(tmp_path_factory.mktemp("ranges_sim") / "libranges_sim.so"))
+    return _bind(mutation.gxx(tmp_path_factory.mktemp("ranges_sim") / "libranges_sim.so", [SIM], **FLAGS))
 
 
 def run(L, arena, ranges, total, crc=True, adler=True, rfc=False):
@@ -165,18 +166,13 @@ def _observe(L):
 def test_mutants_of_the_header_are_killed(sim, tmp_path):
     """each one-line mutant of checksum_ranges.h, built into a model of its own, changes what the model says of at least
     one case (a result, a count, or an index that leaves its array: the model counts such an index, it never follows it)"""
-    src = open(HEADER).read()
     base = _observe(sim)
     assert all(dict(row[3])["violations"] == 0 for row in base)
     alive = []
     for k, (name, line, mutated) in enumerate(MUTANTS):
-        assert src.count(line) == 1, (name, "the line is not in the header, or not once")
-        hdr = str(tmp_path / ("mutant%d.h" % k))
-        with open(hdr, "w") as f:
-            f.write(src.replace(line, mutated).replace('#include "adler_chain.h"', '#include "%s"' % os.path.join(os.path.dirname(HEADER), "adler_chain.h"))
-                    .replace('#include "zd_common.h"', '#include "%s"' % os.path.join(os.path.dirname(HEADER), "zd_common.h")))
-        got = _observe(_build(str(tmp_path / ("libmutant%d.so" % k)), hdr))
-        if got == base:
+        so = mutation.header_model(SIM, "RANGES_HEADER", HEADER, line, mutated, str(tmp_path / ("mutant%d" % k) / "libmutant.so"),
+                                   rewrite_includes=("adler_chain.h", "zd_common.h"), **FLAGS)
+        if _observe(_bind(so)) == base:
             alive.append(name)
     assert alive == []
 
@@ -185,8 +181,8 @@ def test_audit_program_under_the_address_sanitizer(tmp_path):
     """the model as a stand-alone program with its own main, built with -fsanitize=address,undefined and run as a process:
     the cases' seams and two thousand random ragged batches; it aborts on any index that leaves its array"""
     exe = str(tmp_path / "ranges_audit")
-    subprocess.run(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=undefined", "-o", exe, os.path.join(SIM_DIR, "audit_main.cpp")], check=True)
+    mutation.gxx(exe, [os.path.join(SIM_DIR, "audit_main.cpp")], shared=False,
+                 extra=["-g", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     assert b"no index left its array" in r.stdout

@@ -7,12 +7,12 @@ header (and over the two functions of packed_layout.h it takes the layout rule f
 program under the address sanitizer (audit_main.cpp).  No GPU; the kernels are checked in tests/test_gpu_deflate_packed.py."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import mutation
 import util  # noqa: F401  (sets sys.path through conftest)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -37,11 +37,10 @@ POISON = 0xEE
 FLAVOURS = ((0, CRC_NOP, 0), (0, CRC_CRC32, 5), (1, CRC_ADLER32, 11))
 
 
-def _build(so, header=None):
-    cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-I", CSRC, "-o", so]
-    if header:
-        cmd.append('-DDPACKED_HEADER="%s"' % header)
-    subprocess.run(cmd + [SIM], check=True)
+FLAGS = dict(include=[CSRC], extra=["-Wall", "-Wno-unknown-pragmas"])
+
+
+def _bind(so):
     L = C.CDLL(so)
     u64, u32, p = C.c_uint64, C.c_uint32, C.c_void_p
     L.sim_dpacked_run.restype = u64
@@ -59,7 +58,7 @@ def _build(so, header=None):
 
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    return _build(str(tmp_path_factory.mktemp("deflate_packed_sim") / "libdeflate_packed_sim.so"))
+    return _bind(mutation.gxx(tmp_path_factory.mktemp("deflate_packed_sim") / "libdeflate_packed_sim.so", [SIM], **FLAGS))
 
 
 def bound(src_len, zlib):
@@ -385,16 +384,10 @@ def test_mutants_of_the_header_are_killed(sim, tmp_path):
     assert all(row[-1][0] == 0 and row[-1][1] == 0 and row[-1][2] == 0 for row in base)
     alive = []
     for k, (name, header, line, mutated) in enumerate(MUTANTS):
-        src = open(header).read()
-        assert src.count(line) == 1, (name, "the line is not in the header, or not once")
-        d = tmp_path / ("mutant%d" % k)
-        d.mkdir()
         # (the mutated header's quoted includes look beside it first: a mutated packed_layout.h lies there under its own name)
-        shutil.copy(HEADER, str(d / "deflate_packed.h"))
-        with open(str(d / os.path.basename(header)), "w") as f:
-            f.write(src.replace(line, mutated))
-        L = _build(str(d / "libmutant.so"), str(d / "deflate_packed.h"))
-        if _observe(L) == base:
+        so = mutation.header_model(SIM, "DPACKED_HEADER", header, line, mutated, str(tmp_path / ("mutant%d" % k) / "libmutant.so"),
+                                   top=HEADER, **FLAGS)
+        if _observe(_bind(so)) == base:
             alive.append(name)
     assert alive == []
 
@@ -404,8 +397,8 @@ def test_audit_program_under_the_address_sanitizer(tmp_path):
     the cases' seams and a few thousand random ragged batches; it aborts on any index that leaves its array, any byte
     written twice or outside a fitting stream, and any result or byte that differs from a serial restatement of the rule"""
     exe = str(tmp_path / "deflate_packed_audit")
-    subprocess.run(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=undefined", "-I", CSRC, "-o", exe, os.path.join(SIM_DIR, "audit_main.cpp")], check=True)
+    mutation.gxx(exe, [os.path.join(SIM_DIR, "audit_main.cpp")], shared=False, include=[CSRC],
+                 extra=["-g", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     assert b"no index left its array" in r.stdout

@@ -7,6 +7,7 @@ import random
 
 import pytest
 
+import mutation
 import util
 from host_sim import lib as sim_lib
 
@@ -438,28 +439,13 @@ def test_coder_choose_mutants_are_killed(oracle, tmp_path):
     """tools/kernel_mutants.py's mutants of coder_choose (the block chooser's two `<=` and Q3's 8 bits of padding, the
     host models' copy of wave_choose and deflate_scan_kernel's): each built into a host model of its own, each must
     change the bytes of an input that sits on its line (util.TIE_CASES).  The GPU copies: tools/kernel_mutants.py."""
-    import os
-    import shutil
-    import subprocess
-
-    from host_sim import HERE as SIM_DIR, SRCS, _bind
+    from host_sim import _bind
     from tools import kernel_mutants as KM
 
     ties = util.tie_cases()
     rows = []
     for m in KM.LANE_MUTANTS:
-        d = tmp_path / m[0]
-        csrc = KM.mutated_tree(m, str(d))
-        sim_dir = d / "tests" / "host_sim"
-        os.makedirs(sim_dir)
-        for f in os.listdir(SIM_DIR):
-            if f.endswith((".cpp", ".h")):
-                shutil.copy(os.path.join(SIM_DIR, f), sim_dir / f)
-        assert os.path.exists(os.path.join(csrc, "deflate_lane.h"))
-        so = str(sim_dir / "libhost_sim.so")
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-I", str(sim_dir), "-o", so]
-                       + [str(sim_dir / s) for s in SRCS], check=True)
-        msim = _bind(C.CDLL(so))
+        msim = _bind(C.CDLL(mutation.host_model(m, tmp_path / m[0])))
         changed = []
         for name, (level, _, _) in util.TIE_CASES.items():
             lv = oracle.LEVELS[level]
@@ -492,6 +478,19 @@ def test_inflate_lane_equals_the_oracle_on_the_rule_cases(sim, oracle, monkeypat
                 assert st == st0 and (st != 0 or (d, a) == (d0, a0)), (name, wide, budget, st, st0)
 
 
+# (name, file, text, replacement): relaxed mutants of inflate_lane.h -- they accept more, and stay in bounds.  They run only
+# in the host models, in child processes, beside the host copies of the stricter ones the GPU runs too
+# (tools/kernel_mutants.py LANE_INFLATE_MUTANTS); no GPU library is ever built from these.
+LANE_INFLATE_RELAXED = [
+    ("lane_nlen_unchecked", "inflate_lane.h", "if (length != ((~inv) & 0xFFFFu))", "if (0 && length != ((~inv) & 0xFFFFu))"),
+    ("lane_single_code_any_length", "inflate_lane.h",
+     "if ((num_codes > 1 && available > 0) || (num_codes == 1 && L.u16(counts_off, 1) != 1))",
+     "if (num_codes > 1 && available > 0)"),
+    ("lane_incomplete_ok", "inflate_lane.h",
+     "if ((num_codes > 1 && available > 0) || (num_codes == 1 && L.u16(counts_off, 1) != 1))",
+     "if (num_codes == 1 && L.u16(counts_off, 1) != 1)"),
+]
+
 _LANE_CHILD = r"""
 import ctypes as C, json, os, sys
 sys.path.insert(0, os.path.join(sys.argv[2], "tests")); sys.path.insert(0, os.path.join(sys.argv[2], "tests", "golden"))
@@ -513,38 +512,16 @@ print(json.dumps(changed))
 
 
 def test_inflate_lane_mutants_are_killed(oracle, tmp_path, capsys):
-    """tools/kernel_mutants.py's mutants of inflate_lane.h -- the stricter ones the GPU runs too, and relaxed ones --
-    each built into a host model of its own and run over every rule case (tests/golden/inflate_rules.py) in a child
+    """The mutants of inflate_lane.h -- the stricter ones the GPU runs too (tools/kernel_mutants.py), and the relaxed ones
+    above -- each built into a host model of its own and run over every rule case (tests/golden/inflate_rules.py) in a child
     process, plain and wide: each must change a result.  A relaxed mutant that read out of bounds would end its child,
     not this run (and would count as a kill only through the results it printed: none)."""
-    import concurrent.futures
-    import json
     import os
-    import shutil
-    import subprocess
-    import sys
 
-    from host_sim import HERE as SIM_DIR, SRCS
     from tools import kernel_mutants as KM
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    muts = [(m, "stricter") for m in KM.LANE_INFLATE_MUTANTS] + [(m, "relaxed") for m in KM.LANE_INFLATE_RELAXED]
-
-    def build(m):
-        d = tmp_path / m[0]
-        KM.mutated_tree(m, str(d))
-        sim_dir = d / "tests" / "host_sim"
-        os.makedirs(sim_dir)
-        for f in os.listdir(SIM_DIR):
-            if f.endswith((".cpp", ".h")):
-                shutil.copy(os.path.join(SIM_DIR, f), sim_dir / f)
-        so = str(sim_dir / "libhost_sim.so")
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-I", str(sim_dir), "-o", so]
-                       + [str(sim_dir / s) for s in SRCS], check=True)
-        return so
-
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
-        sos = list(ex.map(build, [m for m, _ in muts]))
+    muts = [(m, "stricter") for m in KM.LANE_INFLATE_MUTANTS] + [(m, "relaxed") for m in LANE_INFLATE_RELAXED]
+    sos = mutation.build_all(lambda m: mutation.host_model(m, tmp_path / m[0]), [m for m, _ in muts])
     rows = []
     for (m, kind), so in zip(muts, sos):
         changed, notes = set(), []
@@ -553,12 +530,11 @@ def test_inflate_lane_mutants_are_killed(oracle, tmp_path, capsys):
             env.pop("SIM_INFLATE_WIDE", None)
             if wide == "1":
                 env["SIM_INFLATE_WIDE"] = "1"
-            r = subprocess.run([sys.executable, "-c", _LANE_CHILD, so, root], env=env, stdout=subprocess.PIPE,
-                               stderr=subprocess.STDOUT, timeout=600)
-            if r.returncode != 0:
-                notes.append("child rc %d" % r.returncode)
+            rc, got, _ = mutation.run_child(_LANE_CHILD, so, mutation.ROOT, env=env, timeout=600)
+            if rc != 0:
+                notes.append("child rc %d" % rc)
                 continue
-            changed |= set(json.loads(r.stdout.decode().strip().splitlines()[-1]))
+            changed |= set(got)
         rows.append((m[0], kind, sorted(changed), notes))
     with capsys.disabled():
         print("\ninflate_lane.h mutants in the host models against the rule cases")

@@ -6,21 +6,19 @@
   - the host model (tests/host_sim/sim_inflate.cpp: inflate_lane.h and inflate_span.h on an emulated wave) on every
     item of the families it can run, plain, with wide turns, and with spans in both lane orders, its destination at an
     unaligned offset inside a poisoned buffer: status, length, bytes, Adler-32 and both guards;
-  - tools/kernel_mutants.py ROOM_MUTANTS, each built into a host model of its own and run in child processes: every
+  - ROOM_MUTANTS below, each built into a host model of its own and run in child processes: every
     one must fail the item it names.
 
 Limits of the CPU side: wave_copy_match, the stored-block copy of inflate.hip and the block path's stores have no host
 twin.  Their coverage is tests/test_gpu_inflate_room.py."""
 import ctypes as C
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import inflate_room_cases as RC
+import mutation
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # how the host model is run: environment of sim_inflate (read at every call)
@@ -188,6 +186,37 @@ def test_host_model_keeps_to_its_room(oracle, monkeypatch, mode, family):
 
 
 # ---- the mutants ---------------------------------------------------------------------------------------------------
+# (name, file, text, replacement, killer): one-line mutants of inflate's ROOM -- where a stream's bytes may go and when it
+# is refused for want of room -- killed on the CPU only, by test_room_mutants_are_killed below:
+# each is built into a host model of its own and run in a child process over the items of tests/inflate_room_cases.py.
+# killer: (the host model's mode, the item that must fail), or ("equivalent", why): no item may fail in any mode.
+# THESE MUTANTS WRITE OUT OF THEIR ROOM BY DESIGN (up to 15 bytes; the test's 64-byte guards hold that inside its own
+# buffer).  They are never built into a GPU library: the table lies here, where no tool that builds one can read it.
+# Each runs in the ONE mode its entry names: the two literal mutants leave out_pos one past cap_min, and the wide turn's
+# `cap_min - out_pos` would then wrap (its child would write all over its heap) -- "plain" decodes symbol by symbol.
+ROOM_MUTANTS = [
+    ("lane_copy_gate_without_its_8", "inflate_lane.h", "(uint64_t)pos + len + 8 <= hard_cap", "(uint64_t)pos + len <= hard_cap",
+     ("plain", "lane/L9_d8_g0/R=79/limit R, cap R")),
+    ("span_flush_quad_over_the_tail", "inflate_span.h", "if (i + 16u <= tile_len) {", "if (i < tile_len) {", ("span_a", "span/skewed_k5_d17/R=10220/no limit, cap R")),
+    ("lane_literal_at_cap_min", "inflate_lane.h", "\n      if (d.out_pos >= d.cap_min) { d.overflow(",
+     "\n      if (d.out_pos > d.cap_min) { d.overflow(", ("plain", "literal_last/n20000/R=19999/no limit, cap R")),
+    ("lane_fixed_literal_at_cap_min", "inflate_lane.h", "\n    if (d.out_pos >= d.cap_min) { d.overflow(",
+     "\n    if (d.out_pos > d.cap_min) { d.overflow(", ("plain", "literal_last/n1/R=0/no limit, cap R")),
+    ("lane_match_to_cap_min_refused", "inflate_lane.h",
+     "if ((uint64_t)d.out_pos + length > d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return SYM_STOP; }",
+     "if ((uint64_t)d.out_pos + length >= d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return SYM_STOP; }",
+     ("plain", "lane/L3_d1_g0/R=73/limit R, cap R")),
+    ("lane_stored_to_cap_min_refused", "inflate_lane.h",
+     "if ((uint64_t)d.out_pos + length > d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return true; }",
+     "if ((uint64_t)d.out_pos + length >= d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return true; }",
+     ("plain", "stored/len16_behind0/R=16/limit R, cap R")),
+    ("cap_min_from_hard_cap_alone", "inflate_lane.h", "d.cap_min = d.limit < d.hard_cap ? d.limit : d.hard_cap;", "d.cap_min = d.hard_cap;",
+     ("plain", "lane/L9_d8_g5/R=83/limit R, cap R+40")),
+    ("span_far_pass_ungated", "inflate_span.h", "if (out_pos + 32u <= hard_cap && wv::any(has_far != 0u)) {", "if (wv::any(has_far != 0u)) {",
+     ("equivalent", "the gate keeps 16-byte LOADS of far sources inside the room; the pass stores into the tile (LDS) only, and what it "
+                    "does not fetch the rounds behind it copy: the host model, whose guards are readable, gives the same bytes")),
+]
+
 _CHILD = r"""
 import ctypes as C, json, os, sys
 root, so, families = sys.argv[1], sys.argv[2], sys.argv[3].split(",")
@@ -202,41 +231,23 @@ print(json.dumps([i for f in families for i, _ in T.sim_failures(sim, oracle, RC
 
 
 def test_room_mutants_are_killed(oracle, tmp_path, capsys):
-    """tools/kernel_mutants.py ROOM_MUTANTS, each built into a host model of its own and run in child processes (they
+    """ROOM_MUTANTS, each built into a host model of its own and run in child processes (they
     write out of their room by design: the guards hold it inside the child's own buffer), in the mode its entry names:
     the item it names must fail; one marked equivalent must fail none of the host model's items in any mode."""
     import concurrent.futures
-    import shutil
-
-    from host_sim import HERE as SIM_DIR, SRCS
-    from tools import kernel_mutants as KM
-
-    def build(m):
-        d = tmp_path / m[0]
-        KM.mutated_tree(m, str(d))
-        sim_dir = d / "tests" / "host_sim"
-        os.makedirs(sim_dir)
-        for f in os.listdir(SIM_DIR):
-            if f.endswith((".cpp", ".h")):
-                shutil.copy(os.path.join(SIM_DIR, f), sim_dir / f)
-        so = str(sim_dir / "libhost_sim.so")
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-I", str(sim_dir), "-o", so]
-                       + [str(sim_dir / s) for s in SRCS], check=True)
-        return so
 
     def child(so, mode, families):
         env = {k: v for k, v in os.environ.items() if not k.startswith("SIM_INFLATE")}
         env.update(MODES[mode])
-        r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, so, ",".join(families)], env=env, stdout=subprocess.PIPE,
-                           stderr=subprocess.STDOUT, timeout=900)
-        assert r.returncode == 0, (mode, r.returncode, r.stdout.decode()[-800:])
-        return json.loads(r.stdout.decode().strip().splitlines()[-1])
+        rc, failed, err = mutation.run_child(_CHILD, ROOT, so, ",".join(families), env=env)
+        assert rc == 0, (mode, rc, err[-800:])
+        return failed
 
     known = {RC.item_id(it) for it in RC.all_items()}
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
-        sos = list(ex.map(build, KM.ROOM_MUTANTS))
+    sos = mutation.build_all(lambda m: mutation.host_model(m, tmp_path / m[0]), ROOM_MUTANTS)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=mutation.workers()) as ex:
         jobs = []
-        for m, so in zip(KM.ROOM_MUTANTS, sos):
+        for m, so in zip(ROOM_MUTANTS, sos):
             killer = m[4]
             if killer[0] == "equivalent":
                 jobs += [(m[0], mode, ex.submit(child, so, mode, RC.SIM_FAMILIES)) for mode in sorted(MODES)]
@@ -248,9 +259,9 @@ def test_room_mutants_are_killed(oracle, tmp_path, capsys):
         for name, mode, job in jobs:
             failed.setdefault(name, []).extend(job.result())
     rows = []
-    for m in KM.ROOM_MUTANTS:
+    for m in ROOM_MUTANTS:
         killer, got = m[4], failed[m[0]]
-        ok = not got if killer[0] == "equivalent" else killer[1] in got
+        ok = mutation.verdict(killer if killer[0] == "equivalent" else killer[1], got)
         rows.append((m[0], "equivalent" if killer[0] == "equivalent" else killer[1], len(got), ok))
     with capsys.disabled():
         print("\ninflate room mutants in the host models")

@@ -5,11 +5,11 @@ runs the mode is checked in tests/test_gpu_inflate_size.py."""
 import collections
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import pytest
 
+import mutation
 import size_cases
 import util
 from host_sim import HERE as HOST_SIM_DIR, lib as host_sim_lib
@@ -27,10 +27,8 @@ FORMS = {"plain-512": (0, 512), "plain-7": (0, 7), "span-a": (1, 24), "span-d": 
 
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("size_sim") / "libsize_sim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-I", HOST_SIM_DIR, "-o", so,
-                    os.path.join(HERE, "size_sim", "sim_size.cpp")], check=True)
-    L = C.CDLL(so)
+    L = C.CDLL(mutation.gxx(tmp_path_factory.mktemp("size_sim") / "libsize_sim.so", [os.path.join(HERE, "size_sim", "sim_size.cpp")],
+                            include=[HOST_SIM_DIR], extra=["-Wall", "-Wno-unknown-pragmas"]))
     L.sim_size.restype = C.c_int
     L.sim_size.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint32, C.c_int,
                            C.c_int, C.POINTER(C.c_uint64)]

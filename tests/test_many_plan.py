@@ -5,12 +5,12 @@ sees any of this; tests/test_gpu_many_plan.py ties the library's calls to the sa
 import ctypes as C
 import os
 import random
-import subprocess
 
 import pytest
 
 import util  # noqa: F401  (sets sys.path through conftest)
 import host_sim
+import mutation
 from host_sim import MANY_DEFLATE, MANY_INFLATE, MANY_RECODE
 
 MIN_DST = 256 << 10  # forms.h BLOCKS_BATCH_MIN_DST
@@ -234,40 +234,43 @@ def _slot(v):
 
 # ---- the mutants ---------------------------------------------------------------------------------------------------------
 
+# (name, file, text, replacement, killer): one-line mutants of the many-stream forms' plan (host_pipeline.h plan_many), killed on
+# the CPU only -- each built into a model of its own (tests/host_sim/sim_many.cpp) by test_plan_mutants_are_killed below.
+# killer: the row of ROWS it must fail.  A wrong cut still gives right bytes: no parity test would notice any of these.
+MANY_PLAN_MUTANTS = [
+    ("taper_shares_not_doubled", "host_pipeline.h", "taper ? 2 * g - 1 : g;", "taper ? g : g;", "taper_K4"),
+    ("taper_divides_by_K", "host_pipeline.h", "so / shares * before", "so / K * before", "taper_K4"),
+    ("shrink_either_clause", "host_pipeline.h", "n / K < least && so / K < least * 65536", "n / K < least || so / K < least * 65536",
+     "shrink_bytes_at_the_limit"),
+    ("slot_without_its_gap", "host_pipeline.h", "return (len + 255) / 256 * 256 + 256;", "return (len + 255) / 256 * 256;", "slots"),
+    ("mid_off_runs_on", "host_pipeline.h", "uint64_t mo = 0;", "uint64_t mo = p.mid_arena;", "recode_mid_arena"),
+    ("six_from_two_gib", "host_pipeline.h", "staged_bytes >= ((uint64_t)1 << 30)", "staged_bytes >= ((uint64_t)1 << 31)", "count_at_a_gib"),
+]
+
+
 def _build_model(csrc_dir, so):
     """sim_many.cpp alone against a copy of zipc_amd/csrc"""
-    src = open(os.path.join(host_sim.HERE, "sim_many.cpp")).read()
-    inc = '#include "../../zipc_amd/csrc/host_pipeline.h"'
-    assert src.count(inc) == 1
-    cpp = so[:-3] + ".cpp"
-    with open(cpp, "w") as f:
-        f.write(src.replace(inc, '#include "%s"' % os.path.join(csrc_dir, "host_pipeline.h")))
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", so, cpp], check=True)
-    return host_sim.bind_many(C.CDLL(so))
+    return host_sim.bind_many(C.CDLL(mutation.single_model(os.path.join(host_sim.HERE, "sim_many.cpp"), "host_pipeline.h", csrc_dir, so)))
 
 
 def test_plan_mutants_are_killed(tmp_path):
-    """tools/kernel_mutants.py MANY_PLAN_MUTANTS: each one-line mutant of host_pipeline.h built into a model of its own; the
+    """MANY_PLAN_MUTANTS: each one-line mutant of host_pipeline.h built into a model of its own; the
     row the table names must fail on it, and every row passes on the unmutated header built the same way."""
-    import concurrent.futures
-
     from tools import kernel_mutants as KM
 
-    names = [m[0] for m in KM.MANY_PLAN_MUTANTS]
-    assert len(names) == len(set(names)) >= 6 and all(m[4] in ROWS for m in KM.MANY_PLAN_MUTANTS)
+    names = [m[0] for m in MANY_PLAN_MUTANTS]
+    assert len(names) == len(set(names)) >= 6 and all(m[4] in ROWS for m in MANY_PLAN_MUTANTS)
     base = _build_model(KM.CSRC, str(tmp_path / "plain.so"))
     for row in ROWS.values():
         row(base)
 
     def build(m):
         d = str(tmp_path / m[0])
-        os.makedirs(d)
         return _build_model(KM.mutated_tree(m, d), os.path.join(d, "mutant.so"))
 
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
-        models = list(ex.map(build, KM.MANY_PLAN_MUTANTS))
+    models = mutation.build_all(build, MANY_PLAN_MUTANTS)
     missed = []
-    for m, model in zip(KM.MANY_PLAN_MUTANTS, models):
+    for m, model in zip(MANY_PLAN_MUTANTS, models):
         try:
             ROWS[m[4]](model)
             missed.append(m[0])

@@ -7,7 +7,6 @@ what the byte-parity tests could have seen."""
 import concurrent.futures
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,9 +16,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import host_sim  # noqa: E402
 import match_cases as mc  # noqa: E402
+import mutation  # noqa: E402
 
 LEVELS = (1, 2, 3)
-WORKERS = min(16, os.cpu_count() or 1)
+WORKERS = mutation.workers()
 
 
 @pytest.fixture(scope="module")
@@ -205,12 +205,10 @@ SPLIT = "// -----"  # the reference is the file's top half (sim_match.cpp)
 def build_mutant(name, old, new, out_dir):
     src = open(os.path.join(HERE, "host_sim", "sim_match.cpp")).read()
     top = src[:src.index(SPLIT)]
-    assert top.count(old) == 1, "%s: the line occurs %d times" % (name, top.count(old))
     path = os.path.join(out_dir, "m_%d" % [m[0] for m in MUTANTS].index(name))
     with open(path + ".cpp", "w") as f:
-        f.write(top.replace(old, new))
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", path + ".so", path + ".cpp"])
-    return host_sim.bind_match(C.CDLL(path + ".so"))
+        f.write(mutation.patched(top, old, new, "sim_match.cpp " + name))
+    return host_sim.bind_match(C.CDLL(mutation.gxx(path + ".so", [path + ".cpp"], extra=["-Wall"])))
 
 
 def mutant_streams():
@@ -226,8 +224,7 @@ def mutant_streams():
 
 def test_every_mutant_of_the_reference_changes_a_record(sim, refs, tmp_path, capsys):
     streams = mutant_streams()
-    with concurrent.futures.ThreadPoolExecutor(max_workers=WORKERS) as ex:
-        libs = list(ex.map(lambda m: build_mutant(m[0], m[1], m[2], str(tmp_path)), MUTANTS))
+    libs = mutation.build_all(lambda m: build_mutant(m[0], m[1], m[2], str(tmp_path)), MUTANTS)
     reads = {lv: {s.name: host_sim.match_parse_reads(sim, len(s), lv, *refs(lv)[s.name]) for s in streams} for lv in LEVELS}
     rows, wrong = [], []
     for (name, _, _, why), ML in zip(MUTANTS, libs):

@@ -1,6 +1,5 @@
 """The mutation table (tests/golden/mutants.py): every one-line mutant of either reading of the reference's encoder
 must change a committed vector of tests/golden/deflate_vectors.json.  No GPU."""
-import concurrent.futures
 import hashlib
 import json
 import os
@@ -8,6 +7,7 @@ import sys
 
 import pytest
 
+import mutation
 import util
 
 sys.path.insert(0, util.GOLDEN)
@@ -56,8 +56,7 @@ def _oracle_changes(O, doc):
 def oracle_mutants(tmp_path_factory):
     """every oracle mutant built with gcc (as oracle/Makefile builds the oracle): name -> .so"""
     d = str(tmp_path_factory.mktemp("oracle_mutants"))
-    with concurrent.futures.ThreadPoolExecutor(max_workers=os.cpu_count() or 1) as ex:
-        sos = list(ex.map(lambda m: mutants.build_oracle(m, d), mutants.MUTANTS))
+    sos = mutation.build_all(lambda m: mutants.build_oracle(m, d), mutants.MUTANTS)
     return {m.name: so for m, so in zip(mutants.MUTANTS, sos)}
 
 
@@ -135,6 +134,45 @@ def test_a_mutant_must_match_once():
     assert mutants.patched("abc", "b", "B", "t") == "aBc"
 
 
+# ---- the harness itself (tests/mutation.py) ----------------------------------------------------------------------------
+
+def test_patched_names_the_place_the_count_and_the_text():
+    assert mutants.patched is mutation.patched  # one rule, one behaviour
+    for text, n in (("abc", 0), ("a.x.b.x", 2)):
+        with pytest.raises(AssertionError) as e:
+            mutation.patched(text, "x", "y", "some_header.h a_mutant")
+        assert "some_header.h a_mutant" in str(e.value) and "occurs %d times" % n in str(e.value) and "'x'" in str(e.value)
+    assert mutation.patched("a.x.b", "x", "y", "t") == "a.y.b"
+
+
+def test_verdict_corners():
+    eq = ("equivalent", "why no input can tell")
+    assert mutation.verdict("case_a", ["case_b", "case_a"]) and not mutation.verdict("case_a", ["case_b"])
+    assert not mutation.verdict("case_a", [])  # a survivor
+    assert mutation.verdict("case_a", ["case_a"], crashed=True)  # (the killer was seen to change before the child ended)
+    assert mutation.verdict(eq, []) and not mutation.verdict(eq, ["case_b"])
+    assert not mutation.verdict(eq, [], crashed=True)  # a child that ended early has not shown that nothing changes
+
+
+def test_a_no_op_mutant_is_reported_as_a_survivor(tmp_path):
+    """a line of adler_chain.h replaced by itself and a comment, through the build and the judge of
+    tests/test_adler_chain_sim.py: the judge must say that the named killer did not change -- a table can not pass vacuously"""
+    import checksum_cases as CC
+    import host_sim
+    import test_adler_chain_sim as T
+
+    cases = CC.mutation_cases()
+    small = sorted(cases, key=lambda n: len(cases[n]["sums"]))[:2]
+    # what the unmutated header says of them: the walk's value by replay (asserted of it in test_adler_chain_mutants_are_killed)
+    base = {n: [CC.walk(cases[n]["sums"], cases[n]["length"])[0], host_sim.ADLER_REPLAY] for n in small}
+    line = "return C >= 0x80000000ull;"
+    no_op = ("no_op", "adler_chain.h", line, line + "  /* the same line */", small[0])
+    run = T._run_child(T._build_model(no_op, tmp_path), [small[0]])
+    assert run[0] == 0 and all(n in run[1] for n in small), run[2]
+    assert T.judge(no_op, base, run) == ([], False)  # survived
+    assert T.judge(no_op[:4] + (("equivalent", "it is the same line"),), base, run) == ([], True)
+
+
 # ---- inflate: tests/golden/inflate_rules.py against mutants.INFLATE_MUTANTS ------------------------------------------
 
 def _inflate_changes(O, cases):
@@ -160,8 +198,7 @@ def test_every_inflate_oracle_mutant_is_killed_by_its_named_rule_case(oracle, tm
     names = [m.name for m in mutants.INFLATE_MUTANTS]
     assert len(names) == len(set(names)) >= 27
     assert all(m.killer is None or m.killer in cases for m in mutants.INFLATE_MUTANTS)
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
-        sos = list(ex.map(lambda m: mutants.build_oracle_patched(m.name, m.patches, str(tmp_path)), mutants.INFLATE_MUTANTS))
+    sos = mutation.build_all(lambda m: mutants.build_oracle_patched(m.name, m.patches, str(tmp_path)), mutants.INFLATE_MUTANTS)
     rows, bad = [], []
     saved_lib, saved_env = O._lib, os.environ.get("ZD_ORACLE_LIB")
     try:

@@ -5,11 +5,11 @@ the few lines of `expect` below, not the header; a mutation table over the heade
 tests/test_gpu_inflate_packed.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import mutation
 import util  # noqa: F401  (sets sys.path through conftest)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -26,11 +26,10 @@ MAX_STREAM_LEN = 0xFFFF0000
 ALIGNS = (1, 2, 16, 4096)
 
 
-def _build(so, header=None):
-    cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-I", CSRC, "-o", so]
-    if header:
-        cmd.append('-DPACKED_HEADER="%s"' % header)
-    subprocess.run(cmd + [SIM], check=True)
+FLAGS = dict(include=[CSRC], extra=["-Wall", "-Wno-unknown-pragmas"])
+
+
+def _bind(so):
     L = C.CDLL(so)
     L.sim_packed_run.restype = C.c_uint64
     L.sim_packed_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -45,7 +44,7 @@ def _build(so, header=None):
 
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    return _build(str(tmp_path_factory.mktemp("packed_sim") / "libpacked_sim.so"))
+    return _bind(mutation.gxx(tmp_path_factory.mktemp("packed_sim") / "libpacked_sim.so", [SIM], **FLAGS))
 
 
 def _descs(n):
@@ -237,15 +236,11 @@ def _observe(L):
 def test_mutants_of_the_header_are_killed(sim, tmp_path):
     """each one-line mutant of packed_layout.h, built into a model of its own, changes what the model says of at least one
     case (a verdict, a descriptor, a result, need, or room handed to inflate outside the arena, which the model counts)"""
-    src = open(HEADER).read()
     base = _observe(sim)
     assert all(row[7][0] == 0 for row in base)
     alive = []
     for k, (name, line, mutated) in enumerate(MUTANTS):
-        assert src.count(line) == 1, (name, "the line is not in the header, or not once")
-        hdr = str(tmp_path / ("mutant%d.h" % k))
-        with open(hdr, "w") as f:
-            f.write(src.replace(line, mutated))
-        if _observe(_build(str(tmp_path / ("libmutant%d.so" % k)), hdr)) == base:
+        so = mutation.header_model(SIM, "PACKED_HEADER", HEADER, line, mutated, str(tmp_path / ("mutant%d" % k) / "libmutant.so"), **FLAGS)
+        if _observe(_bind(so)) == base:
             alive.append(name)
     assert alive == []

@@ -4,11 +4,11 @@ interior form (no clamps, no masks of the stream's end, no block cut) or in the 
 the header.  No GPU; the kernels are checked in tests/test_gpu_parse_tiles.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import mutation
 import util  # noqa: F401  (sets sys.path through conftest)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -21,9 +21,8 @@ STEP_MAX = 255 + 258  # deferral literals + the longest match: the furthest a ma
 
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("parse_tile_sim") / "libparse_tile_sim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-I", CSRC, "-o", so, SIM], check=True)
-    L = C.CDLL(so)
+    L = C.CDLL(mutation.gxx(tmp_path_factory.mktemp("parse_tile_sim") / "libparse_tile_sim.so", [SIM], include=[CSRC],
+                            extra=["-Wall", "-Wno-unknown-pragmas"]))
     L.sim_parse_tile_interior.restype = C.c_int
     L.sim_parse_tile_interior.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.sim_parse_tile_forms.restype = None

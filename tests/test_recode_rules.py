@@ -7,6 +7,7 @@ import subprocess
 
 import pytest
 
+import mutation
 import util  # noqa: F401  (sets sys.path through conftest)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -16,9 +17,8 @@ MAX_MID = 1000
 
 
 def build(tmp, *flags):
-    exe = str(tmp / ("sim_recode" + ("_san" if flags else "")))
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Wno-unknown-pragmas", *flags, "-o", exe, SRC], check=True)
-    return exe
+    return mutation.gxx(tmp / ("sim_recode" + ("_san" if flags else "")), [SRC], shared=False, opt="-O1",
+                        extra=["-g", "-Wall", "-Wextra", "-Wno-unknown-pragmas", *flags])
 
 
 @pytest.fixture(scope="module")

@@ -8,9 +8,10 @@ import ctypes as C
 import itertools
 import os
 import shutil
-import subprocess
 
 import pytest
+
+import mutation
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -31,15 +32,12 @@ def _build(tmp, patch=None):
         for h in ("inflate_blocks.h", "forms.h", "tuning.h", "zd_common.h"):
             shutil.copy(os.path.join(CSRC, h), tree)
         p = os.path.join(tree, "inflate_blocks.h")
-        text = open(p).read()
-        assert text.count(patch[0]) == 1, "the mutant's patch must match exactly once"
-        open(p, "w").write(text.replace(patch[0], patch[1]))
+        text = mutation.patched(open(p).read(), patch[0], patch[1], "inflate_blocks.h")
+        open(p, "w").write(text)
         os.makedirs(os.path.join(str(tmp), "tests", "size_blocks_sim"))
         src = os.path.join(str(tmp), "tests", "size_blocks_sim", "sim_size_blocks.cpp")
         shutil.copy(SIM, src)
-    so = os.path.join(str(tmp), "libsize_blocks_sim.so")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src], check=True)
-    L = C.CDLL(so)
+    L = C.CDLL(mutation.gxx(os.path.join(str(tmp), "libsize_blocks_sim.so"), [src], opt="-O1", extra=["-Wall", "-Wno-unknown-pragmas"]))
     for f in ("sim_blocks_min_src", "sim_blocks_max_src", "sim_blocks_max_streams", "sim_size_scratch_budget"):
         getattr(L, f).restype = C.c_uint64
     L.sim_size_gate.restype = C.c_int

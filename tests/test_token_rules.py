@@ -10,20 +10,18 @@
         tok[i] == i  iff  byte i is a literal or a stored byte;
         else tok[i] < i and tok[i] lies on byte i's chain of copies (an ancestor);
         follow 0 (sources written down plainly): tok[i] == src[i] exactly.
-  - tools/kernel_mutants.py TOKEN_MUTANTS: one-line changes of the span decoder's token parts, each built into a host model
+  - TOKEN_MUTANTS below: one-line changes of the span decoder's token parts, each built into a host model
     of its own; each is killed by the stream its entry names, or breaks no word of any stream (equivalent).
 tests/test_gpu_inflate_tokens.py holds the device's words to the same reference.
 """
-import concurrent.futures
 import json
 import os
-import subprocess
-import sys
 import zlib
 
 import numpy as np
 import pytest
 
+import mutation
 import token_cases as TC
 import token_ref as TR
 
@@ -299,16 +297,14 @@ def _run_children(so, names, configs, workers=8):
     lots = [lot for lot in lots if lot]
 
     def child(lot):
-        r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, so, json.dumps(lot)], stdout=subprocess.PIPE,
-                           stderr=subprocess.PIPE, timeout=900)
-        if r.returncode != 0:  # (a mutant may crash its model: every stream of the lot counts as broken)
-            return {"%s/crashed" % name: {"status": r.returncode, "bytes": True, "words": -1, "first": r.stderr.decode()[-300:]} for name, _ in lot}
-        return json.loads(r.stdout.decode().strip().splitlines()[-1])
+        rc, got, err = mutation.run_child(_CHILD, ROOT, so, json.dumps(lot))
+        if rc != 0:  # (a mutant may crash its model: every stream of the lot counts as broken)
+            return {"%s/crashed" % name: {"status": rc, "bytes": True, "words": -1, "first": err[-300:]} for name, _ in lot}
+        return got
 
     out = {}
-    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as ex:
-        for part in ex.map(child, lots):
-            out.update(part)
+    for part in mutation.build_all(child, lots):
+        out.update(part)
     return out
 
 
@@ -392,38 +388,44 @@ NEAR_END_BITS = 1024
 # the streams the mutants run over: every made stream for the block path but the long ones (nothing in those is not in these)
 MUTANT_STREAMS = ["cross_near", "len_dist_grid", "overlap_between_literals", "overlap_back_to_back", "tile_edges", "chain_255_256_257",
                   "kinds_fixed_first", "kinds_stored_first", "interval_checkpoint_near_end"]
+# (name, file, text, replacement, killer): one-line mutants of the TOKEN parts of the span decoder (inflate_span.h: what a byte of a
+# match is written down as a copy of), killed on the CPU only and never built for the GPU, in the manner of
+# tests/test_inflate_room_rules.py ROOM_MUTANTS: each is built into a host model of its own and run in child processes by
+# test_token_mutants_are_killed below, which holds every word of tok[] to tests/token_ref.py.  killer: the stream of
+# tests/token_cases.py whose words it must break, or ("equivalent", why): it must break none.  The test prints per mutant whether
+# the BYTES alone would have caught it.
+TOKEN_MUTANTS = [
+    ("follow_from_off_by_one", "inflate_span.h", "const uint32_t from = dp + 32768u - dist;", "const uint32_t from = dp + 32767u - dist;",
+     "len_dist_grid"),
+    ("follow_in_tile_test_strict", "inflate_span.h", "if (sp >= 32768u && (mbits[(sp - 32768u) >> 5] >> (sp & 31u)) & 1u)",
+     "if (sp > 32768u && (mbits[(sp - 32768u) >> 5] >> (sp & 31u)) & 1u)",
+     ("equivalent", "(tile_edges has sources that begin at a tile's first byte) sp == 32768 is tile position 0: not following it inside the tile leaves the byte a copy of tile byte 0, a byte of "
+                    "the same chain one link further from the literal -- a longer way, never a wrong one")),
+    ("follow_sweep_test_strict", "inflate_span.h", "v[u] = sp >= 32768u ? out_pos", "v[u] = sp > 32768u ? out_pos",
+     ("equivalent", "sp == 32768 then reads tok[out_pos], the word of tile byte 0 itself: out_pos while nobody has written it, or what "
+                    "tile byte 0 is a copy of -- the same chain either way")),
+    ("follow_wrap_dropped", "inflate_span.h", "r = r + 1u == dist ? 0u : r + 1u;", "r = r + 1u;",
+     ("equivalent", "without the wrap byte i >= dist of an overlapping match is written down as a copy of byte i - dist of the match "
+                    "itself, which is src[i] to the letter: one link more per period, the same chain")),
+    ("plain_source_not_advanced", "inflate_span.h", "tok[at + i] = from + i;", "tok[at + i] = from;", "len_dist_grid"),
+    ("follow_step_reads_the_neighbour", "inflate_span.h", "srcpos[b] = srcpos[sp - 32768u];", "srcpos[b] = srcpos[sp - 32767u];",
+     "len_dist_grid"),
+    ("follow_store_inverted", "inflate_span.h", "if (v[u] != out_pos + b) tok[out_pos + b] = v[u];",
+     "if (v[u] == out_pos + b) tok[out_pos + b] = v[u];", "len_dist_grid"),
+]
 
 
 def test_token_mutants_are_killed(tmp_path, capsys):
-    import shutil
-
-    from host_sim import HERE as SIM_DIR, SRCS
-    from tools import kernel_mutants as KM
-
-    def build(m):
-        d = tmp_path / m[0]
-        KM.mutated_tree(m, str(d))
-        sim_dir = d / "tests" / "host_sim"
-        os.makedirs(sim_dir)
-        for f in os.listdir(SIM_DIR):
-            if f.endswith((".cpp", ".h")):
-                shutil.copy(os.path.join(SIM_DIR, f), sim_dir / f)
-        so = str(sim_dir / "libhost_sim.so")
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-I", str(sim_dir), "-o", so]
-                       + [str(sim_dir / s) for s in SRCS], check=True)
-        return so
-
     assert all(TC.by_name(n).taken and TC.by_name(n).blocks is not None for n in MUTANT_STREAMS)
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
-        sos = list(ex.map(build, KM.TOKEN_MUTANTS))
+    sos = mutation.build_all(lambda m: mutation.host_model(m, tmp_path / m[0]), TOKEN_MUTANTS)
     rows = []
-    for m, so in zip(KM.TOKEN_MUTANTS, sos):
+    for m, so in zip(TOKEN_MUTANTS, sos):
         killer = m[4]
         assert killer[0] == "equivalent" or killer in MUTANT_STREAMS, m[0]
         got = _run_children(so, MUTANT_STREAMS, CONFIGS)
         by_words = sorted({k.split("/")[0] for k, v in got.items() if v["words"]})
         by_bytes = sorted({k.split("/")[0] for k, v in got.items() if v["bytes"]})
-        ok = not by_words and not by_bytes if killer[0] == "equivalent" else killer in by_words
+        ok = mutation.verdict(killer, by_words + by_bytes if killer[0] == "equivalent" else by_words)
         rows.append((m[0], "equivalent" if killer[0] == "equivalent" else killer, len(by_words), len(by_bytes), ok))
     with capsys.disabled():
         print("\ntoken mutants in the host model (%d streams, %d runs each)" % (len(MUTANT_STREAMS), len(CONFIGS)))

@@ -3,10 +3,10 @@ and this test -- compiled with g++ (tests/zlib_sim/sim_zlib.cpp) and held agains
 zlib_compress.  No GPU; the kernels that apply the rules are checked in tests/test_gpu_zlib_batch.py."""
 import ctypes as C
 import os
-import subprocess
 
 import pytest
 
+import mutation
 import util  # noqa: F401  (sets sys.path through conftest)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -15,10 +15,8 @@ HEADER_STATUSES = (1, 3, 4, 5)  # what the reference's checks of the first two b
 
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("zlib_sim") / "libzlib_sim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so,
-                    os.path.join(HERE, "zlib_sim", "sim_zlib.cpp")], check=True)
-    L = C.CDLL(so)
+    L = C.CDLL(mutation.gxx(tmp_path_factory.mktemp("zlib_sim") / "libzlib_sim.so", [os.path.join(HERE, "zlib_sim", "sim_zlib.cpp")],
+                            extra=["-Wall", "-Wno-unknown-pragmas"]))
     L.sim_zlib_open_status.restype = C.c_uint
     L.sim_zlib_open_status.argtypes = [C.c_ulonglong, C.c_uint, C.c_uint]
     L.sim_zlib_open_status_all.restype = None

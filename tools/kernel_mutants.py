@@ -20,16 +20,14 @@ the fixed path, the serial header and stored code, which the host models compile
 makes a check STRICTER -- it refuses more or stops earlier -- so it touches no memory the real kernel does not.  Each
 one of the decoding copies must make the rule tests fail.  The span's refusals hand a symbol to the plain step, so a
 stricter refusal must change NO result: those are listed as expected to survive, and the rule tests (under every
-override) passing under them is what shows the hand-off right.  The relaxed mutants (LANE_INFLATE_RELAXED) run only in
-the host models, in child processes: tests/test_host_sim.py::test_inflate_lane_mutants_are_killed.
+override) passing under them is what shows the hand-off right.
 
-The mutants of the Adler-32 chunk chain (ADLER_MUTANTS, zipc_amd/csrc/adler_chain.h) are killed on the CPU only:
-tests/test_adler_chain_sim.py::test_adler_chain_mutants_are_killed.
-The mutants of inflate's room (ROOM_MUTANTS: where a stream's bytes may go) are killed on the CPU only, and are never built
-for the GPU: tests/test_inflate_room_rules.py::test_room_mutants_are_killed.
-The mutants of the span decoder's token form (TOKEN_MUTANTS) are killed on the CPU only, and are never built for the GPU:
-tests/test_token_rules.py::test_token_mutants_are_killed.
-The coder_choose mutants are killed on the CPU: tests/test_host_sim.py::test_coder_choose_mutants_are_killed.
+Every table here is one a GPU library may be built from.  LANE_MUTANTS and LANE_INFLATE_MUTANTS are the host models'
+copies of the GPU ones, killed on the CPU by tests/test_host_sim.py (test_coder_choose_mutants_are_killed,
+test_inflate_lane_mutants_are_killed).  Mutants that only ever run in a host model on the CPU -- relaxed checks, the
+Adler-32 chunk chain, the many-stream plan, inflate's destination room, the span decoder's tokens -- are tables of the tests
+that run them (tests/test_host_sim.py, test_adler_chain_sim.py, test_many_plan.py, test_inflate_room_rules.py,
+test_token_rules.py); they share mutated_tree through tests/mutation.py and nothing else of this file.
 Each text must occur exactly once in its file, so a change of the kernels cannot quietly make a mutant a no-op.
 """
 import argparse
@@ -102,122 +100,8 @@ INFLATE_GPU_MUTANTS = [
     ("span_refuses_the_top_dist_symbol", "inflate_span.h", "dsym > dist_max_sym || dsym > DIST_SYM_MAX) {",
      "dsym >= dist_max_sym || dsym > DIST_SYM_MAX) {", "survives"),
 ]
-# the host models' copies: the inflate_lane.h mutants above, and relaxed ones (accept more) that stay in bounds
+# the host models' copies: the inflate_lane.h mutants above
 LANE_INFLATE_MUTANTS = [m[:4] for m in INFLATE_GPU_MUTANTS if m[1] == "inflate_lane.h"]
-LANE_INFLATE_RELAXED = [
-    ("lane_nlen_unchecked", "inflate_lane.h", "if (length != ((~inv) & 0xFFFFu))", "if (0 && length != ((~inv) & 0xFFFFu))"),
-    ("lane_single_code_any_length", "inflate_lane.h",
-     "if ((num_codes > 1 && available > 0) || (num_codes == 1 && L.u16(counts_off, 1) != 1))",
-     "if (num_codes > 1 && available > 0)"),
-    ("lane_incomplete_ok", "inflate_lane.h",
-     "if ((num_codes > 1 && available > 0) || (num_codes == 1 && L.u16(counts_off, 1) != 1))",
-     "if (num_codes == 1 && L.u16(counts_off, 1) != 1)"),
-]
-# (name, file, text, replacement, killer): one-line mutants of the Adler-32 chunk chain's arithmetic, killed on the CPU only --
-# each built into a host model of its own (tests/host_sim/sim_adler.cpp) and run in a child process by
-# tests/test_adler_chain_sim.py::test_adler_chain_mutants_are_killed.  killer: the case of tests/checksum_cases.py
-# mutation_cases() whose result it must change, or ("equivalent", why): it must change none.
-# (The ambiguity bounds the other way -- `<=` for `<` -- only replay a chunk more: equivalent by construction, not listed.)
-ADLER_MUTANTS = [
-    ("amb_low_bound_less_1", "adler_chain.h", "return C < ADLER_BASE ||", "return C < ADLER_BASE - 1 ||",
-     ("equivalent", "|s2| <= 65520, so a chunk with C = 65520 never goes negative: the bound is one wider than it must be")),
-    ("amb_low_bound_less_2", "adler_chain.h", "return C < ADLER_BASE ||", "return C < ADLER_BASE - 2 ||", "low_bound_stays_negative_last"),
-    ("amb_mid_lower_bound_plus_1", "adler_chain.h", "(C > 0x80000000ull - ADLER_BASE &&", "(C > 0x80000000ull - ADLER_BASE + 1 &&",
-     "mid_lower_bound"),
-    ("amb_mid_upper_bound_less_1", "adler_chain.h", "C < 0x80000000ull + ADLER_BASE);", "C < 0x80000000ull + ADLER_BASE - 1);",
-     ("equivalent", "s2 >= -65520, so C = 2^31 + 65520 stays at or above 2^31: the bound is one wider than it must be")),
-    ("amb_mid_upper_bound_less_2", "adler_chain.h", "C < 0x80000000ull + ADLER_BASE);", "C < 0x80000000ull + ADLER_BASE - 2);",
-     "mid_upper_bound"),
-    ("a_term_without_225", "adler_chain.h", "hi_k ? ADLER_BASE - 225u : 0u", "hi_k ? 0u : 0u", "ff_chunks"),
-    ("hi_k_strict", "adler_chain.h", "return C >= 0x80000000ull;", "return C > 0x80000000ull;",
-     ("equivalent", "C = 2^31 is ambiguous: the chunk is replayed exactly, its a term is taken back out by the same function, "
-                    "and the branch of an ambiguous chunk is read by nobody (the next chunk takes exact_next or does not care)")),
-    ("zero_residue_negative", "adler_chain.h", "(rr == 0 ? 0 : (int32_t)rr - (int32_t)ADLER_BASE)", "((int32_t)rr - (int32_t)ADLER_BASE)",
-     "zero_behind_hi_then_mid"),
-    ("exact_at_ignored", "adler_chain.h", "k == st.exact_at ? st.exact_next : adler_signed_s2(rr, prev)", "adler_signed_s2(rr, prev)",
-     "adjacent_exact"),
-    ("prev_branch_no_walk_back", "adler_chain.h", "  while (run >= 0 && run_last_hi[run] == 0xFFFFFFFFu) run--;\n", "",
-     ("equivalent", "run (k - 1) / per holds chunk k - 1, so it is never empty: the walk back never takes a step")),
-    ("prev_branch_of_k", "adler_chain.h", "int64_t run = (int64_t)((k - 1) / per);", "int64_t run = (int64_t)(k / per);",
-     "opens_run_behind_hi"),
-    ("delta_not_carried", "adler_chain.h", "const uint32_t rr = addmod(res, st.delta);", "const uint32_t rr = addmod(res, 0u);",
-     "delta_carried"),
-    ("final_without_delta", "adler_chain.h", "(total_res + st.delta) % ADLER_BASE", "(total_res + 0u) % ADLER_BASE", "mid_upper_bound"),
-    ("final_ignores_exact_at", "adler_chain.h", "if (st.exact_at == n_chunks) final_s2", "if (false && st.exact_at == n_chunks) final_s2",
-     "low_bound_stays_negative_last"),
-    ("fallback_at_the_limit", "adler_chain.h", "n_amb > amb_cap || n_amb > replay_max", "n_amb > amb_cap || n_amb >= replay_max",
-     "replay_at_its_limit"),
-    ("per_rounded_down", "adler_chain.h", "(n_chunks + n_runs - 1) / n_runs : 1", "n_chunks / n_runs : 1", "ten_chunks_four_runs"),
-    ("rfc_chain_bytes_not_reduced", "adler_chain.h", "(nb[i] % ADLER_BASE) * c1", "nb[i] * c1",
-     ("equivalent", "a run's bytes stay below 2^37 for any length the launches take and c1 < 2^16: the 64-bit product cannot wrap")),
-]
-# (name, file, text, replacement, killer): one-line mutants of the many-stream forms' plan (host_pipeline.h plan_many), killed on
-# the CPU only -- each built into a model of its own (tests/host_sim/sim_many.cpp) by
-# tests/test_many_plan.py::test_plan_mutants_are_killed.  killer: the row of that file's ROWS it must fail.  A wrong cut still
-# gives right bytes: no parity test would notice any of these.
-MANY_PLAN_MUTANTS = [
-    ("taper_shares_not_doubled", "host_pipeline.h", "taper ? 2 * g - 1 : g;", "taper ? g : g;", "taper_K4"),
-    ("taper_divides_by_K", "host_pipeline.h", "so / shares * before", "so / K * before", "taper_K4"),
-    ("shrink_either_clause", "host_pipeline.h", "n / K < least && so / K < least * 65536", "n / K < least || so / K < least * 65536",
-     "shrink_bytes_at_the_limit"),
-    ("slot_without_its_gap", "host_pipeline.h", "return (len + 255) / 256 * 256 + 256;", "return (len + 255) / 256 * 256;", "slots"),
-    ("mid_off_runs_on", "host_pipeline.h", "uint64_t mo = 0;", "uint64_t mo = p.mid_arena;", "recode_mid_arena"),
-    ("six_from_two_gib", "host_pipeline.h", "staged_bytes >= ((uint64_t)1 << 30)", "staged_bytes >= ((uint64_t)1 << 31)", "count_at_a_gib"),
-]
-# (name, file, text, replacement, killer): one-line mutants of inflate's ROOM -- where a stream's bytes may go and when it
-# is refused for want of room -- killed on the CPU only, by tests/test_inflate_room_rules.py::test_room_mutants_are_killed:
-# each is built into a host model of its own and run in a child process over the items of tests/inflate_room_cases.py.
-# killer: (the host model's mode, the item that must fail), or ("equivalent", why): no item may fail in any mode.
-# THESE MUTANTS WRITE OUT OF THEIR ROOM BY DESIGN (up to 15 bytes; the test's 64-byte guards hold that inside its own
-# buffer).  They are never built into a GPU library: they are in no list that --build or a GPU run reads, and must not be.
-# Each runs in the ONE mode its entry names: the two literal mutants leave out_pos one past cap_min, and the wide turn's
-# `cap_min - out_pos` would then wrap (its child would write all over its heap) -- "plain" decodes symbol by symbol.
-ROOM_MUTANTS = [
-    ("lane_copy_gate_without_its_8", "inflate_lane.h", "(uint64_t)pos + len + 8 <= hard_cap", "(uint64_t)pos + len <= hard_cap",
-     ("plain", "lane/L9_d8_g0/R=79/limit R, cap R")),
-    ("span_flush_quad_over_the_tail", "inflate_span.h", "if (i + 16u <= tile_len) {", "if (i < tile_len) {", ("span_a", "span/skewed_k5_d17/R=10220/no limit, cap R")),
-    ("lane_literal_at_cap_min", "inflate_lane.h", "\n      if (d.out_pos >= d.cap_min) { d.overflow(",
-     "\n      if (d.out_pos > d.cap_min) { d.overflow(", ("plain", "literal_last/n20000/R=19999/no limit, cap R")),
-    ("lane_fixed_literal_at_cap_min", "inflate_lane.h", "\n    if (d.out_pos >= d.cap_min) { d.overflow(",
-     "\n    if (d.out_pos > d.cap_min) { d.overflow(", ("plain", "literal_last/n1/R=0/no limit, cap R")),
-    ("lane_match_to_cap_min_refused", "inflate_lane.h",
-     "if ((uint64_t)d.out_pos + length > d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return SYM_STOP; }",
-     "if ((uint64_t)d.out_pos + length >= d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return SYM_STOP; }",
-     ("plain", "lane/L3_d1_g0/R=73/limit R, cap R")),
-    ("lane_stored_to_cap_min_refused", "inflate_lane.h",
-     "if ((uint64_t)d.out_pos + length > d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return true; }",
-     "if ((uint64_t)d.out_pos + length >= d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return true; }",
-     ("plain", "stored/len16_behind0/R=16/limit R, cap R")),
-    ("cap_min_from_hard_cap_alone", "inflate_lane.h", "d.cap_min = d.limit < d.hard_cap ? d.limit : d.hard_cap;", "d.cap_min = d.hard_cap;",
-     ("plain", "lane/L9_d8_g5/R=83/limit R, cap R+40")),
-    ("span_far_pass_ungated", "inflate_span.h", "if (out_pos + 32u <= hard_cap && wv::any(has_far != 0u)) {", "if (wv::any(has_far != 0u)) {",
-     ("equivalent", "the gate keeps 16-byte LOADS of far sources inside the room; the pass stores into the tile (LDS) only, and what it "
-                    "does not fetch the rounds behind it copy: the host model, whose guards are readable, gives the same bytes")),
-]
-# (name, file, text, replacement, killer): one-line mutants of the TOKEN parts of the span decoder (inflate_span.h: what a byte of a
-# match is written down as a copy of), killed on the CPU only and never built for the GPU, in the manner of ROOM_MUTANTS: each is
-# built into a host model of its own and run in child processes by tests/test_token_rules.py::test_token_mutants_are_killed, which
-# holds every word of tok[] to tests/token_ref.py.  killer: the stream of tests/token_cases.py whose words it must break, or
-# ("equivalent", why): it must break none.  The test prints per mutant whether the BYTES alone would have caught it.
-TOKEN_MUTANTS = [
-    ("follow_from_off_by_one", "inflate_span.h", "const uint32_t from = dp + 32768u - dist;", "const uint32_t from = dp + 32767u - dist;",
-     "len_dist_grid"),
-    ("follow_in_tile_test_strict", "inflate_span.h", "if (sp >= 32768u && (mbits[(sp - 32768u) >> 5] >> (sp & 31u)) & 1u)",
-     "if (sp > 32768u && (mbits[(sp - 32768u) >> 5] >> (sp & 31u)) & 1u)",
-     ("equivalent", "(tile_edges has sources that begin at a tile's first byte) sp == 32768 is tile position 0: not following it inside the tile leaves the byte a copy of tile byte 0, a byte of "
-                    "the same chain one link further from the literal -- a longer way, never a wrong one")),
-    ("follow_sweep_test_strict", "inflate_span.h", "v[u] = sp >= 32768u ? out_pos", "v[u] = sp > 32768u ? out_pos",
-     ("equivalent", "sp == 32768 then reads tok[out_pos], the word of tile byte 0 itself: out_pos while nobody has written it, or what "
-                    "tile byte 0 is a copy of -- the same chain either way")),
-    ("follow_wrap_dropped", "inflate_span.h", "r = r + 1u == dist ? 0u : r + 1u;", "r = r + 1u;",
-     ("equivalent", "without the wrap byte i >= dist of an overlapping match is written down as a copy of byte i - dist of the match "
-                    "itself, which is src[i] to the letter: one link more per period, the same chain")),
-    ("plain_source_not_advanced", "inflate_span.h", "tok[at + i] = from + i;", "tok[at + i] = from;", "len_dist_grid"),
-    ("follow_step_reads_the_neighbour", "inflate_span.h", "srcpos[b] = srcpos[sp - 32768u];", "srcpos[b] = srcpos[sp - 32767u];",
-     "len_dist_grid"),
-    ("follow_store_inverted", "inflate_span.h", "if (v[u] != out_pos + b) tok[out_pos + b] = v[u];",
-     "if (v[u] == out_pos + b) tok[out_pos + b] = v[u];", "len_dist_grid"),
-]
 # what runs against each GPU mutant: the vectors under the default form, then under every override (one process each)
 TESTS = "tests/test_gpu_parity.py"
 SELECT = "second_readings_vectors"
