@@ -417,6 +417,52 @@ int zipc_hip_zlib_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
                              const zipc_hip_stream_desc *d_descs,
                              zipc_hip_stream_result *d_results, size_t n_streams);
 
+/* A prefix: the first dst_cap bytes of every stream of a batch -- for a caller who wants the beginning of each stream (a
+ * magic number, a header line, a first record) and neither the time nor the room of the whole.  Every other decode form
+ * is all or nothing: a stream that does not fit its room is ZIPC_HIP_ERR_DST_TOO_SMALL with nothing to show. */
+typedef struct {            /* 16 bytes, the layout of zipc_hip_stream_result */
+  uint32_t status;   /* ZIPC_HIP_OK or the stream's own error */
+  uint32_t ended;    /* 1: the stream's final block ended within the room; 0: cut at dst_cap, or an error */
+  uint64_t out_len;  /* bytes at dst_off; 0 unless OK */
+} zipc_hip_prefix_result;
+/* All pointers are DEVICE pointers.  The descriptors are zipc_hip_inflate_batch's, every field with the meaning it has
+ * there, limit and ZIPC_HIP_STREAM_HAS_LIMIT included.
+ * The defining property, the one rule: for every stream let (s, n) be the status and out_len that zipc_hip_inflate_batch
+ * (ZIPC_HIP_CRC_NOP) reports for the same descriptor.
+ *   s == ZIPC_HIP_OK: the result is {ZIPC_HIP_OK, ended 1, n} and the room holds the same bytes.
+ *   s == ZIPC_HIP_ERR_DST_TOO_SMALL: the result is {ZIPC_HIP_OK, ended 0, out_len = dst_cap} and the room holds the first
+ *     dst_cap bytes of the serial decode: the whole symbols before the one that did not fit and, of a match or a stored
+ *     block that straddles the end, the bytes that fit.  Nothing behind the cut is read or judged: an error of the stream
+ *     that lies behind the symbol that was cut is not reported.
+ *   any other s: that status, ended 0, out_len 0 -- ZIPC_HIP_ERR_CORRUPTED, ZIPC_HIP_ERR_SIZE_EXCEEDED (also where a limit
+ *     lies inside the straddling symbol, exactly as the table at zipc_hip_inflate_batch says) and the
+ *     ZIPC_HIP_ERR_INVALID_ARG of a flag bit or of a length above ZIPC_HIP_MAX_STREAM_LEN.
+ * What follows from it:
+ *   - symbols with no output still count: an end of block, a block header, an empty stored block behind a full room are
+ *     still read, and their errors reported;
+ *   - the exact fit: a stream whose output is exactly dst_cap is ended 1 iff its final block ends before a symbol needs room;
+ *   - dst_cap == 0 is legal: {ZIPC_HIP_OK, 0, 0} for a stream that has output;
+ *   - nothing is written in front of dst_off or behind dst_off + dst_cap, whatever the status.
+ * Always a wave per stream, whatever dst_cap: this form has no by-blocks path and reads nothing back
+ * (zipc_hip_last_inflate_blocks is 0 behind it).  One launch, enqueued on the context's stream and never synchronised;
+ * growing the context's scratch may synchronise, as everywhere.  A wave that is cut has read only the source it needed.
+ * No checksum is offered: zipc_hip_checksum_batch over the prefixes is the way to one.
+ * Null ctx, d_descs or d_results, or n_streams above 0x7FFFFFFF, fails the call with ZIPC_HIP_ERR_INVALID_ARG;
+ * n_streams == 0 is ZIPC_HIP_OK and nothing is enqueued.  INTEGRATION.md has the recipe "peek, then decide". */
+int zipc_hip_inflate_prefix_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                  const zipc_hip_stream_desc *d_descs, zipc_hip_prefix_result *d_results,
+                                  size_t n_streams);
+/* The same for WHOLE zlib streams (stream i of the source arena as in zipc_hip_zlib_decompress_batch): the container's
+ * checks before (csrc/zlib.hip, unchanged) -- a stream that fails them reports that status, ended 0, out_len 0, and
+ * nothing of it is written -- the prefix kernel over the bodies with the context's Adler-32 flavour, and a close, a lane
+ * per stream: a stream that ENDED within its room has its Adler-32 compared as zipc_hip_zlib_decompress_batch compares
+ * it, and on a mismatch reports ZIPC_HIP_ERR_CHECKSUM, ended 0, out_len 0 (the value found is not reported: there is no
+ * field for it); a stream that was cut is {ZIPC_HIP_OK, 0, dst_cap} with nothing compared -- its trailer has not been
+ * reached; every other status is the body's.  Enqueued and never synchronised; the same argument rules. */
+int zipc_hip_zlib_decompress_prefix_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                          const zipc_hip_stream_desc *d_descs, zipc_hip_prefix_result *d_results,
+                                          size_t n_streams);
+
 /* Sizing with the long streams of the call BY BLOCKS: descriptors, results, argument rules and the defining property of
  * zipc_hip_inflate_size_batch / zipc_hip_zlib_size_batch, word for word -- status and out_len are what
  * zipc_hip_inflate_batch (ZIPC_HIP_CRC_NOP) reports with dst_cap = ZIPC_HIP_MAX_STREAM_LEN, checksum is 0, no arena is

@@ -121,6 +121,8 @@ SYMBOLS = [
     ("zipc_hip_zlib_compress_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int]),
     ("zipc_hip_inflate_size_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_zlib_size_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
+    ("zipc_hip_inflate_prefix_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ]),
+    ("zipc_hip_zlib_decompress_prefix_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ]),
     ("zipc_hip_inflate_size_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_zlib_size_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_inflate_packed_batch", C.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _SZ, C.c_int, _P]),

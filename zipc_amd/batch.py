@@ -18,6 +18,9 @@ DESC_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("dst_off", "<u8"
                        ("reserved", "<u4")])
 RESULT_DTYPE = np.dtype([("status", "<u4"), ("checksum", "<u4"), ("out_len", "<u8")])
 assert DESC_DTYPE.itemsize == 48 and RESULT_DTYPE.itemsize == 16
+# zipc_hip_prefix_result: ended 1 -- the stream's final block ended within its room; 0 -- cut at dst_cap, or an error
+PREFIX_RESULT_DTYPE = np.dtype([("status", "<u4"), ("ended", "<u4"), ("out_len", "<u8")])
+assert PREFIX_RESULT_DTYPE.itemsize == 16
 # zipc_hip_recode_desc / zipc_hip_recode_result
 RECODE_DESC_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("mid_off", "<u8"), ("mid_cap", "<u8"),
                               ("dst_off", "<u8"), ("dst_cap", "<u8"), ("limit", "<u8"), ("flags", "<u4"),
@@ -141,6 +144,36 @@ def zlib_size_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int, s
     if sync:
         _sync_torch(src)
     st = lib().zipc_hip_zlib_size_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def prefix_results_from_device(t) -> np.ndarray:
+    return t.cpu().numpy().view(PREFIX_RESULT_DTYPE).copy()
+
+
+def inflate_prefix_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, sync: bool = True):
+    """zipc_hip_inflate_prefix_batch: the first dst_cap bytes of every raw deflate stream of `src` -- a stream that
+    inflate_batch reports OK is (OK, ended 1, its length), one it reports DST_TOO_SMALL is (OK, ended 0, dst_cap) with the
+    first dst_cap bytes of its output in its room, every other status is the stream's own.  results_dev: a uint8 cuda
+    tensor of PREFIX_RESULT_DTYPE records.  Always a wave per stream; nothing is read back."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_inflate_prefix_batch(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(),
+                                             results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def zlib_decompress_prefix_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, sync: bool = True):
+    """zipc_hip_zlib_decompress_prefix_batch: the same for whole zlib streams -- the header's verdict first; a stream that
+    ended within its room has its Adler-32 compared (CHECKSUM on a mismatch), one that was cut has not."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_zlib_decompress_prefix_batch(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(),
+                                                     results_dev.data_ptr(), n_streams)
     ctx.check(st)
     if sync:
         ctx.synchronize()
@@ -451,5 +484,6 @@ __all__ = ["DESC_DTYPE", "RESULT_DTYPE", "RECODE_DESC_DTYPE", "RECODE_RESULT_DTY
            "PACKED_RESULT_DTYPE", "inflate_packed_batch", "zlib_decompress_packed_batch", "packed_results_from_device",
            "deflate_packed_batch", "zlib_compress_packed_batch", "deflate_packed_bound",
            "RANGE_DTYPE", "CHECKSUM_RESULT_DTYPE", "make_ranges", "checksum_results_from_device", "checksum_batch", "checksum_many",
+           "PREFIX_RESULT_DTYPE", "inflate_prefix_batch", "zlib_decompress_prefix_batch", "prefix_results_from_device",
            "deflate_bound", "zlib_bound",
            "uniform_layout", "compact_descs", "OK"]

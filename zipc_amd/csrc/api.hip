@@ -319,7 +319,7 @@ void zipc_hip_destroy(zipc_hip_ctx *ctx) {
   free_buf(ctx->tok_scratch);
   free_buf(ctx->descs_marked);
   free_buf(ctx->size_descs); free_buf(ctx->size_head); free_buf(ctx->size_rest);
-  free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre);
+  free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre); free_buf(ctx->prefix_adlers);
   free_buf(ctx->recode_descs); free_buf(ctx->recode_res); free_buf(ctx->recode_verdicts);
   free_buf(ctx->packed_descs); free_buf(ctx->packed_res); free_buf(ctx->packed_verdicts);
   free_buf(ctx->dpacked_staging); free_buf(ctx->dpacked_descs); free_buf(ctx->dpacked_res);
@@ -427,6 +427,12 @@ int zipc_hip_inflate_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena, cons
                                 zipc_hip_stream_result *d_results, size_t n_streams) {
   if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
   return launch_inflate_size(ctx, d_src_arena, d_descs, d_results, n_streams);
+}
+
+int zipc_hip_inflate_prefix_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                  zipc_hip_prefix_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  return launch_inflate_prefix(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, ZIPC_HIP_CRC_NOP, nullptr);
 }
 
 int zipc_hip_inflate_size_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
@@ -785,6 +791,22 @@ int zipc_hip_zlib_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const z
   st = zipc_hip_inflate_size_batch(ctx, d_src_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, d_results, n_streams);
   if (st) return st;
   return launch_zlib_close_size(ctx, d_results, n_streams);
+}
+
+// The first dst_cap bytes of every zlib stream: open as ever, the prefix kernel over the bodies with the context's Adler-32,
+// and zlib_container.h's zlib_close_prefix -- an ended stream's Adler-32 is compared, a cut one's is not
+int zipc_hip_zlib_decompress_prefix_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                          const zipc_hip_stream_desc *d_descs, zipc_hip_prefix_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  ctx->last_inflate_blocks = 0;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = launch_zlib_open(ctx, d_src_arena, d_descs, n_streams, 0);
+  if (st) return st;
+  HIP_TRY(ctx, ctx->ensure(ctx->prefix_adlers, n_streams * sizeof(uint32_t)));
+  st = launch_inflate_prefix(ctx, d_src_arena, d_dst_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, d_results, n_streams,
+                             zlib_crc_op(ctx), (uint32_t *)ctx->prefix_adlers.p);
+  if (st) return st;
+  return launch_zlib_close_prefix(ctx, d_results, n_streams);
 }
 
 // ... with the long bodies sized by blocks: the same open and close around launch_inflate_size_blocks over the body descriptors

@@ -57,6 +57,7 @@ struct zipc_hip_ctx {
   Buf descs_marked;                               // ... a call's descriptors with those streams marked as done, for the one waves of the rest
   Buf size_descs, size_head, size_rest;                      // sizing by blocks: the call's descriptors with no destination (dst_off 0, dst_cap the longest stream's), the heads' results and span slots, the one-wave results of the streams left
   Buf zlib_descs, zlib_pre;                       // the zlib batch forms: the descriptors the codec runs with, the container checks' verdicts (zlib.hip)
+  Buf prefix_adlers;                              // the zlib prefix form: the Adler-32 of every stream that ended within its room (inflate.hip inflate_prefix_kernel)
   Buf recode_descs, recode_res, recode_verdicts;  // the recode forms: the descriptors inflate, then deflate run with, their results, what is known of a stream between the steps (recode.hip)
   Buf packed_descs, packed_res, packed_verdicts;  // the packed decode forms: the descriptors inflate runs with, the sizing pass's results and then inflate's, the layout's verdicts (packed.hip)
   Buf dpacked_staging, dpacked_descs, dpacked_res;  // the packed encode forms: the staging arena of the slots, the descriptors deflate runs with, its results (deflate_packed.hip)
@@ -162,6 +163,11 @@ int launch_inflate(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena
 // stream, one launch on ctx->cur
 int launch_inflate_size(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
                         size_t n_streams);
+// inflate.hip: zipc_hip_inflate_prefix_batch behind its argument checks (a ZIPC_HIP_* status): inflate_prefix_kernel, a wave
+// per stream whatever its room, one launch on ctx->cur; crc_op: ZIPC_HIP_CRC_NOP, or zlib_crc_op's with d_adlers a word per
+// stream for the Adler-32 of those that ended (the zlib form)
+int launch_inflate_prefix(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                          zipc_hip_prefix_result *d_results, size_t n_streams, int crc_op, uint32_t *d_adlers);
 // inflate.hip: zipc_hip_inflate_size_blocks_batch behind its argument checks: the call's long streams (forms.h size_blocks_pick)
 // by the block path's first half and a head walk, the rest by inflate_size_kernel's wave; h_descs: the caller's host copy of
 // the descriptors, or null: they are read back.  Synchronises ctx->stream unless no stream of the call is long.
@@ -198,6 +204,7 @@ int launch_zlib_open(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_
 int launch_zlib_close(zipc_hip_ctx *ctx, void *d_dst_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
                       size_t n, int compress, int level);
 int launch_zlib_close_size(zipc_hip_ctx *ctx, zipc_hip_stream_result *d_results, size_t n);
+int launch_zlib_close_prefix(zipc_hip_ctx *ctx, zipc_hip_prefix_result *d_results, size_t n);  // (the Adler-32s: ctx->prefix_adlers)
 // many.hip: the staging threads' pools, shared by the process's contexts (zipc_hip_create / zipc_hip_destroy)
 void many_pools_acquire();
 void many_pools_release();

@@ -642,11 +642,19 @@ __device__ __forceinline__ Explore no_explore() {
 // HEAD (with IM_SIZE): the stream's first blocks only (inflate_size_head_kernel) -- the wave stops at the first end of a
 // block at which the output has reached BLOCK_DRY_BASE bytes, or behind the final block, and returns what it found
 // (status, whether the last block it read was final, end bit, output position, in pad the blocks it walked); no result is stored.
-template <int MODE, bool MULTI = false, bool REUSE = false, bool HEAD = false>
+// PREFIX (with IM_REAL): the prefix forms' wave (inflate_prefix_kernel) -- the plain step cuts the symbol that does not fit
+// where it would report ST_DST_TOO_SMALL (inflate_prefix.h, InflateLane::prefix_cut): the status is ST_PREFIX_CUT from then
+// on and the phase a request for the part that fits (or PH_DONE: none of it does).  Such a request is never served in
+// line, where the decode would go on behind it: the loop's services fill the queued copies first, copy it, and the wave
+// is done.  The result is a PrefixResult (inflate_prefix.h prefix_result); adler_out: where the Adler-32 of an ended
+// stream goes for the zlib form, or null.
+template <int MODE, bool MULTI = false, bool REUSE = false, bool HEAD = false, bool PREFIX = false>
 __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t *__restrict__ src_arena, uint8_t *__restrict__ dst_arena,
                                                  const StreamDesc &sd, const BlockStart at, StreamResult *__restrict__ result,
                                                  uint16_t *__restrict__ span_idx, uint32_t *__restrict__ tok, int crc_op,
-                                                 const Explore X = no_explore(), uint16_t *srcpos = nullptr) {
+                                                 const Explore X = no_explore(), uint16_t *srcpos = nullptr,
+                                                 uint32_t *__restrict__ adler_out = nullptr) {
+  static_assert(!PREFIX || (MODE == IM_REAL && !MULTI && !REUSE && !HEAD), "the prefix form is the stream's plain wave");
   const int lane = threadIdx.x;
   const bool crc_adler = MODE == IM_REAL && (crc_op == CRC_ADLER32 || crc_op == CRC_ADLER32_RFC);
   const bool adler_rfc = crc_op == CRC_ADLER32_RFC;
@@ -789,7 +797,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
         }
         lit_stride = 0;  // (a block whose tables are not built -- a fixed block's table-free start -- has no stride of the block before's)
         bool ok = true;
-        if (lane == 0) ok = lane_header_step(d, L, src_arena);
+        if (lane == 0) ok = lane_header_step(d, L, src_arena, PREFIX);
         uniformize(d);  // lane 0 is the first active lane: everybody takes its state
         if (!uni((uint32_t)ok)) break;  // waits for input
         ZD_PH(ph_hdr);
@@ -839,13 +847,13 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
       } else if (d.phase == PH_SYMBOLS && d.fixed_lazy) {  // a fixed block's first symbols, straight from the code
         turn++;
         ZD_PH_START();
-        const int r = lane_one_symbol_fixed(d, L, A, writer, MODE == IM_REAL);
+        const int r = lane_one_symbol_fixed(d, L, A, writer, MODE == IM_REAL, PREFIX);
         uniformize(d);
         const int ru = uni(r);
         ZD_PH(ph_plain);
         if (ru == SYM_EOB) { d.fixed_lazy = 0; lane_end_of_block(d, crc_adler); block_done(); }
         else if (ru == SYM_STOP) {
-          if (d.phase == PH_REQ_MATCH && d.q_count == 0) {
+          if (d.phase == PH_REQ_MATCH && d.q_count == 0 && !(PREFIX && d.status != ST_OK)) {
             wave_match<MODE>(dst, tok, d.out_pos, d.req_dist, d.req_len, lane, L.x + LDS_SPAN_TILE_BYTE);
             lane_after_match(d);
           } else break;
@@ -899,7 +907,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
         ZD_PH(ph_wide);
         if (stopped) {
           const uint32_t pos_before = d.in_word * 32u + d.boff;
-          const int r = lane_one_symbol(d, L, A, writer, MODE == IM_REAL);
+          const int r = lane_one_symbol(d, L, A, writer, MODE == IM_REAL, PREFIX);
           uniformize(d);
           const int ru = uni(r);
           ZD_PH(ph_plain);
@@ -907,7 +915,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
           else if (ru == SYM_STOP) {
             // a match that cannot be queued (long, or overlapping its own output) and nothing queued
             // before it: the wave copies it here and now instead of going round through the services
-            if (d.phase == PH_REQ_MATCH && d.q_count == 0) {
+            if (d.phase == PH_REQ_MATCH && d.q_count == 0 && !(PREFIX && d.status != ST_OK)) {
               d.req_len = match_run(d, L, lane, d.in_word * 32u + d.boff - pos_before);
               wave_match<MODE>(dst, tok, d.out_pos, d.req_dist, d.req_len, lane, L.x + LDS_SPAN_TILE_BYTE);
               lane_after_match(d);
@@ -938,6 +946,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
       lane_after_copy(d, crc_adler);
       block_done();
     }
+    if (PREFIX && d.status == ST_PREFIX_CUT) d.phase = PH_DONE;  // the part of the cut symbol that fits is copied: nothing behind it is read
     if (MODE != IM_SIZE && d.phase == PH_REQ_ADLER) {
       // the block's bytes were stored by other lanes of this wave: make them visible
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -959,6 +968,14 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
   e.out_len = d.out_pos - (MODE == IM_DRY ? BLOCK_DRY_BASE : at.out_pos);
   e.pad = MODE == IM_DRY ? ck.n : left_early ? 1u : 0u;
   if constexpr (HEAD) { e.pad = n_listed; return e; }
+  if constexpr (PREFIX) {
+    if (writer) {
+      const PrefixResult r = prefix_result(d.status, d.out_pos, d.cap_min);
+      *(PrefixResult *)result = r;
+      if (adler_out != nullptr) *adler_out = crc_adler && r.ended ? d.adler : 0u;
+    }
+    return e;
+  }
   if (MODE != IM_REAL && MODE != IM_SIZE) return e;
   if (writer || (MODE == IM_SIZE && lane == 0)) {
     StreamResult r;
@@ -1044,6 +1061,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   at.bit = 0; at.out_pos = 0; at.chunk0 = 0;
   inflate_wave<IM_SIZE>(lds_raw, src_arena, nullptr, descs[stream], at, results + stream,
                         span_scratch + (size_t)stream * SPAN_IDX_ENTRIES, nullptr, CRC_NOP);
+}
+// The prefix forms: the stream's wave with the symbol that does not fit its room cut instead of refused (PREFIX, inflate_wave)
+// -- results[stream] = inflate_prefix.h's record of what inflate_batch_kernel would report for the same descriptor: ended
+// with its bytes, cut at dst_cap with the first dst_cap bytes, or the stream's error.  One kernel for every call size.
+// adlers: null, or a word per stream for the Adler-32 of an ended stream (the zlib form's close compares it).
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void inflate_prefix_kernel(const uint8_t *__restrict__ src_arena,
+                                                           uint8_t *__restrict__ dst_arena,
+                                                           const StreamDesc *__restrict__ descs,
+                                                           PrefixResult *__restrict__ results,
+                                                           uint32_t n_streams, uint16_t *__restrict__ span_scratch, int crc_op,
+                                                           uint32_t *__restrict__ adlers) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LDS_BYTES_PER_LANE];
+  const uint32_t stream = blockIdx.x;
+  if (stream >= n_streams) return;
+  static_assert(sizeof(PrefixResult) == sizeof(StreamResult), "an invalid flag's record is written as a StreamResult: status, 0, 0");
+  if (inflate_skips_stream(descs[stream].flags, crc_op, (StreamResult *)(results + stream))) {
+    if (adlers != nullptr && threadIdx.x == 0) adlers[stream] = 0u;
+    return;
+  }
+  BlockStart at;
+  at.bit = 0; at.out_pos = 0; at.chunk0 = 0;
+  inflate_wave<IM_REAL, false, false, false, true>(lds_raw, src_arena, dst_arena, descs[stream], at, (StreamResult *)(results + stream),
+                                                   span_scratch + (size_t)stream * SPAN_IDX_ENTRIES, nullptr, crc_op, no_explore(), nullptr,
+                                                   adlers != nullptr ? adlers + stream : nullptr);
 }
 
 
@@ -2222,6 +2263,21 @@ int launch_inflate_size(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_h
   HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_streams * INFLATE_SCRATCH_PER_STREAM));
   ZD_LAUNCH(ctx, "inflate_size", inflate_size_kernel, dim3((unsigned)n_streams), dim3(64), 0, (const uint8_t *)d_src_arena,
             (const StreamDesc *)d_descs, (StreamResult *)d_results, (uint32_t)n_streams, (uint16_t *)ctx->inflate_scratch.p);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+
+// zipc_hip_inflate_prefix_batch behind its argument checks, and the zlib form's middle step (ctx.h): one launch, a wave per
+// stream whatever its room, on the context's stream -- no by-blocks path, nothing read back
+int launch_inflate_prefix(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                          zipc_hip_prefix_result *d_results, size_t n_streams, int crc_op, uint32_t *d_adlers) {
+  ctx->last_inflate_blocks = 0;  // (zipc_hip_last_inflate_blocks: no stream of this call goes by blocks)
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_streams * INFLATE_SCRATCH_PER_STREAM));
+  ZD_LAUNCH(ctx, "inflate_prefix", inflate_prefix_kernel, dim3((unsigned)n_streams), dim3(64), 0, (const uint8_t *)d_src_arena,
+            (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs, (PrefixResult *)d_results, (uint32_t)n_streams,
+            (uint16_t *)ctx->inflate_scratch.p, crc_op, d_adlers);
   HIP_TRY(ctx, hipGetLastError());
   return ZIPC_HIP_OK;
 }

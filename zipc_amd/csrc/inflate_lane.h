@@ -38,6 +38,7 @@
 //   Huffman.init_decoder           src/zipc_deflate.ml:355-391
 #pragma once
 
+#include "inflate_prefix.h"
 #include "zd_common.h"
 
 namespace zd {
@@ -220,6 +221,15 @@ struct InflateLane {
   // decompression size exceeded" (zd.ml:27-29); running out of the caller's
   // dst_cap with no limit given is the boundary's DST_TOO_SMALL.
   ZD_HD void overflow(uint64_t need) { fail(need > limit ? ST_SIZE_EXCEEDED : ST_DST_TOO_SMALL); }
+  // The prefix forms (inflate_prefix.h; `prefix`: the wave is one of theirs) ask first, at the same four places: where
+  // overflow() would say ST_DST_TOO_SMALL the symbol is cut instead -- true, with req_len the bytes of it that fit and the
+  // position still in front of it; the caller, who knows the symbol, says where they come from and what copies them.
+  ZD_HD bool prefix_cut(bool prefix, uint64_t need) {
+    if (!prefix || !prefix_cuts(need, limit)) return false;
+    status = ST_PREFIX_CUT;
+    req_len = prefix_cut_len(out_pos, cap_min);
+    return true;
+  }
 };
 
 // A symbol being decoded out of a 64-bit peek: `used` of `avail` real bits.
@@ -525,7 +535,7 @@ constexpr int FIXED_LAZY_SYMBOLS = 48;  // symbols of a fixed block decoded with
 // One block header (inflate_loop zd.ml:694-701) up to the point where symbols
 // can be decoded, or a stored block can be copied.  Returns false when the lane
 // must wait for input (nothing consumed).
-ZD_HD bool lane_block_header(InflateLane &d, const LaneLds &L, const uint8_t *__restrict__ sa) {
+ZD_HD bool lane_block_header(InflateLane &d, const LaneLds &L, const uint8_t *__restrict__ sa, bool prefix = false) {
   if (!d.input_ready(HEADER_WORDS)) return false;  // 3 + 14 + 57 header bits at most
   uint32_t v;
   const uint8_t *src = sa + d.src_off;
@@ -544,6 +554,11 @@ ZD_HD bool lane_block_header(InflateLane &d, const LaneLds &L, const uint8_t *__
     if (length != ((~inv) & 0xFFFFu)) { d.fail(ST_CORRUPTED); return true; }
     pos += 4;
     if (d.src_len - pos < length) { d.fail(ST_CORRUPTED); return true; }
+    if ((uint64_t)d.out_pos + length > d.cap_min && d.prefix_cut(prefix, (uint64_t)d.out_pos + length)) {  // the block's first req_len bytes
+      d.req_src = prefix_stored_from(pos);
+      d.phase = d.req_len ? PH_REQ_COPY : PH_DONE;
+      return true;
+    }
     if ((uint64_t)d.out_pos + length > d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return true; }
     d.req_src = pos;
     d.req_len = length;
@@ -588,8 +603,14 @@ ZD_HD constexpr bool im_stores(int mode) { return mode == IM_REAL || mode == IM_
 // A decoded match (its bits in c): the reference's checks, then Buf.recopy zd.ml:615 -- queued, or
 // handed to the wave
 ZD_HD int lane_match_commit(InflateLane &d, const LaneLds &L, bool writer, const BitCursor &c, uint32_t length, uint32_t dist,
-                            bool may_queue = true) {
+                            bool may_queue = true, bool prefix = false) {
   if (dist > d.out_pos) { d.fail(ST_CORRUPTED); return SYM_STOP; }  // zd.ml:614
+  if ((uint64_t)d.out_pos + length > d.cap_min && d.prefix_cut(prefix, (uint64_t)d.out_pos + length)) {  // the match's first req_len bytes
+    d.req_src = prefix_match_from(d.out_pos, dist);
+    d.req_dist = d.out_pos - d.req_src;
+    d.phase = d.req_len ? PH_REQ_MATCH : PH_DONE;
+    return SYM_STOP;
+  }
   if ((uint64_t)d.out_pos + length > d.cap_min) { d.overflow((uint64_t)d.out_pos + length); return SYM_STOP; }
   d.advance((uint32_t)c.used);
   // Buf.recopy zd.ml:615 -- queued, or handed to the wave
@@ -612,7 +633,7 @@ ZD_HD int lane_match_commit(InflateLane &d, const LaneLds &L, bool writer, const
 
 // Exactly one symbol of read_block_symbols (zd.ml:593-616), decoded the plain
 // way.  SYM_STOP: failed, parked on a request, or waiting for input.
-ZD_HD int lane_one_symbol(InflateLane &d, const LaneLds &L, const Arenas &A, bool writer, bool may_queue = true) {
+ZD_HD int lane_one_symbol(InflateLane &d, const LaneLds &L, const Arenas &A, bool writer, bool may_queue = true, bool prefix = false) {
   uint8_t *dst = A.dst + d.dst_off;
   if (!d.input_ready(3)) return SYM_STOP;
   BitCursor c = cursor_at(d, L);
@@ -633,6 +654,7 @@ ZD_HD int lane_one_symbol(InflateLane &d, const LaneLds &L, const Arenas &A, boo
     int sym = read_symbol_walk(c, L, LDS_LIT_COUNTS, LDS_LIT_SYMS);
     if (sym < 0) { d.fail(ST_CORRUPTED); return SYM_STOP; }
     if (sym < LITLEN_EOB) {
+      if (d.out_pos >= d.cap_min && d.prefix_cut(prefix, (uint64_t)d.out_pos + 1)) { d.phase = PH_DONE; return SYM_STOP; }  // nothing of a literal fits
       if (d.out_pos >= d.cap_min) { d.overflow((uint64_t)d.out_pos + 1); return SYM_STOP; }
       if (writer) dst[d.out_pos] = (uint8_t)sym;
       d.out_pos++;
@@ -652,7 +674,7 @@ ZD_HD int lane_one_symbol(InflateLane &d, const LaneLds &L, const Arenas &A, boo
     if (vextra != 0 && !c.take((int)vextra, v)) { d.fail(ST_CORRUPTED); return SYM_STOP; }
     dist = vbase + v;
   }
-  return lane_match_commit(d, L, writer, c, length, dist, may_queue);
+  return lane_match_commit(d, L, writer, c, length, dist, may_queue, prefix);
 }
 
 // read_symbol on the FIXED codes (fixed_litlen_decoder / fixed_dist_decoder zd.ml:334-349) without
@@ -674,13 +696,14 @@ ZD_HD int fixed_litlen_symbol(BitCursor &c) {
   return (int)(144u + bitrev(x & 511u, 9) - 0x190u);
 }
 // lane_one_symbol for a fixed block whose tables are not built
-ZD_HD int lane_one_symbol_fixed(InflateLane &d, const LaneLds &L, const Arenas &A, bool writer, bool may_queue = true) {
+ZD_HD int lane_one_symbol_fixed(InflateLane &d, const LaneLds &L, const Arenas &A, bool writer, bool may_queue = true, bool prefix = false) {
   uint8_t *dst = A.dst + d.dst_off;
   if (!d.input_ready(3)) return SYM_STOP;
   BitCursor c = cursor_at(d, L);
   const int sym = fixed_litlen_symbol(c);
   if (sym < 0) { d.fail(ST_CORRUPTED); return SYM_STOP; }
   if (sym < LITLEN_EOB) {
+    if (d.out_pos >= d.cap_min && d.prefix_cut(prefix, (uint64_t)d.out_pos + 1)) { d.phase = PH_DONE; return SYM_STOP; }  // nothing of a literal fits
     if (d.out_pos >= d.cap_min) { d.overflow((uint64_t)d.out_pos + 1); return SYM_STOP; }
     if (writer) dst[d.out_pos] = (uint8_t)sym;
     d.out_pos++;
@@ -700,12 +723,12 @@ ZD_HD int lane_one_symbol_fixed(InflateLane &d, const LaneLds &L, const Arenas &
   dist_sym_value(dsym, vbase, vextra);
   v = 0;
   if (vextra != 0 && !c.take((int)vextra, v)) { d.fail(ST_CORRUPTED); return SYM_STOP; }
-  return lane_match_commit(d, L, writer, c, length, vbase + v, may_queue);
+  return lane_match_commit(d, L, writer, c, length, vbase + v, may_queue, prefix);
 }
 
 // One header action: false = must wait for input.
-ZD_HD bool lane_header_step(InflateLane &d, const LaneLds &L, const uint8_t *__restrict__ sa) {
-  if (d.phase == PH_HEADER) return lane_block_header(d, L, sa);
+ZD_HD bool lane_header_step(InflateLane &d, const LaneLds &L, const uint8_t *__restrict__ sa, bool prefix = false) {
+  if (d.phase == PH_HEADER) return lane_block_header(d, L, sa, prefix);
   if (d.phase == PH_HDR_CODELEN) {  // (the host model's way; its bits were made ready with the header's: HEADER_WORDS)
     if (!setup_codelen_code(d, L)) d.fail(ST_CORRUPTED);
     else d.phase = PH_HDR_LENGTHS;

@@ -7,6 +7,8 @@
 //   zlib_close_kernel  puts that verdict and the codec's result together: the Adler-32 compared with the stream's own,
 //                      or the header and the trailer stored around what deflate wrote.
 //   zlib_close_size_kernel  the same behind inflate's size kernel (zipc_hip_zlib_size_batch): the verdict, or the body's size.
+//   zlib_close_prefix_kernel  the same behind inflate's prefix kernel (zipc_hip_zlib_decompress_prefix_batch): an ended stream's
+//                      Adler-32 compared, a cut one's not.
 // The rules themselves are zlib_container.h's (the host forms and the tests compile the same functions).  Nothing is
 // read back: the calls enqueue and return like the raw batch forms.  The launches at the end of this file are the one
 // way to the kernels (ctx.h).
@@ -93,6 +95,14 @@ __global__ __launch_bounds__(256) void zlib_close_size_kernel(const ZlibPre *__r
   results[i] = zlib_close_size(pre[i].status, results[i]);
 }
 
+// zipc_hip_zlib_decompress_prefix_batch's close: the container check's verdict over the prefix kernel's (zlib_close_prefix)
+__global__ __launch_bounds__(256) void zlib_close_prefix_kernel(const ZlibPre *__restrict__ pre, const uint32_t *__restrict__ adlers,
+                                                                PrefixResult *__restrict__ results, uint32_t n_streams) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_streams) return;
+  results[i] = zlib_close_prefix(pre[i].status, pre[i].expect, adlers[i], results[i]);
+}
+
 int zlib_crc_op(const zipc_hip_ctx *ctx) { return ctx->adler_rfc1950 ? ZIPC_HIP_CRC_ADLER32_RFC1950 : ZIPC_HIP_CRC_ADLER32; }
 
 // zlib_open_kernel over the caller's descriptors: the codec's descriptors and the checks' verdicts, in the context's scratch
@@ -115,6 +125,13 @@ int launch_zlib_close(zipc_hip_ctx *ctx, void *d_dst_arena, const zipc_hip_strea
 int launch_zlib_close_size(zipc_hip_ctx *ctx, zipc_hip_stream_result *d_results, size_t n) {
   ZD_LAUNCH(ctx, "zlib_close_size", zlib_close_size_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
             (const ZlibPre *)ctx->zlib_pre.p, (StreamResult *)d_results, (uint32_t)n);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+
+int launch_zlib_close_prefix(zipc_hip_ctx *ctx, zipc_hip_prefix_result *d_results, size_t n) {
+  ZD_LAUNCH(ctx, "zlib_close_prefix", zlib_close_prefix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+            (const ZlibPre *)ctx->zlib_pre.p, (const uint32_t *)ctx->prefix_adlers.p, (PrefixResult *)d_results, (uint32_t)n);
   HIP_TRY(ctx, hipGetLastError());
   return ZIPC_HIP_OK;
 }

@@ -8,6 +8,7 @@
 //   * into tests/zlib_sim/sim_zlib.cpp with g++, where tests/test_zlib_rules.py holds every (CMF, FLG) pair to the oracle.
 #pragma once
 
+#include "inflate_prefix.h"
 #include "zd_common.h"
 
 namespace zd {
@@ -76,6 +77,15 @@ ZD_HD StreamResult zlib_close_decompress(uint32_t pre, uint32_t expect, StreamRe
 ZD_HD StreamResult zlib_close_size(uint32_t pre, StreamResult inner) {
   if (pre != ST_OK) { inner.status = pre; inner.out_len = 0; }
   inner.checksum = 0;
+  return inner;
+}
+// The prefix of a zlib stream (zipc_hip_zlib_decompress_prefix_batch): `inner` is the prefix kernel's record of the body,
+// `adler` the Adler-32 of its bytes where it ended.  A stream that failed its own check says so; one that ENDED within its
+// room is compared as zlib_close_decompress compares it (the value found is not reported: the record has no field for
+// it); one that was cut has not been read to its end and nothing of it is compared; everything else is inflate's.
+ZD_HD PrefixResult zlib_close_prefix(uint32_t pre, uint32_t expect, uint32_t adler, PrefixResult inner) {
+  if (pre != ST_OK) { inner.status = pre; inner.ended = 0; inner.out_len = 0; }
+  else if (inner.status == ST_OK && inner.ended != 0 && adler != expect) { inner.status = ST_CHECKSUM; inner.ended = 0; inner.out_len = 0; }
   return inner;
 }
 // zlib_compress: `inner` is deflate's, the result counts the container's bytes too.  *wrap: the caller has to put the
