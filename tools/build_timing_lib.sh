@@ -16,6 +16,6 @@ case $MACRO in ZD_INFLATE_PHASES) SRC=inflate;; *) SRC=deflate;; esac
 make -s -C "$C" -j4 all
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 $HIPCC -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -D$MACRO -c "$C/$SRC.hip" -o "$C/build/${SRC}_$MACRO.o"
-OBJS=""; for o in api inflate checksum deflate; do if [ $o = $SRC ]; then OBJS="$OBJS $C/build/${SRC}_$MACRO.o"; else OBJS="$OBJS $C/build/$o.o"; fi; done
+OBJS=""; for o in $(sed -n 's/^SRCS *:= *//p' "$C/Makefile" | sed 's/\.hip//g'); do if [ $o = $SRC ]; then OBJS="$OBJS $C/build/${SRC}_$MACRO.o"; else OBJS="$OBJS $C/build/$o.o"; fi; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" $OBJS
 echo "$OUT"

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Phase times inside deflate_emit_kernel, from a timing-only build of the library
-(-DZD_EMIT_PHASES: the per-stream results carry s_memtime deltas, shader-clock ticks, instead of lengths).
+(-DZD_EMIT_PHASES: the per-stream results carry s_memtime deltas, shader-clock ticks, instead of lengths: the whole
+stream, the histograms and the code constructions of all its blocks, and everything behind its first block).
 ZIPC_HIP_LIB must point at that build."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,4 +24,6 @@ MHZ = 2381.0  # s_memtime is the shader clock; calibrated against s_memrealtime 
 us = lambda t: t / MHZ
 print("per stream, us (s_memtime at %.0f MHz): total %.1f  histogram %.1f  codes %.1f  pack+rest %.1f   (streams %d)"
       % (MHZ, us(tot.mean()), us(hist.mean()), us(code.mean()), us((tot - hist - code).mean()), n))
+rest = res["status"].astype(np.float64) * 16  # (the timing build puts a clock where the status is)
+print("of the total, the blocks behind a stream's first: %.1f us" % us(rest.mean()))
 print("slowest / mean stream: %.2f ; p99 / mean: %.2f" % (tot.max() / tot.mean(), np.percentile(tot, 99) / tot.mean()))

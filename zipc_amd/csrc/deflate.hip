@@ -1743,6 +1743,7 @@ __global__ __launch_bounds__(64) void lz_parse_gather_kernel(const StreamDesc *_
 // (measured, same box, emit on C2 / text with 1 / 2 / 3 / 4 / 6 / 8 tiles: 3.05 / 2.61 / 2.41 / 2.38 / 2.31 / 2.56 and 1.70 / 1.57 / 1.55 / 1.51 /
 // 1.49 / 1.70 ms: fewer flushes per item, until the staging row costs the wave its place on the CU)
 constexpr int PACK_TILES = 6;  // tiles of 64 items packed between two flushes of the staging row
+static_assert(PACK_TILES % 2 == 0, "an interior turn is PACK_TILES / 2 tiles of 128 symbols (pack_pairs)");
 constexpr int STAGE_WORDS = (7 + PACK_TILES * 64 * 48 + 31) / 32 + 7;  // 7 carried bits + 48 bits per item
 
 // The emit kernel runs one wave per workgroup: LDS operations of one wave execute
@@ -1763,27 +1764,39 @@ struct BitOut {
 
 __device__ __forceinline__ void store_u32_unaligned(uint8_t *p, uint32_t v) { __builtin_memcpy(p, &v, 4); }
 
-// pack PACK_TILES tiles: lane holds (value, nbits) of one item per tile (nbits = 0
-// for idle lanes); tile u's items follow tile u-1's in the bit stream
-__device__ __forceinline__ void pack_tiles(BitOut &bo, uint32_t *stage, const uint64_t *value, const int *nbits,
-                                           int lane) {
-  // stage[] is zero except stage[0] = pending bits
-  uint32_t at = (uint32_t)bo.acc_bits;  // bit offset of the tile in the staging row
-#pragma unroll
-  for (int u = 0; u < PACK_TILES; u++) {
-    const uint32_t incl = wave_scan_incl((uint32_t)nbits[u]);
-    if (nbits[u]) {
-      const uint32_t o = at + incl - (uint32_t)nbits[u];
-      const uint32_t wi = o >> 5, sh = o & 31;
-      const uint64_t lo = value[u] << sh;
-      atomicOr(&stage[wi], (uint32_t)lo);
-      const uint32_t mid = (uint32_t)(lo >> 32);
-      if (mid) atomicOr(&stage[wi + 1], mid);
-      if (sh && nbits[u] + (int)sh > 64) atomicOr(&stage[wi + 2], (uint32_t)(value[u] >> (64 - sh)));
-    }
-    at += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+// dist_to_sym (zd_common.h) as the interior turns issue it: the float converter finds the top bit.  A float's exponent and
+// first mantissa bit are floor(log2 x) and the bit below x's top one, so for x = dist - 1 >= 2 the symbol 2 e + 2 + ((x >> e) & 1),
+// e = floor(log2 x) - 1, is bits 22.. of (float)x less 2 * 127 (x < 2^24: the conversion is exact); 6 vector instructions
+// where the count of leading zeros, its shifts and the test for dist <= 4 took 9.  dist = 0 (no match) gives 64.
+__host__ __device__ constexpr uint32_t dist_sym_cvt(uint32_t dist) {
+  const uint32_t x = dist - 1u;
+  const uint32_t f = (__builtin_bit_cast(uint32_t, (float)x) >> 22) - 254u;
+  return x < 2u ? x : f;
+}
+constexpr bool dist_sym_cvt_ok() {  // every distance, against the symbols' bases and extra bits (dist_sym_value)
+  uint32_t d = 1;
+  for (uint32_t sym = 0; sym <= (uint32_t)DIST_SYM_MAX; sym++) {
+    const uint32_t extra = sym < 4 ? 0u : (sym >> 1) - 1u, base = sym < 4 ? 1u + sym : 1u + ((2u + (sym & 1u)) << extra);
+    if (base != d) return false;
+    for (uint32_t k = 0; k < (1u << extra); k++, d++)
+      if (dist_sym_cvt(d) != sym) return false;
   }
-  const uint32_t total = at;
+  return d == 32769u && dist_sym_cvt(0) == 64u;
+}
+static_assert(dist_sym_cvt_ok(), "dist_sym_cvt is dist_to_sym for every distance of the window");
+
+// nbits (1..64) bits of value into the staging row from bit o on
+__device__ __forceinline__ void stage_put(uint32_t *stage, uint32_t o, uint64_t value, uint32_t nbits) {
+  const uint32_t wi = o >> 5, sh = o & 31;
+  const uint64_t lo = value << sh;
+  atomicOr(&stage[wi], (uint32_t)lo);
+  const uint32_t mid = (uint32_t)(lo >> 32);
+  if (mid) atomicOr(&stage[wi + 1], mid);
+  if (sh && nbits + sh > 64) atomicOr(&stage[wi + 2], (uint32_t)(value >> (64 - sh)));
+}
+
+// the staging row's whole bytes to the stream; what is left (< 8 bits) stays in stage[0]
+__device__ __forceinline__ void pack_flush(BitOut &bo, uint32_t *stage, uint32_t total, int lane) {
   wave_sync();
   const uint32_t full_bytes = total >> 3;
   const uint32_t full_words = full_bytes >> 2;
@@ -1802,6 +1815,44 @@ __device__ __forceinline__ void pack_tiles(BitOut &bo, uint32_t *stage, const ui
   bo.acc = last;
   bo.acc_bits = (int)rem_bits;
   wave_sync();
+}
+
+// pack PACK_TILES tiles: lane holds (value, nbits) of one item per tile (nbits = 0
+// for idle lanes); tile u's items follow tile u-1's in the bit stream
+__device__ __forceinline__ void pack_tiles(BitOut &bo, uint32_t *stage, const uint64_t *value, const int *nbits,
+                                           int lane) {
+  // stage[] is zero except stage[0] = pending bits
+  uint32_t at = (uint32_t)bo.acc_bits;  // bit offset of the tile in the staging row
+#pragma unroll
+  for (int u = 0; u < PACK_TILES; u++) {
+    const uint32_t incl = wave_scan_incl((uint32_t)nbits[u]);
+    if (nbits[u]) stage_put(stage, at + incl - (uint32_t)nbits[u], value[u], (uint32_t)nbits[u]);
+    at += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  }
+  pack_flush(bo, stage, at, lane);
+}
+
+// The same turn where all PACK_TILES * 64 items are symbols: PACK_TILES / 2 tiles of 128, lane i holding symbols 2i
+// (v0, n0) and 2i + 1 (v1, n1) of each.  A pair goes in as one item of n0 + n1 bits -- one scan, one offset, one
+// placement for two symbols -- unless some lane's pair is longer than 64 bits (48 + 48 can be): that tile's lanes place
+// their two symbols one by one, behind the same scan.
+__device__ __forceinline__ void pack_pairs(BitOut &bo, uint32_t *stage, const uint64_t *v0, const int *n0,
+                                           const uint64_t *v1, const int *n1, int lane) {
+  uint32_t at = (uint32_t)bo.acc_bits;
+#pragma unroll
+  for (int q = 0; q < PACK_TILES / 2; q++) {
+    const uint32_t n = (uint32_t)(n0[q] + n1[q]);  // (every lane has two symbols: never 0)
+    const uint32_t incl = wave_scan_incl(n);
+    const uint32_t o = at + incl - n;
+    if (__builtin_amdgcn_ballot_w64(n > 64u) == 0) {  // wave-uniform
+      stage_put(stage, o, v0[q] | (v1[q] << n0[q]), n);
+    } else {
+      stage_put(stage, o, v0[q], (uint32_t)n0[q]);
+      stage_put(stage, o + (uint32_t)n0[q], v1[q], (uint32_t)n1[q]);
+    }
+    at += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  }
+  pack_flush(bo, stage, at, lane);
 }
 
 // ---- the block coder by the whole wave (serial forms: deflate_lane.h, which the
@@ -2157,7 +2208,7 @@ __device__ __forceinline__ void deflate_emit_wave(const uint8_t *__restrict__ sr
   uint32_t adler = 1;  // Adler_32.init
   uint32_t status = ST_OK;
 #ifdef ZD_EMIT_PHASES  // timing-only build: the results carry cycle counts instead (tools/exp_emit_phases.py)
-  uint64_t ph_hist = 0, ph_code = 0;
+  uint64_t ph_hist = 0, ph_code = 0, ph_first = 0;  // ph_first: when the stream's first block was done
   const uint64_t ph_begin = __builtin_readcyclecounter();
 #endif
 
@@ -2172,6 +2223,9 @@ __device__ __forceinline__ void deflate_emit_wave(const uint8_t *__restrict__ sr
   }
   const uint32_t b_first = MODE == 0 ? 0u : only_block, b_end = MODE == 0 ? nblk : only_block + 1u;
   for (uint32_t b = b_first; b < b_end && status == ST_OK; b++) {
+#ifdef ZD_EMIT_PHASES
+    if (b == b_first + 1) ph_first = __builtin_readcyclecounter();
+#endif
     const BlockDesc bd = blocks[b];
     const bool final = b + 1 == nblk;
     // deflated_block_src_crc zd.ml:1081-1086 (Adler: one update call per block)
@@ -2204,6 +2258,8 @@ __device__ __forceinline__ void deflate_emit_wave(const uint8_t *__restrict__ sr
     wave_sync();
     // length -> litlen symbol as a table (in the heap's LDS, idle until the codes are built)
     for (int len = lane; len <= MAX_MATCH_LEN; len += 64) heap[len] = len >= MIN_MATCH_LEN - 1 ? (uint32_t)length_to_sym(len) : 0u;
+    static_assert(MAX_MATCH_LEN < 260, "the length table ends where the second tables of the interior turns begin");
+    for (int i = 260 + lane; i < 580; i += 64) heap[i] = 0;
     wave_sync();
     // 4 tiles of symbols per turn, the next turn's requested before this one's are
     // counted.  The loads are unconditional (clamped index, validity tested at use) so
@@ -2236,9 +2292,50 @@ __device__ __forceinline__ void deflate_emit_wave(const uint8_t *__restrict__ sr
           }
         }
       };
+      // Interior turns: 512 symbols that all lie inside the block.  Order does not matter to a histogram, so a lane
+      // takes 4 consecutive symbols by one 16-byte load from the scalar base (any 4-byte alignment: sym_start of a
+      // later block is what it is), unclamped and untested; the length table is read for every lane (a literal reads
+      // its own entry, below MIN_MATCH_LEN - 1 or not: discarded), one add serves literals and lengths alike, and only
+      // the distance's add stands under the match mask.  The block's last turns keep the edge form below.
+      auto load_in = [&](uint32_t k0) -> u32x4 {
+        u32x4 v;
+        __builtin_memcpy(&v, bsyms + k0 + 4u * (uint32_t)lane, 16);
+        return v;
+      };
+      // (the odd lanes count into a second pair of tables, in what the length table leaves of the heap's LDS: adds to one
+      // address go one after the other, and a block has few symbols that are frequent)
+      uint32_t *lit_freq2 = heap + 260, *dist_freq2 = heap + 260 + 288;
+      uint32_t *lf = (lane & 1) ? lit_freq2 : lit_freq, *df = (lane & 1) ? dist_freq2 : dist_freq;
+      auto count_in = [&](u32x4 w) {
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+          const uint32_t v = w[u], dist = v >> 9;
+          const uint32_t lsym = heap[v & 0x1FF];
+          atomicAdd(&lf[dist == 0 ? v : lsym], 1u);
+          if (dist != 0) atomicAdd(&df[dist_sym_cvt(dist)], 1u);
+        }
+      };
+      uint32_t k_in = 0;
+      if (n_syms_s >= 512u) {  // (wave-uniform)
+        u32x4 wa = load_in(0), wb = load_in(256);
+        for (; k_in + 1024u <= n_syms_s; k_in += 512u) {
+          const u32x4 na = load_in(k_in + 512u), nb = load_in(k_in + 768u);
+          count_in(wa);
+          count_in(wb);
+          wa = na;
+          wb = nb;
+        }
+        count_in(wa);
+        count_in(wb);
+        k_in += 512u;
+        wave_sync();
+        for (int i = lane; i < 288; i += 64) lit_freq[i] += lit_freq2[i];
+        if (lane < 32) dist_freq[lane] += dist_freq2[lane];
+        wave_sync();
+      }
       uint32_t va[4], vb[4];
-      load4(0, va);
-      for (uint32_t k0 = 0; k0 < n_syms_s; k0 += 512) {
+      load4(k_in, va);
+      for (uint32_t k0 = k_in; k0 < n_syms_s; k0 += 512) {
         load4(k0 + 256u, vb);
         count4(k0, va);
         load4(k0 + 512u, va);
@@ -2374,8 +2471,61 @@ __device__ __forceinline__ void deflate_emit_wave(const uint8_t *__restrict__ sr
         nbits = (int)(n + count + (di & 0x1F));
       }
     };
+    // (Two forms of one mapping on purpose: the edge turns and MODE 3's sum of bits, which must agree with the packer bit for
+    // bit, keep encode and dist_to_sym; encode_in and dist_sym_cvt serve the interior turns alone, and dist_sym_cvt's
+    // static_assert holds it to the same symbols.  With the interior forms the emit kernel stands at 128 VGPRs, no scratch:
+    // exactly what __launch_bounds__(64, 4) allows -- whatever is added to this kernel next spills, or must free registers first.)
+    // ... and as an interior turn issues it: both sides for every lane and a select, no branch around either -- nearly every
+    // tile holds both kinds.  (A literal reads the length's and the distance's tables at its own value and at 0, a match
+    // the literals' table at its length: all inside the tables, all discarded.)
+    auto encode_in = [&](uint32_t sr, uint64_t &value, int &nbits) {
+      const uint32_t dist = sr >> 9, len = sr & 0x1FF;
+      const uint32_t sl = hl[len], li = len_item[len];
+      const uint32_t dsym = dist_sym_cvt(dist) & 31u;
+      const uint32_t si = hd[dsym], di = dist_info[dsym];
+      const uint32_t n = li & 0x1F, count = si & 0x1F;
+      const uint64_t mv = (uint64_t)(li >> 5) | (((uint64_t)(si >> 5) | ((uint64_t)(dist - (di >> 5)) << count)) << n);
+      const uint32_t mn = n + count + (di & 0x1F);
+      const bool lit = dist == 0;
+      value = lit ? (uint64_t)(sl >> 5) : mv;
+      nbits = (int)(lit ? sl & 0x1F : mn);
+    };
     // one turn: PACK_TILES tiles of items from `base` on, their symbols in sref (requested a turn ago)
+    // An interior turn -- PACK_TILES * 64 symbols of this part, nothing else -- takes them two to a lane (pack_pairs):
+    // its loads are 8 bytes from the scalar base plus the lane (any 4-byte alignment), sref[2q], sref[2q + 1] the
+    // symbols 2 lane, 2 lane + 1 of tile q.  The turns that hold the type bits, the header or the end-of-block symbol,
+    // and a part's last turn where it is not a whole one, keep the form of one item a lane.  (A part behind the first
+    // begins with symbols, so its first turn is interior like any other: bo.acc_bits seeds the offset.)
+    auto turn_interior = [&](uint32_t base) -> bool {  // (scalar)
+      return base > n_hdr && base + 64u * PACK_TILES <= 1u + n_hdr + n_syms_s && base + 64u * PACK_TILES <= item_hi;
+    };
+    auto fetch_turn = [&](uint32_t base, uint32_t *sref) {
+      if (turn_interior(base)) {
+        const uint32_t *p = bsyms + (base - 1u - n_hdr) + 2u * (uint32_t)lane;
+#pragma unroll
+        for (int q = 0; q < PACK_TILES / 2; q++) {
+          uint2 v;
+          __builtin_memcpy(&v, p + 128 * q, 8);
+          sref[2 * q] = v.x;
+          sref[2 * q + 1] = v.y;
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < PACK_TILES; u++) sref[u] = fetch(base + (uint32_t)(64 * u + lane));
+      }
+    };
     auto pack_turn = [&](uint32_t base, const uint32_t *sref) {
+      if (turn_interior(base)) {
+        uint64_t v0[PACK_TILES / 2], v1[PACK_TILES / 2];
+        int n0[PACK_TILES / 2], n1[PACK_TILES / 2];
+#pragma unroll
+        for (int q = 0; q < PACK_TILES / 2; q++) {
+          encode_in(sref[2 * q], v0[q], n0[q]);
+          encode_in(sref[2 * q + 1], v1[q], n1[q]);
+        }
+        pack_pairs(bo, stage, v0, n0, v1, n1, lane);
+        return;
+      }
       uint64_t value[PACK_TILES];
       int nbits[PACK_TILES];
 #pragma unroll
@@ -2419,16 +2569,13 @@ __device__ __forceinline__ void deflate_emit_wave(const uint8_t *__restrict__ sr
     }
     // (two sets of registers that swap roles by name, as in the histogram loop)
     uint32_t sref_a[PACK_TILES], sref_b[PACK_TILES];
-#pragma unroll
-    for (int u = 0; u < PACK_TILES; u++) sref_a[u] = fetch(item_lo + (uint32_t)(64 * u + lane));
+    fetch_turn(item_lo, sref_a);
     for (uint32_t base = item_lo; base < item_hi; base += 2u * 64u * PACK_TILES) {
-#pragma unroll
-      for (int u = 0; u < PACK_TILES; u++) sref_b[u] = fetch(base + 64u * (uint32_t)(PACK_TILES + u) + (uint32_t)lane);
-      pack_turn(base, sref_a);
       const uint32_t base2 = base + 64u * PACK_TILES;
+      fetch_turn(base2, sref_b);
+      pack_turn(base, sref_a);
       if (base2 >= item_hi) break;  // uniform
-#pragma unroll
-      for (int u = 0; u < PACK_TILES; u++) sref_a[u] = fetch(base2 + 64u * (uint32_t)(PACK_TILES + u) + (uint32_t)lane);
+      fetch_turn(base2 + 64u * PACK_TILES, sref_a);
       pack_turn(base2, sref_b);
     }
   }
@@ -2452,6 +2599,7 @@ __device__ __forceinline__ void deflate_emit_wave(const uint8_t *__restrict__ sr
 #ifdef ZD_EMIT_PHASES
     r.checksum = (uint32_t)((__builtin_readcyclecounter() - ph_begin) >> 4);
     r.out_len = (ph_hist >> 4) | ((ph_code >> 4) << 32);
+    r.status = ph_first ? (uint32_t)((__builtin_readcyclecounter() - ph_first) >> 4) : 0u;  // the blocks behind the first
 #endif
     results[stream] = r;
   }
