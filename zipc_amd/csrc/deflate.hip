@@ -273,7 +273,7 @@ __device__ __forceinline__ void lz_chain_workgroup(const uint8_t *__restrict__ s
           d = (p - e_old[i]) & 0xFFFFu;
           if (d > 32768) d = 0;
         }
-        if (!SEG || p >= own_lo) prev[p] = (uint16_t)d;
+        if (!SEG || p >= own_lo) prev[p] = (uint16_t)d;  // (at most 32768, or 0: lz_match's steady loop relies on it, deflate_lane.h match_run_step_masks)
       }
     }
     lds_barrier();
@@ -376,7 +376,7 @@ __device__ __forceinline__ void lz_chain_xchg_workgroup(const uint8_t *__restric
     for (int u = 0; u < XCHG_U; u++) {
       const uint32_t p = t * XCHG_TURN + 64u * (uint32_t)u + lane;
       const uint32_t d = p - old[u];
-      if ((decltype(WHOLE)::value || p <= max_pos) && (!SEG || p >= own_lo)) prev[p] = (uint16_t)(d <= (uint32_t)MAX_MATCH_DIST ? d : 0u);
+      if ((decltype(WHOLE)::value || p <= max_pos) && (!SEG || p >= own_lo)) prev[p] = (uint16_t)(d <= (uint32_t)MAX_MATCH_DIST ? d : 0u);  // (lz_match's steady loop relies on this bound)
     }
   };
   uint32_t wa[XCHG_U], wb[XCHG_U];
@@ -670,6 +670,38 @@ __device__ __forceinline__ u32x4 links_for_window(u32x4 v) {
   return __builtin_bit_cast(u32x4, __builtin_elementwise_add_sat((u16x8)(__builtin_bit_cast(u16x8, v) - one), one));
 }
 
+// The first form of a tile's walk, OUT OF LINE (round 10).  Inlined beside the second form its loops share one register
+// assignment with it, and a change of the first form moved the second's: with the steady loop inline the second form's code
+// kept scalar constants it had held in registers inside its loops and the corpus' lz_match read 3.3 % higher, with not one
+// instruction of its source changed.  The window, its links and the pool's counter come as LDS addresses and the tables as
+// global pointers, so that the loads and stores keep their address spaces across the call.  In the library's build neither
+// the function nor the kernel has a stack (private segment 0); built with -gline-tables-only for a listing, the function saves
+// one register on it, 8 bytes a lane.
+struct MatchFirstForm { uint32_t iters, two; };  // the wave's iterations; some position of mine left a second answer
+__device__ __attribute__((noinline)) MatchFirstForm lz_match_first_form(uint32_t lds_src, uint32_t lds_links, uint32_t lds_pool, uint32_t w0,
+                                                                         uint32_t len, uint32_t t0, uint32_t tend, uint32_t lane,
+                                                                         __attribute__((address_space(1))) uint32_t *match,
+                                                                         __attribute__((address_space(1))) uint32_t *snap, int K, int Kq) {
+  typedef __attribute__((address_space(3))) uint8_t lds_u8;
+  typedef __attribute__((address_space(3))) uint16_t lds_u16;
+  typedef __attribute__((address_space(3))) uint32_t lds_u32;
+  typedef __attribute__((address_space(1))) uint32_t glob_u32;
+  // a function's arguments arrive in vector registers: all but `lane` are wave-uniform, and the loop must know it (without
+  // this its steady form issued 312 vector instructions where the inlined one issues 243)
+  auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+  auto uni_p = [&](glob_u32 *q) { return (glob_u32 *)(uintptr_t)((uint64_t)uni((uint32_t)(uintptr_t)q) | ((uint64_t)uni((uint32_t)((uintptr_t)q >> 32)) << 32)); };
+  lds_src = uni(lds_src); lds_links = uni(lds_links); lds_pool = uni(lds_pool); w0 = uni(w0); len = uni(len); t0 = uni(t0); tend = uni(tend);
+  K = (int)uni((uint32_t)K); Kq = (int)uni((uint32_t)Kq);
+  match = uni_p(match); snap = uni_p(snap);
+  const uint8_t *ws = (const uint8_t *)(lds_u8 *)(uintptr_t)lds_src - w0;  // indexed by stream position
+  const WinLinks wp{(const uint16_t *)(lds_u16 *)(uintptr_t)lds_links - w0};
+  TilePool pool{(uint32_t *)(lds_u32 *)(uintptr_t)lds_pool, t0, tend, lane, 0u};
+  uint32_t two = 0;
+  auto sink = [&](uint32_t p, uint32_t best, uint32_t first) { two |= match_store((uint32_t *)match, (uint32_t *)snap, p, best, first) ? 1u : 0u; };
+  const uint32_t iters = lz_match_runs_pool<MATCHW_NP>(ws, len, pool, tend, lane, wp, K, Kq, sink);
+  return MatchFirstForm{iters, two};
+}
+
 // A workgroup takes tiles_per_group consecutive tiles of one stream: between workgroups
 // a CU sat idle for 4.4 us of a 29.3 us tile on C2 (tools/exp_match_phases.py).  A wave
 // requests its share of the next tile's window into registers as soon as it has walked
@@ -818,8 +850,6 @@ __global__ __launch_bounds__(MATCHW_THREADS) void lz_match_window_kernel(const u
     const unsigned long long ph1 = __builtin_readcyclecounter();
 #endif
     const bool has_next = c.tile + 1 < c.tile_end;  // (of the same group; uniform over the workgroup)
-    const uint8_t *ws = win_src - g.w0;  // indexed by stream position
-    const WinLinks wp{win_prev - g.w0};
     // The tile's positions are ONE pool for the workgroup's 16 waves (lz_match_runs_pool): a wave
     // fetches chunks of 256 from pool_next and hands them to its run slots as they finish.  The
     // first schedule gave every wave a fixed 1 Ki positions and every lane every 64th of them: a
@@ -838,10 +868,22 @@ __global__ __launch_bounds__(MATCHW_THREADS) void lz_match_window_kernel(const u
       const uint32_t lds_src = (uint32_t)(uintptr_t)(lds_u8 *)win_src, lds_links = (uint32_t)(uintptr_t)(lds_u8 *)win_prev;
       const uint32_t off_w = g.w0 - lds_src;  // coordinate + off_w = stream position
       auto sink_w = [&](uint32_t p, uint32_t best, uint32_t first) { sink(p + off_w, best, first); };
-      TilePool pool{&pool_next, g.t0, (uint32_t)tend64, tid & 63u, 0u}, pool_w{&pool_next, g.t0 - off_w, (uint32_t)tend64 - off_w, tid & 63u, POOL_TAPER};
-      const uint32_t iters = scan_form ? lz_match_scan_pool<MATCHW_SCAN_NP>((const uint8_t *)win_src - lds_src, c.len - off_w, pool_w, (uint32_t)tend64 - off_w, tid & 63u,
-                                                                          WinLinks{win_prev - lds_src}, lds_links - 2u * lds_src, K, Kq, sink_w)
-                                       : lz_match_runs_pool<MATCHW_NP>(ws, c.len, pool, (uint32_t)tend64, tid & 63u, wp, K, Kq, sink);
+      TilePool pool_w{&pool_next, g.t0 - off_w, (uint32_t)tend64 - off_w, tid & 63u, POOL_TAPER};
+      uint32_t iters;
+      // (the second form's arm is the expected one: beside a call that may go either way its inlined loops were laid out and
+      // given registers around the call's -- 223 vector instructions an iteration where the parent has 207 and this has 207 again --
+      // and the corpus read 0.7 % higher; nothing but the layout depends on it, and the first form's code is in its function)
+      if (__builtin_expect(scan_form, 1)) {
+        iters = lz_match_scan_pool<MATCHW_SCAN_NP>((const uint8_t *)win_src - lds_src, c.len - off_w, pool_w, (uint32_t)tend64 - off_w, tid & 63u,
+                                                   WinLinks{win_prev - lds_src}, lds_links - 2u * lds_src, K, Kq, sink_w);
+      } else {  // (out of line: lz_match_first_form)
+        typedef __attribute__((address_space(3))) uint32_t lds_u32;
+        typedef __attribute__((address_space(1))) uint32_t glob_u32;
+        const MatchFirstForm f = lz_match_first_form(lds_src, lds_links, (uint32_t)(uintptr_t)(lds_u32 *)&pool_next, g.w0, c.len, g.t0, (uint32_t)tend64, tid & 63u,
+                                                     (glob_u32 *)(S.match + c.base), (glob_u32 *)(S.snap + c.base), K, Kq);
+        iters = f.iters;
+        two |= f.two;
+      }
       if (two) S.snap_used[c.stream] = 1;  // (every writer writes the same word; read by the parse, a kernel later)
       if (has_next && (tid & 63u) == 0) atomicAdd(&tile_iters[c.tile & 1u], iters);
     }

@@ -17,6 +17,7 @@
 #pragma once
 
 #include "zd_common.h"
+#include "match_pool.h"
 
 namespace zd {
 
@@ -498,8 +499,7 @@ ZD_HD void lz_match_scan_serial(const uint8_t *s, uint32_t len, uint32_t first, 
 // iteration count.
 constexpr uint32_t POOL_TAPER = 4096;
 constexpr uint32_t POOL_TAPER_Q = 2;  // chunks of a quarter for the last POOL_TAPER / POOL_TAPER_Q positions (TilePool below)
-constexpr uint32_t POOL_CHUNK = 256;  // >= 64 * NP: a fresh chunk serves any one handout.  Measured, same box, 128 / 256 / 512:
-                                      // C2 5.58 / 5.44-5.48 / 5.83 ms, real text 145.5 / 150.1 / 167.5 ms
+// (POOL_CHUNK, the positions a wave fetches at a time, and the handout's arithmetic: match_pool.h)
 // first form of the walk (match_run_step: every candidate's 8 bytes are read): the faster one
 // where chains are a candidate or two long.  Returns the wave's iterations: x 64 NP / positions = steps per position / lane use.
 // (sink(p, best, first): where a finished position's two answers go -- the kernel's tables)
@@ -565,26 +565,39 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
 // Here the finished runs come back as a mask and the steps are counted by an add-with-carry of the walk mask: three vector
 // instructions fewer per run slot and iteration, no scalar instruction more (the mask form that moved MORE to the scalar
 // unit lost: `git show 4d5ffca:tools/experiments/lz_match_walk_masks`).  Returns the lanes whose position is finished.
-template <typename Sink, typename S, typename P>
+// STEADY (round 10; the steady loop of lz_match_runs_pool): every lane of the wave is alive, its maxlen is MAX_MATCH_LEN,
+// and K and Kq are not 0.  Then r.alive and r.maxlen are neither read nor written, and of the five compares that make
+// `walk` ONE is left, dn != none:
+//   * a run that goes on: the step before made `more` of the same operands (r.q - r.dn there is qc - d2 here), and more
+//     implies d2 != none;
+//   * a run that starts: steps = 0 != K, best_len = 3 < 258, and p - qn is its link, which is at most MAX_MATCH_DIST
+//     whenever it is not "none": both forms of lz_chain store a distance above MAX_MATCH_DIST as 0 (deflate.hip, the two
+//     `prev[p] =` of the ordering and the exchange kernel: `if (d > 32768) d = 0`, `d <= MAX_MATCH_DIST ? d : 0`; the
+//     ordering kernel's other two sources are distances inside its own turn), tests/test_gpu_chain_links.py holds every
+//     link to the serial insert, and the window's staging maps 0 to 0xFFFF and nothing else.
+// (The carried form -- `more` kept as a scalar pair per slot, the start's compare made in the handout -- asks that compare
+// where the link has just been requested from LDS; at the step's head the other slot's step lies between.)
+template <bool STEADY, typename Sink, typename S, typename P>
 __device__ __forceinline__ unsigned long long match_run_step_masks(MatchRun &r, S s, P prev, uint32_t K, uint32_t Kq, Sink sink) {
   auto ballot = [](bool b) { return (unsigned long long)__builtin_amdgcn_ballot_w64(b); };
   auto mine = [](unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); };
   const uint32_t qn = r.q - r.dn;
-  const unsigned long long alive_m = ballot(r.alive != 0);
-  const unsigned long long walk_m = alive_m & ballot(r.dn != LinkNone<P>::value) & ballot(r.steps != K) & ballot(r.best_len < r.maxlen) &
-                                    ballot(r.p - qn <= (uint32_t)MAX_MATCH_DIST);  // zd.ml:1181,1187
+  const uint32_t maxlen = STEADY ? (uint32_t)MAX_MATCH_LEN : r.maxlen;
+  const unsigned long long alive_m = STEADY ? ~0ull : ballot(r.alive != 0);
+  unsigned long long walk_m = ballot(r.dn != LinkNone<P>::value);
+  if (!STEADY) walk_m &= alive_m & ballot(r.steps != K) & ballot(r.best_len < maxlen) & ballot(r.p - qn <= (uint32_t)MAX_MATCH_DIST);  // zd.ml:1181,1187
   const bool walk = mine(walk_m);
   const uint32_t qc = walk ? qn : r.p;
   const uint64_t x = load_u64_words(s, qc) ^ r.pw;
   const uint32_t d2 = prev[qc];
   uint32_t l = x ? (uint32_t)(__builtin_ctzll(x) >> 3) : 8u;
-  if (walk && (x == 0 || r.maxlen < 8)) {  // (as in match_run_step_to)
+  if (walk && (x == 0 || maxlen < 8)) {  // (as in match_run_step_to)
     bool compare = true;
     if (x == 0 && r.best_len >= 8u) {
       const uint32_t toff = r.best_len - 7u;
       compare = load_u64_words(s, qc + toff) == load_u64_words(s, r.p + toff);
     }
-    if (compare) l = common_prefix_t<true>(s, qc, r.p, r.maxlen, r.maxlen >= 8u ? 8u : 0u);
+    if (compare) l = common_prefix_t<true>(s, qc, r.p, maxlen, maxlen >= 8u ? 8u : 0u);
   }
   unsigned long long carry_out;
   uint32_t steps;
@@ -597,16 +610,26 @@ __device__ __forceinline__ unsigned long long match_run_step_masks(MatchRun &r, 
   r.q = qc;
   r.steps = steps;
   r.dn = d2;
-  const unsigned long long more_m = walk_m & ballot(l != r.maxlen) & ballot(d2 != LinkNone<P>::value) & ballot(steps != K) &
+  const unsigned long long more_m = walk_m & ballot(l != maxlen) & ballot(d2 != LinkNone<P>::value) & ballot(steps != K) &
                                     ballot(r.p - qc + d2 <= (uint32_t)MAX_MATCH_DIST);
   const unsigned long long fin_m = alive_m & ~more_m;
   if (mine(fin_m)) {
-    const uint32_t snap = Kq == 0 ? 0u : (r.snap != SNAP_NONE ? r.snap : best);
+    const uint32_t snap = !STEADY && Kq == 0 ? 0u : (r.snap != SNAP_NONE ? r.snap : best);
     sink(r.p, best, snap);
   }
   return fin_m;
 }
 
+// The STEADY loop (round 10) stands in front of the general one: the form the loop takes in the interior of a stream, where
+// every one of the wave's 64 NP runs holds a real position whose maxlen is MAX_MATCH_LEN (match_pool.h: match_chunk_steady).
+// It has no `alive` and no `maxlen` (match_run_step_masks<true>), its start of a position makes neither, parks nothing
+// and asks no `np < lim`, it has no exit test -- while the pool hands out no run is dead -- and its common handout is an add.
+// It is entered behind the first fill if the first chunk is a whole, steady one, and left through the handout alone: at the
+// first one match_handout_steady refuses (a fresh chunk that is short, or near the stream's end, or none).  That handout
+// -- its chunk already fetched -- and the rest of that iteration are the general code's, and the general loop goes on with
+// the runs as they are.  On a 64 KiB stream that is all of a wave's chunks but its last in either tile, and the stream's
+// last two.  Pools with a taper, K = 0 and Kq = 0 (whose second answer is 0: the step's Kq == 0 is a test per launch,
+// made here) keep the general loop alone.
 template <int NP, typename Sink, typename S, typename P, typename Pool>
 __device__ __forceinline__ uint32_t lz_match_runs_pool(S s, uint32_t len, Pool &pool, uint32_t pend, uint32_t lane,
                                                         P prev, int K, int Kq, Sink sink) {
@@ -628,6 +651,7 @@ __device__ __forceinline__ uint32_t lz_match_runs_pool(S s, uint32_t len, Pool &
   uint32_t next = fetch(true);  // my chunk is [next, cend)
   uint32_t cend = pend - next > pool.size ? next + pool.size : pend;
   bool empty = next >= pend;
+  bool steady = !Pool::WANTS_OLDEST && pool.taper == 0 && K != 0 && Kq != 0 && cend - next == POOL_CHUNK && match_chunk_steady(cend, len);
   // (positions are formed as "start + offset if offset < what is left, else the limit": a stream
   // may end within a chunk of 2^32 and a sum must not wrap into a position that looks valid)
 #pragma unroll
@@ -636,47 +660,105 @@ __device__ __forceinline__ uint32_t lz_match_runs_pool(S s, uint32_t len, Pool &
     match_run_start<true>(r[i], s, len, off < cend - next ? next + off : cend, cend, prev);
   }
   next = cend - next > 64u * NP ? next + 64u * NP : cend;
-  for (;;) {
+  auto rank_of = [](unsigned long long fm) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u)); };
+  // the general handout of a slot whose step finished the lanes fm (not 0), and the start of their next positions.  given:
+  // the chunk this handout runs into has been fetched already, it starts at gc (the steady loop's last handout)
+  auto hand = [&](MatchRun &n, unsigned long long fm, bool given, uint32_t gc) __attribute__((always_inline)) {
+    const bool fin = __builtin_amdgcn_inverse_ballot_w64(fm);
+    ZD_COUNT(6, 1); ZD_COUNT(7, __builtin_popcountll(fm));
+    const uint32_t rank = rank_of(fm);
+    const uint32_t taken = (uint32_t)__builtin_popcountll(fm);
+    const bool fresh = taken > cend - next && !empty;  // wave-uniform: the chunk runs out within this handout
+    uint32_t c = 0, ce = 0;
+    if (fresh) {
+      c = given ? gc : fetch(false);
+      ce = pend - c > pool.size ? c + pool.size : pend;
+      empty = c >= pend;
+    }
+    const MatchHandout h = match_handout(rank, taken, next, cend, fresh, c, ce);
+    next = h.next;
+    cend = h.cend;
+    if (fin) {  // match_run_start with the position's test made once (the shared form clamps np to lim and then compares again)
+      const uint32_t park = h.lim ? h.lim - 1u : 0u;  // a finished run parks on a valid position
+      n.alive = h.np < h.lim ? 1u : 0u;
+      n.p = h.np < park ? h.np : park;
+      n.q = n.p;
+      n.best_len = MIN_MATCH_LEN - 1;
+      n.best = 0; n.snap = SNAP_NONE; n.steps = 0;
+      n.maxlen = len - n.p < (uint32_t)MAX_MATCH_LEN ? len - n.p : (uint32_t)MAX_MATCH_LEN;
+      n.pw = load_u64_words(s, n.p);
+      n.dn = prev[n.p];
+    }
+  };
+  bool go = true;  // (wave-uniform) some run still has a position
+  if (steady) {
+    int left = NP;                // the slot whose handout left the steady form ...
+    unsigned long long lfm = 0;   // ... the lanes its step finished ...
+    uint32_t lc = 0;              // ... and the chunk fetched for them
+    for (;;) {  // (no exit test: while the pool hands out, no run is without a position)
+      iters++;
+      ZD_COUNT(1, 1); ZD_COUNT(2, 1);
+#pragma unroll
+      for (int i = 0; i < NP; i++) {
+        ZD_COUNT(8, 64);
+        const unsigned long long fm = match_run_step_masks<true>(r[i], s, prev, (uint32_t)K, (uint32_t)Kq, sink);
+        if (fm) {  // wave-uniform
+          const uint32_t rank = rank_of(fm);
+          const uint32_t taken = (uint32_t)__builtin_popcountll(fm);
+          MatchHandout h = match_handout_within(rank, taken, next, cend);
+          if (__builtin_expect(!match_handout_steady(taken, next, cend, false, 0u, 0u, len), 0)) {  // wave-uniform: the chunk runs out
+            const uint32_t c = fetch(false);
+            const uint32_t ce = pend - c > pool.size ? c + pool.size : pend;
+            if (!match_handout_steady(taken, next, cend, true, c, ce, len)) { left = i; lfm = fm; lc = c; goto leave_steady; }
+            h = match_handout(rank, taken, next, cend, true, c, ce);
+          }
+          ZD_COUNT(6, 1); ZD_COUNT(7, taken);
+          next = h.next;
+          cend = h.cend;
+          if (__builtin_amdgcn_inverse_ballot_w64(fm)) {  // the start of a steady position
+            MatchRun &n = r[i];
+            n.p = h.np;
+            n.q = h.np;
+            n.best_len = MIN_MATCH_LEN - 1;
+            n.best = 0; n.snap = SNAP_NONE; n.steps = 0;
+            n.pw = load_u64_words(s, h.np);
+            n.dn = prev[h.np];
+          }
+        }
+      }
+    }
+  leave_steady:
+    // the rest of the iteration in the general form: slot `left` from its handout on, the slots behind it whole
+    bool alive = false;
+#pragma unroll
+    for (int i = 0; i < NP; i++) {
+      r[i].alive = 1u;
+      r[i].maxlen = (uint32_t)MAX_MATCH_LEN;
+    }
+#pragma unroll
+    for (int i = 0; i < NP; i++) {
+      if (i == left) hand(r[i], lfm, true, lc);  // wave-uniform, like the next
+      if (i > left) {
+        ZD_COUNT(8, 64);
+        const unsigned long long fm = match_run_step_masks<false>(r[i], s, prev, (uint32_t)K, (uint32_t)Kq, sink);
+        if (fm) hand(r[i], fm, false, 0u);
+      }
+      alive |= r[i].alive;
+    }
+    go = __builtin_amdgcn_ballot_w64(alive) != 0;
+  }
+  while (go) {
     bool alive = false;
     iters++;
     ZD_COUNT(1, 1); ZD_COUNT(2, 1);
 #pragma unroll
     for (int i = 0; i < NP; i++) {
       ZD_COUNT(8, __builtin_popcountll(__builtin_amdgcn_ballot_w64(r[i].alive != 0)));
-      const unsigned long long fm = match_run_step_masks(r[i], s, prev, (uint32_t)K, (uint32_t)Kq, sink);
-      const bool fin = __builtin_amdgcn_inverse_ballot_w64(fm);
-      if (fm) {  // wave-uniform
-        ZD_COUNT(6, 1); ZD_COUNT(7, __builtin_popcountll(fm));
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
-        const uint32_t taken = (uint32_t)__builtin_popcountll(fm);
-        const uint32_t rem = cend - next;
-        uint32_t np = rank < rem ? next + rank : cend, lim = cend;
-        if (taken > rem && !empty) {  // wave-uniform: the chunk runs out within this handout
-          const uint32_t c = fetch(false);
-          const uint32_t ce = pend - c > pool.size ? c + pool.size : pend;
-          empty = c >= pend;
-          if (rank >= rem) { np = rank - rem < ce - c ? c + (rank - rem) : ce; lim = ce; }
-          next = ce - c > taken - rem ? c + (taken - rem) : ce;
-          cend = ce;
-        } else {
-          next = rem > taken ? next + taken : cend;
-        }
-        if (fin) {  // match_run_start with the position's test made once (the shared form clamps np to lim and then compares again)
-          MatchRun &n = r[i];
-          const uint32_t park = lim ? lim - 1u : 0u;  // a finished run parks on a valid position
-          n.alive = np < lim ? 1u : 0u;
-          n.p = np < park ? np : park;
-          n.q = n.p;
-          n.best_len = MIN_MATCH_LEN - 1;
-          n.best = 0; n.snap = SNAP_NONE; n.steps = 0;
-          n.maxlen = len - n.p < (uint32_t)MAX_MATCH_LEN ? len - n.p : (uint32_t)MAX_MATCH_LEN;
-          n.pw = load_u64_words(s, n.p);
-          n.dn = prev[n.p];
-        }
-      }
+      const unsigned long long fm = match_run_step_masks<false>(r[i], s, prev, (uint32_t)K, (uint32_t)Kq, sink);
+      if (fm) hand(r[i], fm, false, 0u);  // wave-uniform
       alive |= r[i].alive;
     }
-    if (__builtin_amdgcn_ballot_w64(alive) == 0) break;
+    go = __builtin_amdgcn_ballot_w64(alive) != 0;
   }
 #ifdef ZD_MATCH_COUNTS
   mc.flush(lane);
