@@ -163,6 +163,45 @@ let zlib_decompress ?decompressed_size ?start ?len s =
   in
   go (if has_limit = 1 then limit else max (3 * n) 1024)
 
+(* ADDITIONS the reference's signature (src/zipc_deflate.mli) does not have: streams whose compressed length is not
+   known.  The range ?start ?len is an upper bound of the stream; the result carries the count of source bytes, from
+   start on, that the stream took (zipc_hip_inflate_extent / zipc_hip_zlib_decompress_extent: a zlib stream's count
+   includes its header and its Adler-32).  The next stream of a run stored back to back begins at start + used. *)
+let c_inflate_extent =
+  f "zipc_hip_inflate_extent"
+    (ctx_t @-> ocaml_string @-> size_t @-> int @-> size_t @-> ocaml_bytes @-> size_t @-> int @->
+     ptr size_t @-> ptr size_t @-> ptr uint32_t @-> returning int)
+let c_zlib_decompress_extent =
+  f "zipc_hip_zlib_decompress_extent"
+    (ctx_t @-> ocaml_string @-> size_t @-> int @-> size_t @-> ocaml_bytes @-> size_t @->
+     ptr size_t @-> ptr size_t @-> ptr uint32_t @-> returning int)
+
+let extent ?decompressed_size ?start ?len s ~call =
+  let s = range ?start ?len s in
+  let n = String.length s in
+  let has_limit, limit = match decompressed_size with None -> 0, 0 | Some d -> 1, d in
+  let rec go cap =
+    let dst = Bytes.create cap in
+    let out_len = allocate size_t Unsigned.Size_t.zero in
+    let used = allocate size_t Unsigned.Size_t.zero in
+    let crc = allocate uint32_t Unsigned.UInt32.zero in
+    let st = call (ocaml_string_start s) (sz n) has_limit (sz limit) (ocaml_bytes_start dst) (sz cap) out_len used crc in
+    if st = err_dst_too_small && has_limit = 0 then go (2 * cap) else
+    if st = err_zlib_method
+    then Error (Printf.sprintf "Unknown compression method (%d)" (String.get_uint8 s 0 land 0x0F)) else
+    if st <> ok then Error (c_strerror st) else
+    Ok (Bytes.sub_string dst 0 (Unsigned.Size_t.to_int (!@ out_len)), Unsigned.Size_t.to_int (!@ used))
+  in
+  go (if has_limit = 1 then limit else max (3 * n) 1024)
+
+let inflate_extent ?decompressed_size ?start ?len s =
+  extent ?decompressed_size ?start ?len s
+    ~call:(fun p n h l d c o u k -> c_inflate_extent (Lazy.force ctx) p n h l d c crc_nop o u k)
+
+let zlib_decompress_extent ?decompressed_size ?start ?len s =
+  extent ?decompressed_size ?start ?len s
+    ~call:(fun p n h l d c o u k -> c_zlib_decompress_extent (Lazy.force ctx) p n h l d c o u k)
+
 type level = [ `None | `Fast | `Default | `Best ]
 
 let level_code = function `None -> 0 | `Fast -> 1 | `Default -> 2 | `Best -> 3

@@ -483,6 +483,85 @@ int zipc_hip_zlib_size_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
                                     const zipc_hip_stream_desc *d_descs,
                                     zipc_hip_stream_result *d_results, size_t n_streams);
 
+/* Streams of UNKNOWN COMPRESSED LENGTH: where each one ends.  Every decode form ignores what lies behind the final block, as
+ * the reference does, so src_len may already be an upper bound of the stream's length -- but a raw deflate stream carries
+ * no length of its own and a zlib stream only an Adler-32 (objects of a git pack, Flate streams of a PDF, zlib streams in
+ * other containers, any run of streams stored back to back).  The extent forms are the forms they mirror, with one more
+ * answer: src_used, the source bytes the stream took.  Nothing of an existing form changes. */
+typedef struct {            /* 32 bytes: zipc_hip_stream_result's three fields, then the extent */
+  uint32_t status;    /* as in the mirrored form */
+  uint32_t checksum;  /* as in the mirrored form; 0 unless OK */
+  uint64_t out_len;   /* as in the mirrored form; 0 unless OK */
+  uint64_t src_used;  /* source bytes from src_off up to and including the byte that holds the last bit of the final block --
+                         behind the end-of-block symbol of a compressed block, behind the last data byte of a stored one
+                         (LEN == 0 included); the zlib forms: the whole stream, header and trailer too.  0 unless OK: a
+                         stream that is refused has no extent.  src_used <= src_len for every OK stream. */
+  uint64_t reserved;  /* 0 */
+} zipc_hip_extent_result;
+/* All pointers are DEVICE pointers.  The descriptors are zipc_hip_stream_desc, every field as in the form each mirrors;
+ * src_len may be any upper bound of the stream's length that lies inside the arena: nothing behind src_off + src_len is read.
+ * The defining properties:
+ *   raw, decode (zipc_hip_inflate_extent_batch): status, checksum, out_len and the destination bytes are what
+ *     zipc_hip_inflate_batch gives for the same descriptor and crc_op -- the table of room rules and the guard-byte contract
+ *     there included.  src_used is 0 unless OK.  For an OK stream, zipc_hip_inflate_batch with src_len := src_used gives the
+ *     same result and bytes.  With ZIPC_HIP_CRC_CRC32 a stream whose output is longer than max_dst_cap is
+ *     ZIPC_HIP_ERR_INVALID_ARG as it is there (its checksum would cover only a part), with checksum, out_len and src_used 0
+ *     like every status but OK (zipc_hip_inflate_batch leaves the length in that one record).
+ *   raw, size (zipc_hip_inflate_size_extent_batch, zipc_hip_inflate_size_extent_blocks_batch): the same with
+ *     zipc_hip_inflate_size_batch / zipc_hip_inflate_size_blocks_batch; checksum is 0, no arena but the source is touched.
+ *     The blocks form synchronises where zipc_hip_inflate_size_blocks_batch does, picks the streams it picks, and
+ *     zipc_hip_last_size_blocks says what it says there; the wave form never synchronises.
+ *   zlib (zipc_hip_zlib_decompress_extent_batch, zipc_hip_zlib_size_extent_batch, zipc_hip_zlib_size_extent_blocks_batch):
+ *     header failures are the reference's, in its order; src_len < 6 is ZIPC_HIP_ERR_CORRUPTED and nothing of the stream is
+ *     read.  The body handed to the codec is the reference's range [2, src_len - 2).  With u the body's extent, the trailer
+ *     is the four bytes at src_off + 2 + u, big-endian, NOT those at src_len - 4; if 2 + u + 4 > src_len the trailer is not
+ *     inside the declared bytes: ZIPC_HIP_ERR_CORRUPTED, nothing compared.  Otherwise the Adler-32 is compared as
+ *     zipc_hip_zlib_decompress_batch compares it: a mismatch is ZIPC_HIP_ERR_CHECKSUM with the value found, out_len 0 and
+ *     src_used 0.  On OK src_used = u + 6, and zipc_hip_zlib_decompress_batch (or zipc_hip_zlib_size_batch) with
+ *     src_len := src_used gives the same status, checksum, out_len and bytes.  The sizing forms compare no checksum, like
+ *     zipc_hip_zlib_size_batch, but hold the same "trailer inside src_len" rule, so a stream they size OK has the src_used
+ *     the decode form reports.
+ * The decode forms are ALWAYS a wave per stream, whatever max_dst_cap: one launch (and for ZIPC_HIP_CRC_CRC32 the checksum
+ * pass over the produced bytes, which max_dst_cap sizes as in zipc_hip_inflate_batch), enqueued on the context's stream and
+ * never synchronised (growing the context's scratch may synchronise, as everywhere); there is no by-blocks path and
+ * zipc_hip_last_inflate_blocks is 0 behind them.  A long stream then costs what its one wave costs: 4.5 - 6.9 ms a MiB of
+ * output (the sizing form's figure), where zipc_hip_inflate_batch decodes it by blocks in 0.13 - 1.8.  A
+ * caller with long streams sizes them with zipc_hip_inflate_size_extent_blocks_batch and decodes with
+ * zipc_hip_inflate_batch over src_len := src_used.
+ * Null ctx, d_descs or d_results, n_streams above 0x7FFFFFFF, or a crc_op outside the ZIPC_HIP_CRC_* values, fails the call
+ * with ZIPC_HIP_ERR_INVALID_ARG; n_streams == 0 is ZIPC_HIP_OK and nothing is enqueued.  A flag bit other than
+ * ZIPC_HIP_STREAM_HAS_LIMIT, or a length above ZIPC_HIP_MAX_STREAM_LEN, is ZIPC_HIP_ERR_INVALID_ARG in the stream's own
+ * result.  Walking a run of back-to-back streams is the caller's loop (each start depends on the end before it):
+ * INTEGRATION.md has the recipe "streams whose compressed length you do not know". */
+int zipc_hip_inflate_extent_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                  const zipc_hip_stream_desc *d_descs, zipc_hip_extent_result *d_results,
+                                  size_t n_streams, size_t max_dst_cap, int crc_op);
+int zipc_hip_zlib_decompress_extent_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                          const zipc_hip_stream_desc *d_descs, zipc_hip_extent_result *d_results,
+                                          size_t n_streams, size_t max_dst_cap);
+int zipc_hip_inflate_size_extent_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
+                                       const zipc_hip_stream_desc *d_descs,
+                                       zipc_hip_extent_result *d_results, size_t n_streams);
+int zipc_hip_zlib_size_extent_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
+                                    const zipc_hip_stream_desc *d_descs,
+                                    zipc_hip_extent_result *d_results, size_t n_streams);
+int zipc_hip_inflate_size_extent_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
+                                              const zipc_hip_stream_desc *d_descs,
+                                              zipc_hip_extent_result *d_results, size_t n_streams);
+int zipc_hip_zlib_size_extent_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena,
+                                           const zipc_hip_stream_desc *d_descs,
+                                           zipc_hip_extent_result *d_results, size_t n_streams);
+/* One stream from HOST memory, staged like zipc_hip_inflate / zipc_hip_zlib_decompress: `len` is an upper bound, *src_used
+ * the bytes of src the stream took (0 unless ZIPC_HIP_OK); everything else as in those two.  The stream's one wave decodes
+ * it whatever its length (see above).  On ZIPC_HIP_ERR_CHECKSUM *adler is the value found, with every other error 0.
+ * Many-stream host forms (_many) of the extent forms are out of scope: there are none. */
+int zipc_hip_inflate_extent(zipc_hip_ctx *ctx, const void *src, size_t len, int has_limit, size_t limit,
+                            void *dst, size_t dst_cap, int crc_op, size_t *out_len, size_t *src_used,
+                            uint32_t *checksum);
+int zipc_hip_zlib_decompress_extent(zipc_hip_ctx *ctx, const void *src, size_t len, int has_limit, size_t limit,
+                                    void *dst, size_t dst_cap, size_t *out_len, size_t *src_used,
+                                    uint32_t *adler);
+
 /* Decode into ONE arena laid out on the device: size-then-decode (above) as one call, for a batch that is on the device
  * and whose caller has no destinations of their own.  The call sizes every stream, lays the outputs end to end in
  * d_dst_arena, decodes them there and says where each one went; nothing is read back for the layout.  All pointers are

@@ -123,6 +123,14 @@ SYMBOLS = [
     ("zipc_hip_zlib_size_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_inflate_prefix_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ]),
     ("zipc_hip_zlib_decompress_prefix_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ]),
+    ("zipc_hip_inflate_extent_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, C.c_int]),
+    ("zipc_hip_zlib_decompress_extent_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ]),
+    ("zipc_hip_inflate_size_extent_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
+    ("zipc_hip_zlib_size_extent_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
+    ("zipc_hip_inflate_size_extent_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
+    ("zipc_hip_zlib_size_extent_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
+    ("zipc_hip_inflate_extent", C.c_int, [_P, _P, _SZ, C.c_int, _SZ, _P, _SZ, C.c_int, _SZP, _SZP, _U32P]),
+    ("zipc_hip_zlib_decompress_extent", C.c_int, [_P, _P, _SZ, C.c_int, _SZ, _P, _SZ, _SZP, _SZP, _U32P]),
     ("zipc_hip_inflate_size_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_zlib_size_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_inflate_packed_batch", C.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _SZ, C.c_int, _P]),

@@ -21,6 +21,10 @@ assert DESC_DTYPE.itemsize == 48 and RESULT_DTYPE.itemsize == 16
 # zipc_hip_prefix_result: ended 1 -- the stream's final block ended within its room; 0 -- cut at dst_cap, or an error
 PREFIX_RESULT_DTYPE = np.dtype([("status", "<u4"), ("ended", "<u4"), ("out_len", "<u8")])
 assert PREFIX_RESULT_DTYPE.itemsize == 16
+# zipc_hip_extent_result: RESULT_DTYPE's fields, then src_used -- the source bytes the stream took (0 unless OK)
+EXTENT_RESULT_DTYPE = np.dtype([("status", "<u4"), ("checksum", "<u4"), ("out_len", "<u8"), ("src_used", "<u8"),
+                                ("reserved", "<u8")])
+assert EXTENT_RESULT_DTYPE.itemsize == 32
 # zipc_hip_recode_desc / zipc_hip_recode_result
 RECODE_DESC_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u8"), ("mid_off", "<u8"), ("mid_cap", "<u8"),
                               ("dst_off", "<u8"), ("dst_cap", "<u8"), ("limit", "<u8"), ("flags", "<u4"),
@@ -192,6 +196,75 @@ def zlib_size_blocks_batch(ctx: Context, src, descs_dev, results_dev, n_streams:
     """zipc_hip_zlib_size_blocks_batch: the same for whole zlib streams (zlib_size_batch's results)."""
     _sync_torch(src)
     st = lib().zipc_hip_zlib_size_blocks_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    ctx.synchronize()
+
+
+def extent_results_from_device(t) -> np.ndarray:
+    return t.cpu().numpy().view(EXTENT_RESULT_DTYPE).copy()
+
+
+def inflate_extent_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, max_dst_cap: int, crc_op: int,
+                         sync: bool = True):
+    """zipc_hip_inflate_extent_batch: inflate_batch's status, checksum, out_len and bytes for raw deflate streams whose
+    src_len is only an upper bound, and src_used -- the source bytes each OK stream took (0 otherwise).  results_dev: a
+    uint8 cuda tensor of EXTENT_RESULT_DTYPE records.  Always a wave per stream, whatever max_dst_cap; nothing is read back."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_inflate_extent_batch(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(),
+                                             results_dev.data_ptr(), n_streams, max_dst_cap, crc_op)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def zlib_decompress_extent_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, max_dst_cap: int,
+                                 sync: bool = True):
+    """zipc_hip_zlib_decompress_extent_batch: the same for whole zlib streams -- the trailer is found behind the body's
+    extent, not at src_len - 4 (CORRUPTED where it does not lie inside src_len); src_used counts header and trailer."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_zlib_decompress_extent_batch(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(),
+                                                     results_dev.data_ptr(), n_streams, max_dst_cap)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def inflate_size_extent_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int, sync: bool = True):
+    """zipc_hip_inflate_size_extent_batch: inflate_size_batch's results with src_used; no destination, nothing written."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_inflate_size_extent_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def zlib_size_extent_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int, sync: bool = True):
+    """zipc_hip_zlib_size_extent_batch: zlib_size_batch's results with src_used; no checksum is compared, the trailer must
+    still lie inside src_len."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_zlib_size_extent_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def inflate_size_extent_blocks_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int):
+    """zipc_hip_inflate_size_extent_blocks_batch: inflate_size_blocks_batch's results with src_used (Context.last_size_blocks
+    as there).  The call synchronises the context's stream."""
+    _sync_torch(src)
+    st = lib().zipc_hip_inflate_size_extent_blocks_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    ctx.synchronize()
+
+
+def zlib_size_extent_blocks_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int):
+    """zipc_hip_zlib_size_extent_blocks_batch: the same for whole zlib streams (zlib_size_extent_batch's results)."""
+    _sync_torch(src)
+    st = lib().zipc_hip_zlib_size_extent_blocks_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
     ctx.check(st)
     ctx.synchronize()
 
@@ -485,5 +558,7 @@ __all__ = ["DESC_DTYPE", "RESULT_DTYPE", "RECODE_DESC_DTYPE", "RECODE_RESULT_DTY
            "deflate_packed_batch", "zlib_compress_packed_batch", "deflate_packed_bound",
            "RANGE_DTYPE", "CHECKSUM_RESULT_DTYPE", "make_ranges", "checksum_results_from_device", "checksum_batch", "checksum_many",
            "PREFIX_RESULT_DTYPE", "inflate_prefix_batch", "zlib_decompress_prefix_batch", "prefix_results_from_device",
+           "EXTENT_RESULT_DTYPE", "extent_results_from_device", "inflate_extent_batch", "zlib_decompress_extent_batch",
+           "inflate_size_extent_batch", "zlib_size_extent_batch", "inflate_size_extent_blocks_batch", "zlib_size_extent_blocks_batch",
            "deflate_bound", "zlib_bound",
            "uniform_layout", "compact_descs", "OK"]

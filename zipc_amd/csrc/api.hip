@@ -319,7 +319,7 @@ void zipc_hip_destroy(zipc_hip_ctx *ctx) {
   free_buf(ctx->tok_scratch);
   free_buf(ctx->descs_marked);
   free_buf(ctx->size_descs); free_buf(ctx->size_head); free_buf(ctx->size_rest);
-  free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre); free_buf(ctx->prefix_adlers);
+  free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre); free_buf(ctx->prefix_adlers); free_buf(ctx->extent_inner);
   free_buf(ctx->recode_descs); free_buf(ctx->recode_res); free_buf(ctx->recode_verdicts);
   free_buf(ctx->packed_descs); free_buf(ctx->packed_res); free_buf(ctx->packed_verdicts);
   free_buf(ctx->dpacked_staging); free_buf(ctx->dpacked_descs); free_buf(ctx->dpacked_res);
@@ -439,6 +439,26 @@ int zipc_hip_inflate_size_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_aren
                                        zipc_hip_stream_result *d_results, size_t n_streams) {
   if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
   return launch_inflate_size_blocks(ctx, d_src_arena, d_descs, d_results, n_streams, nullptr);
+}
+
+// The extent forms (inflate_extent.h has the rule): the forms above with src_used in a 32-byte result
+int zipc_hip_inflate_extent_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                  zipc_hip_extent_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op) {
+  if (!ctx || !d_descs || !d_results) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (crc_op < 0 || crc_op > 3 || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  return launch_inflate_extent(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, max_dst_cap, crc_op);
+}
+
+int zipc_hip_inflate_size_extent_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                       zipc_hip_extent_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  return launch_inflate_size_extent(ctx, d_src_arena, d_descs, d_results, n_streams);
+}
+
+int zipc_hip_inflate_size_extent_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                              zipc_hip_extent_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  return launch_inflate_size_extent_blocks(ctx, d_src_arena, d_descs, d_results, n_streams, nullptr);
 }
 
 int zipc_hip_deflate_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
@@ -748,6 +768,58 @@ int zipc_hip_inflate_size(zipc_hip_ctx *ctx, const void *src, size_t len, int ha
   return ZIPC_HIP_OK;
 }
 
+// one host stream of unknown length through an extent batch form of one (zlib: the container's form), staged like one_stream
+static int one_stream_extent(zipc_hip_ctx *ctx, bool zlib, const void *src, size_t len, int has_limit, size_t limit, void *dst,
+                             size_t dst_cap, int crc_op, size_t *out_len, size_t *src_used, uint32_t *checksum) {
+  if (!ctx || (!src && len) || (!dst && dst_cap) || !out_len || !src_used) return ZIPC_HIP_ERR_INVALID_ARG;
+  *out_len = 0;
+  *src_used = 0;
+  if (checksum) *checksum = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int st = stage_in(ctx, src, len);
+  if (st) return st;
+  HIP_TRY(ctx, ctx->ensure(ctx->io_dst, dst_cap + 64));
+  HIP_TRY(ctx, ctx->ensure(ctx->io_desc, sizeof(StreamDesc)));
+  HIP_TRY(ctx, ctx->ensure(ctx->io_res, sizeof(ExtentResult)));
+  StreamDesc d;
+  memset(&d, 0, sizeof d);
+  d.src_off = 0; d.src_len = len; d.dst_off = 0; d.dst_cap = dst_cap;
+  d.limit = limit; d.flags = has_limit ? STREAM_HAS_LIMIT : 0;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->io_desc.p, &d, sizeof d, hipMemcpyHostToDevice, ctx->stream));
+  if (zlib)
+    st = zipc_hip_zlib_decompress_extent_batch(ctx, ctx->io_src.p, ctx->io_dst.p, (zipc_hip_stream_desc *)ctx->io_desc.p,
+                                               (zipc_hip_extent_result *)ctx->io_res.p, 1, dst_cap);
+  else
+    st = zipc_hip_inflate_extent_batch(ctx, ctx->io_src.p, ctx->io_dst.p, (zipc_hip_stream_desc *)ctx->io_desc.p,
+                                       (zipc_hip_extent_result *)ctx->io_res.p, 1, dst_cap, crc_op);
+  if (st) return st;
+  ExtentResult r;
+  HIP_TRY(ctx, hipMemcpyAsync(&r, ctx->io_res.p, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (r.status != ST_OK) {
+    if (checksum) *checksum = r.checksum;  // (ZIPC_HIP_ERR_CHECKSUM: the value found; 0 with every other status)
+    return (int)r.status;
+  }
+  if (r.out_len > dst_cap) return ZIPC_HIP_ERR_DST_TOO_SMALL;
+  if (r.out_len) {
+    HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->io_dst.p, r.out_len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  *out_len = r.out_len;
+  *src_used = r.src_used;
+  if (checksum) *checksum = r.checksum;
+  return ZIPC_HIP_OK;
+}
+
+int zipc_hip_inflate_extent(zipc_hip_ctx *ctx, const void *src, size_t len, int has_limit, size_t limit, void *dst, size_t dst_cap,
+                            int crc_op, size_t *out_len, size_t *src_used, uint32_t *checksum) {
+  return one_stream_extent(ctx, false, src, len, has_limit, limit, dst, dst_cap, crc_op, out_len, src_used, checksum);
+}
+int zipc_hip_zlib_decompress_extent(zipc_hip_ctx *ctx, const void *src, size_t len, int has_limit, size_t limit, void *dst,
+                                    size_t dst_cap, size_t *out_len, size_t *src_used, uint32_t *adler) {
+  return one_stream_extent(ctx, true, src, len, has_limit, limit, dst, dst_cap, 0, out_len, src_used, adler);
+}
+
 int zipc_hip_deflate(zipc_hip_ctx *ctx, const void *src, size_t len, int level, int crc_op, void *dst,
                      size_t dst_cap, size_t *out_len, uint32_t *checksum) {
   if (level < 0 || level > 3) return ZIPC_HIP_ERR_INVALID_ARG;
@@ -807,6 +879,43 @@ int zipc_hip_zlib_decompress_prefix_batch(zipc_hip_ctx *ctx, const void *d_src_a
                              zlib_crc_op(ctx), (uint32_t *)ctx->prefix_adlers.p);
   if (st) return st;
   return launch_zlib_close_prefix(ctx, d_results, n_streams);
+}
+
+// The zlib extent forms: open as ever (its `expect`, read at src_len - 4, is not used), the extent kernel over the bodies, and
+// zlib_container.h's zlib_close_extent, which finds the trailer behind the body's extent
+int zipc_hip_zlib_decompress_extent_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                          zipc_hip_extent_result *d_results, size_t n_streams, size_t max_dst_cap) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  ctx->last_inflate_blocks = 0;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = launch_zlib_open(ctx, d_src_arena, d_descs, n_streams, 0);
+  if (st) return st;
+  st = launch_inflate_extent(ctx, d_src_arena, d_dst_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, d_results, n_streams,
+                             max_dst_cap, zlib_crc_op(ctx));
+  if (st) return st;
+  return launch_zlib_close_extent(ctx, d_src_arena, d_descs, d_results, n_streams, 1);
+}
+int zipc_hip_zlib_size_extent_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                    zipc_hip_extent_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  ctx->last_size_blocks = 0;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = launch_zlib_open(ctx, d_src_arena, d_descs, n_streams, 0);
+  if (st) return st;
+  st = launch_inflate_size_extent(ctx, d_src_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, d_results, n_streams);
+  if (st) return st;
+  return launch_zlib_close_extent(ctx, d_src_arena, d_descs, d_results, n_streams, 0);
+}
+int zipc_hip_zlib_size_extent_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                           zipc_hip_extent_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  ctx->last_size_blocks = 0;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = launch_zlib_open(ctx, d_src_arena, d_descs, n_streams, 0);
+  if (st) return st;
+  st = launch_inflate_size_extent_blocks(ctx, d_src_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, d_results, n_streams, nullptr);
+  if (st) return st;
+  return launch_zlib_close_extent(ctx, d_src_arena, d_descs, d_results, n_streams, 0);
 }
 
 // ... with the long bodies sized by blocks: the same open and close around launch_inflate_size_blocks over the body descriptors

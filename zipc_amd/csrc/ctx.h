@@ -58,6 +58,7 @@ struct zipc_hip_ctx {
   Buf size_descs, size_head, size_rest;                      // sizing by blocks: the call's descriptors with no destination (dst_off 0, dst_cap the longest stream's), the heads' results and span slots, the one-wave results of the streams left
   Buf zlib_descs, zlib_pre;                       // the zlib batch forms: the descriptors the codec runs with, the container checks' verdicts (zlib.hip)
   Buf prefix_adlers;                              // the zlib prefix form: the Adler-32 of every stream that ended within its room (inflate.hip inflate_prefix_kernel)
+  Buf extent_inner;                               // the extent decode form with CRC-32: a StreamResult per stream for the checksum pass (inflate.hip launch_inflate_extent)
   Buf recode_descs, recode_res, recode_verdicts;  // the recode forms: the descriptors inflate, then deflate run with, their results, what is known of a stream between the steps (recode.hip)
   Buf packed_descs, packed_res, packed_verdicts;  // the packed decode forms: the descriptors inflate runs with, the sizing pass's results and then inflate's, the layout's verdicts (packed.hip)
   Buf dpacked_staging, dpacked_descs, dpacked_res;  // the packed encode forms: the staging arena of the slots, the descriptors deflate runs with, its results (deflate_packed.hip)
@@ -168,6 +169,17 @@ int launch_inflate_size(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_h
 // stream for the Adler-32 of those that ended (the zlib form)
 int launch_inflate_prefix(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
                           zipc_hip_prefix_result *d_results, size_t n_streams, int crc_op, uint32_t *d_adlers);
+// inflate.hip: the extent forms behind their argument checks (a ZIPC_HIP_* status each; inflate_extent.h has the rule).
+// launch_inflate_extent: inflate_extent_kernel, a wave per stream whatever max_dst_cap, one launch on ctx->cur, and for
+// ZIPC_HIP_CRC_CRC32 the checksum pass behind it; launch_inflate_size_extent: inflate_size_extent_kernel, one launch;
+// launch_inflate_size_extent_blocks: launch_inflate_size_blocks' path, decision for decision, with the extent forms of the
+// verdict and of the one wave -- it synchronises where that one does.
+int launch_inflate_extent(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                          zipc_hip_extent_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op);
+int launch_inflate_size_extent(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                               zipc_hip_extent_result *d_results, size_t n_streams);
+int launch_inflate_size_extent_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                      zipc_hip_extent_result *d_results, size_t n_streams, const StreamDesc *h_descs);
 // inflate.hip: zipc_hip_inflate_size_blocks_batch behind its argument checks: the call's long streams (forms.h size_blocks_pick)
 // by the block path's first half and a head walk, the rest by inflate_size_kernel's wave; h_descs: the caller's host copy of
 // the descriptors, or null: they are read back.  Synchronises ctx->stream unless no stream of the call is long.
@@ -205,6 +217,9 @@ int launch_zlib_close(zipc_hip_ctx *ctx, void *d_dst_arena, const zipc_hip_strea
                       size_t n, int compress, int level);
 int launch_zlib_close_size(zipc_hip_ctx *ctx, zipc_hip_stream_result *d_results, size_t n);
 int launch_zlib_close_prefix(zipc_hip_ctx *ctx, zipc_hip_prefix_result *d_results, size_t n);  // (the Adler-32s: ctx->prefix_adlers)
+// ... of the extent forms: d_descs the caller's (the trailer is read at 2 + the body's extent); compare 0: the sizing form's
+int launch_zlib_close_extent(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                             zipc_hip_extent_result *d_results, size_t n, int compare);
 // many.hip: the staging threads' pools, shared by the process's contexts (zipc_hip_create / zipc_hip_destroy)
 void many_pools_acquire();
 void many_pools_release();

@@ -51,6 +51,7 @@
 
 #include "ctx.h"
 #include "inflate_blocks.h"
+#include "inflate_extent.h"
 #include "inflate_find.h"
 #include "inflate_lane.h"
 #include "inflate_span.h"
@@ -648,13 +649,17 @@ __device__ __forceinline__ Explore no_explore() {
 // line, where the decode would go on behind it: the loop's services fill the queued copies first, copy it, and the wave
 // is done.  The result is a PrefixResult (inflate_prefix.h prefix_result); adler_out: where the Adler-32 of an ended
 // stream goes for the zlib form, or null.
-template <int MODE, bool MULTI = false, bool REUSE = false, bool HEAD = false, bool PREFIX = false>
+// EXTENT (with IM_REAL or IM_SIZE): the extent forms' wave (inflate_extent_kernel, inflate_size_extent_kernel) -- the plain
+// wave to its last instruction but the result store: an ExtentResult (inflate_extent.h extent_result) from the status, the
+// Adler-32, the length and the position the wave stands at, which is exactly behind the final block (see that header).
+template <int MODE, bool MULTI = false, bool REUSE = false, bool HEAD = false, bool PREFIX = false, bool EXTENT = false>
 __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t *__restrict__ src_arena, uint8_t *__restrict__ dst_arena,
                                                  const StreamDesc &sd, const BlockStart at, StreamResult *__restrict__ result,
                                                  uint16_t *__restrict__ span_idx, uint32_t *__restrict__ tok, int crc_op,
                                                  const Explore X = no_explore(), uint16_t *srcpos = nullptr,
                                                  uint32_t *__restrict__ adler_out = nullptr) {
   static_assert(!PREFIX || (MODE == IM_REAL && !MULTI && !REUSE && !HEAD), "the prefix form is the stream's plain wave");
+  static_assert(!EXTENT || ((MODE == IM_REAL || MODE == IM_SIZE) && !MULTI && !REUSE && !HEAD && !PREFIX), "the extent forms are the stream's plain wave");
   const int lane = threadIdx.x;
   const bool crc_adler = MODE == IM_REAL && (crc_op == CRC_ADLER32 || crc_op == CRC_ADLER32_RFC);
   const bool adler_rfc = crc_op == CRC_ADLER32_RFC;
@@ -976,6 +981,11 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
     }
     return e;
   }
+  if constexpr (EXTENT) {
+    if (writer || (MODE == IM_SIZE && lane == 0))
+      *(ExtentResult *)result = extent_result(d.status, crc_adler ? d.adler : 0u, d.out_pos, e.end_bit);
+    return e;
+  }
   if (MODE != IM_REAL && MODE != IM_SIZE) return e;
   if (writer || (MODE == IM_SIZE && lane == 0)) {
     StreamResult r;
@@ -1011,6 +1021,13 @@ __device__ __forceinline__ bool inflate_skips_stream(uint32_t flags, int &crc_op
     r.status = ST_INVALID_ARG; r.checksum = 0; r.out_len = 0;
     *result = r;
   }
+  return true;
+}
+
+// ... and of the extent forms, whose launches mark nothing: every bit but STREAM_HAS_LIMIT is an invalid argument
+__device__ __forceinline__ bool inflate_skips_stream(uint32_t flags, ExtentResult *result) {
+  if ((flags & ~STREAM_HAS_LIMIT) == 0) return false;
+  if ((threadIdx.x & 63u) == 0) *result = extent_result(ST_INVALID_ARG, 0, 0, 0);
   return true;
 }
 
@@ -1085,6 +1102,51 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   inflate_wave<IM_REAL, false, false, false, true>(lds_raw, src_arena, dst_arena, descs[stream], at, (StreamResult *)(results + stream),
                                                    span_scratch + (size_t)stream * SPAN_IDX_ENTRIES, nullptr, crc_op, no_explore(), nullptr,
                                                    adlers != nullptr ? adlers + stream : nullptr);
+}
+// The extent forms: the stream's wave as inflate_batch_kernel runs it, with the result an ExtentResult (EXTENT, inflate_wave):
+// what that kernel reports for the same descriptor, and on ST_OK the source bytes up to the end of the final block.  One
+// kernel for every call size, always a wave per stream.  inner: null, or a StreamResult per stream for the CRC-32 pass
+// behind the kernel (status and length as crc32_pass reads them; extent_put_crc_kernel brings its checksum back).
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void inflate_extent_kernel(const uint8_t *__restrict__ src_arena,
+                                                           uint8_t *__restrict__ dst_arena,
+                                                           const StreamDesc *__restrict__ descs,
+                                                           ExtentResult *__restrict__ results,
+                                                           uint32_t n_streams, uint16_t *__restrict__ span_scratch, int crc_op,
+                                                           StreamResult *__restrict__ inner) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LDS_BYTES_PER_LANE];
+  const uint32_t stream = blockIdx.x;
+  if (stream >= n_streams) return;
+  StreamResult in;
+  in.status = ST_INVALID_ARG; in.checksum = 0; in.out_len = 0;
+  if (!inflate_skips_stream(descs[stream].flags, results + stream)) {
+    BlockStart at;
+    at.bit = 0; at.out_pos = 0; at.chunk0 = 0;
+    const BlockEnd e = inflate_wave<IM_REAL, false, false, false, false, true>(lds_raw, src_arena, dst_arena, descs[stream], at,
+                                                                               (StreamResult *)(results + stream),
+                                                                               span_scratch + (size_t)stream * SPAN_IDX_ENTRIES, nullptr, crc_op);
+    in.status = e.status;
+    in.out_len = e.status == ST_OK ? e.out_len : 0u;
+  }
+  if (inner != nullptr && threadIdx.x == 0) inner[stream] = in;
+}
+// ... and the sizing form: inflate_size_kernel's wave (IM_SIZE: no arena but the source is touched), checksum 0
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void inflate_size_extent_kernel(const uint8_t *__restrict__ src_arena, const StreamDesc *__restrict__ descs,
+                                                                 ExtentResult *__restrict__ results, uint32_t n_streams,
+                                                                 uint16_t *__restrict__ span_scratch) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LDS_BYTES_PER_LANE];
+  const uint32_t stream = blockIdx.x;
+  if (stream >= n_streams) return;
+  if (inflate_skips_stream(descs[stream].flags, results + stream)) return;
+  BlockStart at;
+  at.bit = 0; at.out_pos = 0; at.chunk0 = 0;
+  inflate_wave<IM_SIZE, false, false, false, false, true>(lds_raw, src_arena, nullptr, descs[stream], at, (StreamResult *)(results + stream),
+                                                          span_scratch + (size_t)stream * SPAN_IDX_ENTRIES, nullptr, CRC_NOP);
+}
+// what the checksum pass left in inner[i], into the stream's ExtentResult (inflate_extent.h extent_with_crc): the CRC-32 of an
+// OK stream, or the pass's own refusal of one whose output is longer than the call's max_dst_cap
+__global__ __launch_bounds__(256) void extent_put_crc_kernel(const StreamResult *__restrict__ inner, ExtentResult *__restrict__ results, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) results[i] = extent_with_crc(results[i], inner[i].status, inner[i].checksum);
 }
 
 
@@ -1692,6 +1754,31 @@ __global__ __launch_bounds__(64) void inflate_size_scatter_kernel(const StreamRe
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < n) results[streams[k]] = listed[k];
 }
+// The extent form of the two (zipc_hip_inflate_size_extent_blocks_batch): the same verdict, to the letter, and with it the
+// bit behind the final block -- the head's own end where it saw that block, else the end of the chain's last block, which
+// chain_ok says is the final one (inflate_extent.h size_blocks_end_bit); the rest go through inflate_size_extent_kernel.
+// Kernels of their own: inflate_size_kernel's and the verdict's compiled code stay as they are.
+__global__ __launch_bounds__(64) void inflate_size_extent_verdict_kernel(const BlocksJob *__restrict__ jobs, const BlockEnd *__restrict__ heads,
+                                                                        ExtentResult *__restrict__ results, uint32_t *__restrict__ sized,
+                                                                        uint32_t n_jobs) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_jobs) return;
+  const BlocksJob J = jobs[j];
+  const BlockEnd h = heads[j];
+  const FindCounts c = *J.counts;
+  const uint32_t n_blocks = c.chain_ok && c.n_blocks <= J.chain_cap ? c.n_blocks : 0u;
+  const int at = n_blocks ? size_chain_at(J.chain, n_blocks, h.end_bit, h.out_len) : SIZE_CHAIN_NONE;
+  const SizeVerdict v = size_blocks_verdict(h.status, h.final_block, h.out_len, c.chain_ok, at, c.out_len);
+  sized[j] = v.sized ? (h.final_block ? h.pad : n_blocks) : 0u;
+  if (!v.sized) return;
+  const uint64_t chain_last = n_blocks ? J.chain_end[n_blocks - 1u].end_bit : 0ull;
+  results[J.stream] = extent_result(ST_OK, 0, v.out_len, size_blocks_end_bit(h.final_block, h.end_bit, chain_last));
+}
+__global__ __launch_bounds__(64) void inflate_size_extent_scatter_kernel(const ExtentResult *__restrict__ listed, const uint32_t *__restrict__ streams,
+                                                                        ExtentResult *__restrict__ results, uint32_t n) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n) results[streams[k]] = listed[k];
+}
 
 // every byte of a match takes the literal its chain of sources ends in (tok[i] after the resolve rounds; a literal's is i).
 // (Four bytes a thread -- one load of their four words, one word stored -- takes the same 0.21-0.23 ms per 64 MiB of text: the
@@ -2282,6 +2369,47 @@ int launch_inflate_prefix(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_ds
   return ZIPC_HIP_OK;
 }
 
+// zipc_hip_inflate_extent_batch behind its argument checks, and the zlib form's middle step (ctx.h): inflate_extent_kernel, a
+// wave per stream whatever max_dst_cap, one launch on the context's stream, nothing read back; ZIPC_HIP_CRC_CRC32: the checksum
+// pass over the produced bytes behind it, as inflate_batch_one_wave runs it, over a StreamResult per stream of the context's.
+int launch_inflate_extent(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                          zipc_hip_extent_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op) {
+  ctx->last_inflate_blocks = 0;  // (zipc_hip_last_inflate_blocks: no stream of this call goes by blocks)
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_streams * INFLATE_SCRATCH_PER_STREAM));
+  StreamResult *inner = nullptr;
+  if (crc_op == ZIPC_HIP_CRC_CRC32) {
+    if (n_streams * crc32_segs(max_dst_cap) > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+    HIP_TRY(ctx, ctx->ensure(ctx->extent_inner, n_streams * sizeof(StreamResult)));
+    inner = (StreamResult *)ctx->extent_inner.p;
+  }
+  ZD_LAUNCH(ctx, "inflate_extent", inflate_extent_kernel, dim3((unsigned)n_streams), dim3(64), 0, (const uint8_t *)d_src_arena,
+            (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs, (ExtentResult *)d_results, (uint32_t)n_streams,
+            (uint16_t *)ctx->inflate_scratch.p, crc_op, inner);
+  HIP_TRY(ctx, hipGetLastError());
+  if (inner == nullptr) return ZIPC_HIP_OK;
+  if (const int st = crc32_pass(ctx, (const uint8_t *)d_dst_arena, RANGE_INFLATE_OUT, (const StreamDesc *)d_descs, inner, n_streams, 0, 0,
+                                max_dst_cap, nullptr))
+    return st;
+  ZD_LAUNCH(ctx, "extent_put_crc", extent_put_crc_kernel, dim3((unsigned)((n_streams + 255) / 256)), dim3(256), 0,
+            (const StreamResult *)inner, (ExtentResult *)d_results, (uint32_t)n_streams);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+// zipc_hip_inflate_size_extent_batch behind its argument checks (ctx.h): one launch, a wave per stream, on the context's stream
+int launch_inflate_size_extent(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                               zipc_hip_extent_result *d_results, size_t n_streams) {
+  ctx->last_size_blocks = 0;  // (zipc_hip_last_size_blocks: every stream by its one wave)
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_streams * INFLATE_SCRATCH_PER_STREAM));
+  ZD_LAUNCH(ctx, "inflate_size_extent", inflate_size_extent_kernel, dim3((unsigned)n_streams), dim3(64), 0, (const uint8_t *)d_src_arena,
+            (const StreamDesc *)d_descs, (ExtentResult *)d_results, (uint32_t)n_streams, (uint16_t *)ctx->inflate_scratch.p);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+
 // A group of a sizing call's long streams by the front alone, over `dd`, the library's copy of the descriptors with dst_off 0
 // and dst_cap MAX_STREAM_LEN (the chain's room is then min(limit, MAX_STREAM_LEN), and dst_arena + dst_off, which IM_DRY
 // forms and never goes through, is null) -- with the head beside it on a queue of its own, and the verdict behind both.
@@ -2292,8 +2420,9 @@ int launch_inflate_prefix(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_ds
 // IM_REAL's; span_decode's tile stores are im_stores, its loads of match sources IM_REAL (the "fly" loads) or behind a
 // count of holes that only IM_REAL raises, the token pass IM_TOKEN.
 // sized[stream]: blocks of what sized it, 0: left to the one wave.  SYNCHRONISES the context's stream.
-static int inflate_size_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, const StreamDesc *dd, StreamResult *d_results,
-                                     const StreamDesc *sds, const uint32_t *streams, size_t nj, uint32_t *sized) {
+// extent: d_results are ExtentResults and the verdict is inflate_size_extent_verdict_kernel's (else StreamResults).
+static int inflate_size_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, const StreamDesc *dd, void *d_results,
+                                     const StreamDesc *sds, const uint32_t *streams, size_t nj, uint32_t *sized, bool extent) {
   BlocksRun run(ctx, nj);
   // (no room for the lists, or for the heads: the streams' one waves need none)
   if (!run.set_up(sds, streams)) return ZIPC_HIP_OK;
@@ -2323,8 +2452,12 @@ static int inflate_size_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, cons
   std::vector<uint32_t> all(nj);
   for (size_t j = 0; j < nj; j++) all[j] = (uint32_t)j;
   HIP_TRY(ctx, run.hand(all));
-  ZD_LAUNCH(ctx, "inflate_size_verdict", inflate_size_verdict_kernel, dim3((ny + 63u) / 64u), dim3(64), 0, (const BlocksJob *)run.d_jobs,
-            (const BlockEnd *)d_heads, d_results, d_sized, (uint32_t)nj);
+  if (extent)
+    ZD_LAUNCH(ctx, "inflate_size_extent_verdict", inflate_size_extent_verdict_kernel, dim3((ny + 63u) / 64u), dim3(64), 0,
+              (const BlocksJob *)run.d_jobs, (const BlockEnd *)d_heads, (ExtentResult *)d_results, d_sized, (uint32_t)nj);
+  else
+    ZD_LAUNCH(ctx, "inflate_size_verdict", inflate_size_verdict_kernel, dim3((ny + 63u) / 64u), dim3(64), 0, (const BlocksJob *)run.d_jobs,
+              (const BlockEnd *)d_heads, (StreamResult *)d_results, d_sized, (uint32_t)nj);
   std::vector<uint32_t> got(nj);
   HIP_TRY(ctx, hipMemcpyAsync(got.data(), d_sized, nj * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the lists handed to the copies go with this frame)
@@ -2338,16 +2471,22 @@ static int inflate_size_blocks_group(zipc_hip_ctx *ctx, const uint8_t *src, cons
 // inflate_batch_kernel does for the decode.  The block path reports no error status of its own.
 // h_descs: fetch_descs.  SYNCHRONISES the context's stream
 // (ZIPC_HIP_INFLATE_BLOCKS=0, or a call without a long stream: launch_inflate_size and nothing else).
-int launch_inflate_size_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
-                               size_t n_streams, const StreamDesc *h_descs) {
+// extent: the call is zipc_hip_inflate_size_extent_blocks_batch's -- d_results are ExtentResults, written by the extent forms
+// of the verdict, the one wave and the scatter; every decision of the path is the same.
+static int size_blocks_call(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, void *d_results,
+                            size_t n_streams, const StreamDesc *h_descs, bool extent) {
+  const auto one_waves = [&]() {
+    return extent ? launch_inflate_size_extent(ctx, d_src_arena, d_descs, (zipc_hip_extent_result *)d_results, n_streams)
+                  : launch_inflate_size(ctx, d_src_arena, d_descs, (zipc_hip_stream_result *)d_results, n_streams);
+  };
   ctx->last_size_blocks = 0;
   if (n_streams == 0) return ZIPC_HIP_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!tuning().inflate_blocks || n_streams > BLOCKS_MAX_STREAMS) return launch_inflate_size(ctx, d_src_arena, d_descs, d_results, n_streams);
+  if (!tuning().inflate_blocks || n_streams > BLOCKS_MAX_STREAMS) return one_waves();
   std::vector<StreamDesc> sds;
   if (const int st = fetch_descs(ctx, d_descs, n_streams, h_descs, sds)) return st;
   const std::vector<uint32_t> picked = size_blocks_pick(sds.data(), n_streams);
-  if (picked.empty()) return launch_inflate_size(ctx, d_src_arena, d_descs, d_results, n_streams);
+  if (picked.empty()) return one_waves();
   // the descriptors every kernel of this call runs with: sizing is "dst_cap = MAX_STREAM_LEN", and the caller's dst_off
   // and dst_cap are not looked at
   for (StreamDesc &sd : sds) { sd.dst_off = 0; sd.dst_cap = MAX_STREAM_LEN; }
@@ -2356,8 +2495,8 @@ int launch_inflate_size_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, const
   std::vector<uint32_t> sized(n_streams, 0);
   size_t begin = 0;
   for (size_t end : size_blocks_groups(sds.data(), picked, tuning().explore_stride)) {
-    const int st = inflate_size_blocks_group(ctx, (const uint8_t *)d_src_arena, (const StreamDesc *)ctx->size_descs.p, (StreamResult *)d_results,
-                                             sds.data(), picked.data() + begin, end - begin, sized.data());
+    const int st = inflate_size_blocks_group(ctx, (const uint8_t *)d_src_arena, (const StreamDesc *)ctx->size_descs.p, d_results,
+                                             sds.data(), picked.data() + begin, end - begin, sized.data(), extent);
     if (st) return st;
     begin = end;
   }
@@ -2372,21 +2511,36 @@ int launch_inflate_size_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, const
   if (nr == 0) return ZIPC_HIP_OK;
   std::vector<StreamDesc> rest_descs(nr);
   for (size_t k = 0; k < nr; k++) rest_descs[k] = sds[rest[k]];
-  const size_t idx_at = align_up(nr * sizeof(StreamResult), 256);
+  const size_t idx_at = align_up(nr * (extent ? sizeof(ExtentResult) : sizeof(StreamResult)), 256);
   HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, nr * INFLATE_SCRATCH_PER_STREAM));
   HIP_TRY(ctx, ctx->ensure(ctx->descs_marked, nr * sizeof(StreamDesc)));
   HIP_TRY(ctx, ctx->ensure(ctx->size_rest, idx_at + nr * sizeof(uint32_t)));
-  StreamResult *d_listed = (StreamResult *)ctx->size_rest.p;
+  void *d_listed = ctx->size_rest.p;
   uint32_t *d_idx = (uint32_t *)((uint8_t *)ctx->size_rest.p + idx_at);
   HIP_TRY(ctx, hipMemcpyAsync(ctx->descs_marked.p, rest_descs.data(), nr * sizeof(StreamDesc), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_idx, rest.data(), nr * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-  ZD_LAUNCH(ctx, "inflate_size", inflate_size_kernel, dim3((unsigned)nr), dim3(64), 0, (const uint8_t *)d_src_arena,
-            (const StreamDesc *)ctx->descs_marked.p, d_listed, (uint32_t)nr, (uint16_t *)ctx->inflate_scratch.p);
-  ZD_LAUNCH(ctx, "inflate_size_scatter", inflate_size_scatter_kernel, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, (const StreamResult *)d_listed,
-            (const uint32_t *)d_idx, (StreamResult *)d_results, (uint32_t)nr);
+  if (extent) {
+    ZD_LAUNCH(ctx, "inflate_size_extent", inflate_size_extent_kernel, dim3((unsigned)nr), dim3(64), 0, (const uint8_t *)d_src_arena,
+              (const StreamDesc *)ctx->descs_marked.p, (ExtentResult *)d_listed, (uint32_t)nr, (uint16_t *)ctx->inflate_scratch.p);
+    ZD_LAUNCH(ctx, "inflate_size_extent_scatter", inflate_size_extent_scatter_kernel, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0,
+              (const ExtentResult *)d_listed, (const uint32_t *)d_idx, (ExtentResult *)d_results, (uint32_t)nr);
+  } else {
+    ZD_LAUNCH(ctx, "inflate_size", inflate_size_kernel, dim3((unsigned)nr), dim3(64), 0, (const uint8_t *)d_src_arena,
+              (const StreamDesc *)ctx->descs_marked.p, (StreamResult *)d_listed, (uint32_t)nr, (uint16_t *)ctx->inflate_scratch.p);
+    ZD_LAUNCH(ctx, "inflate_size_scatter", inflate_size_scatter_kernel, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, (const StreamResult *)d_listed,
+              (const uint32_t *)d_idx, (StreamResult *)d_results, (uint32_t)nr);
+  }
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the lists go with this frame)
   return ZIPC_HIP_OK;
+}
+int launch_inflate_size_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                               size_t n_streams, const StreamDesc *h_descs) {
+  return size_blocks_call(ctx, d_src_arena, d_descs, d_results, n_streams, h_descs, false);
+}
+int launch_inflate_size_extent_blocks(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                      zipc_hip_extent_result *d_results, size_t n_streams, const StreamDesc *h_descs) {
+  return size_blocks_call(ctx, d_src_arena, d_descs, d_results, n_streams, h_descs, true);
 }
 
 // zipc_hip_inflate_batch behind its argument checks (ctx.h)

@@ -9,6 +9,8 @@
 //   zlib_close_size_kernel  the same behind inflate's size kernel (zipc_hip_zlib_size_batch): the verdict, or the body's size.
 //   zlib_close_prefix_kernel  the same behind inflate's prefix kernel (zipc_hip_zlib_decompress_prefix_batch): an ended stream's
 //                      Adler-32 compared, a cut one's not.
+//   zlib_close_extent_kernel, zlib_close_size_extent_kernel  the same behind inflate's extent kernels (zipc_hip_zlib_decompress_extent_batch,
+//                      zipc_hip_zlib_size_extent_batch): the trailer found behind the body's extent, not at src_len - 4.
 // The rules themselves are zlib_container.h's (the host forms and the tests compile the same functions).  Nothing is
 // read back: the calls enqueue and return like the raw batch forms.  The launches at the end of this file are the one
 // way to the kernels (ctx.h).
@@ -103,6 +105,24 @@ __global__ __launch_bounds__(256) void zlib_close_prefix_kernel(const ZlibPre *_
   results[i] = zlib_close_prefix(pre[i].status, pre[i].expect, adlers[i], results[i]);
 }
 
+// The extent forms' closes, a lane per stream: src_len is only a bound, so zlib_open_kernel's `expect` (read at src_len - 4)
+// is not used; the trailer is read from the source arena at 2 + u, u the body's extent, if it lies inside the declared
+// bytes (zlib_container.h zlib_close_extent).  The sizing form compares nothing and holds the same bound.
+__global__ __launch_bounds__(256) void zlib_close_extent_kernel(const uint8_t *__restrict__ src_arena, const StreamDesc *__restrict__ descs,
+                                                                const ZlibPre *__restrict__ pre, ExtentResult *__restrict__ results,
+                                                                uint32_t n_streams) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_streams) return;
+  results[i] = zlib_close_extent(pre[i].status, descs[i].src_len, src_arena + descs[i].src_off, results[i], true);
+}
+__global__ __launch_bounds__(256) void zlib_close_size_extent_kernel(const uint8_t *__restrict__ src_arena, const StreamDesc *__restrict__ descs,
+                                                                     const ZlibPre *__restrict__ pre, ExtentResult *__restrict__ results,
+                                                                     uint32_t n_streams) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_streams) return;
+  results[i] = zlib_close_extent(pre[i].status, descs[i].src_len, src_arena + descs[i].src_off, results[i], false);
+}
+
 int zlib_crc_op(const zipc_hip_ctx *ctx) { return ctx->adler_rfc1950 ? ZIPC_HIP_CRC_ADLER32_RFC1950 : ZIPC_HIP_CRC_ADLER32; }
 
 // zlib_open_kernel over the caller's descriptors: the codec's descriptors and the checks' verdicts, in the context's scratch
@@ -132,6 +152,18 @@ int launch_zlib_close_size(zipc_hip_ctx *ctx, zipc_hip_stream_result *d_results,
 int launch_zlib_close_prefix(zipc_hip_ctx *ctx, zipc_hip_prefix_result *d_results, size_t n) {
   ZD_LAUNCH(ctx, "zlib_close_prefix", zlib_close_prefix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
             (const ZlibPre *)ctx->zlib_pre.p, (const uint32_t *)ctx->prefix_adlers.p, (PrefixResult *)d_results, (uint32_t)n);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+
+int launch_zlib_close_extent(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                             zipc_hip_extent_result *d_results, size_t n, int compare) {
+  if (compare)
+    ZD_LAUNCH(ctx, "zlib_close_extent", zlib_close_extent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint8_t *)d_src_arena,
+              (const StreamDesc *)d_descs, (const ZlibPre *)ctx->zlib_pre.p, (ExtentResult *)d_results, (uint32_t)n);
+  else
+    ZD_LAUNCH(ctx, "zlib_close_size_extent", zlib_close_size_extent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+              (const uint8_t *)d_src_arena, (const StreamDesc *)d_descs, (const ZlibPre *)ctx->zlib_pre.p, (ExtentResult *)d_results, (uint32_t)n);
   HIP_TRY(ctx, hipGetLastError());
   return ZIPC_HIP_OK;
 }

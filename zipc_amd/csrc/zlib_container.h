@@ -8,6 +8,7 @@
 //   * into tests/zlib_sim/sim_zlib.cpp with g++, where tests/test_zlib_rules.py holds every (CMF, FLG) pair to the oracle.
 #pragma once
 
+#include "inflate_extent.h"
 #include "inflate_prefix.h"
 #include "zd_common.h"
 
@@ -86,6 +87,26 @@ ZD_HD StreamResult zlib_close_size(uint32_t pre, StreamResult inner) {
 ZD_HD PrefixResult zlib_close_prefix(uint32_t pre, uint32_t expect, uint32_t adler, PrefixResult inner) {
   if (pre != ST_OK) { inner.status = pre; inner.ended = 0; inner.out_len = 0; }
   else if (inner.status == ST_OK && inner.ended != 0 && adler != expect) { inner.status = ST_CHECKSUM; inner.ended = 0; inner.out_len = 0; }
+  return inner;
+}
+// A zlib stream of unknown length (zipc_hip_zlib_decompress_extent_batch, zipc_hip_zlib_size_extent_batch): src_len is an
+// upper bound, so the trailer is not at src_len - 4.  The body handed to the codec is still [2, src_len - 2); with u the
+// body's extent (inner.src_used) the trailer is the four bytes at 2 + u of the stream, and it has to lie inside the
+// declared bytes: 2 + u + 4 > src_len is ST_CORRUPTED with nothing read or compared.  `stream`: the stream's first byte;
+// only [2 + u, 2 + u + 4) is read, and only when `compare` (the sizing form compares nothing, like zlib_close_size, but
+// holds the same bound, so that a stream it sizes OK has the src_used the decode form reports).  The Adler-32 is compared
+// as zlib_close_decompress compares it; a mismatch reports the value found and no bytes.  OK: the whole stream, 6 more.
+ZD_HD ExtentResult zlib_close_extent(uint32_t pre, uint64_t src_len, const uint8_t *stream, ExtentResult inner, bool compare) {
+  if (pre != ST_OK) return extent_result(pre, 0, 0, 0);
+  if (inner.status != ST_OK) return extent_result(inner.status, 0, 0, 0);
+  const uint64_t u = inner.src_used;
+  if (2u + u + 4u > src_len) return extent_result(ST_CORRUPTED, 0, 0, 0);
+  if (!compare) inner.checksum = 0;
+  else if (inner.checksum != zlib_expect(stream + 2u + u)) {
+    inner.status = ST_CHECKSUM; inner.out_len = 0; inner.src_used = 0;
+    return inner;
+  }
+  inner.src_used = u + 6u;
   return inner;
 }
 // zlib_compress: `inner` is deflate's, the result counts the container's bytes too.  *wrap: the caller has to put the

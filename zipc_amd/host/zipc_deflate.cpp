@@ -212,6 +212,50 @@ Result<std::pair<std::string, Adler_32::t>> inflate_and_adler_32(const std::stri
   return R::Ok({std::move(out), c});
 }
 
+// the two extent values: one loop around zipc_hip_inflate_extent / zipc_hip_zlib_decompress_extent, the buffer doubled while
+// the library answers DST_TOO_SMALL without ?decompressed_size, as in inflate_raw
+static Result<std::pair<std::string, std::size_t>> extent_raw(bool zlib, const std::string &s,
+                                                              std::optional<std::size_t> decompressed_size, std::size_t start,
+                                                              std::size_t len) {
+  typedef Result<std::pair<std::string, std::size_t>> R;
+  const auto r = range(s, start, len);
+  const char *p = s.data() + r.first;
+  const std::size_t n = r.second;
+  std::size_t cap = decompressed_size ? *decompressed_size : (3 * n < 1024 ? 1024 : 3 * n);
+  std::string out;
+  for (;;) {
+    out.resize(cap);
+    std::size_t out_len = 0, used = 0;
+    uint32 c = 0;
+    const int has_limit = decompressed_size ? 1 : 0;
+    const std::size_t limit = decompressed_size ? *decompressed_size : 0;
+    const int st = zlib ? zipc_hip_zlib_decompress_extent(context(), p, n, has_limit, limit, cap ? &out[0] : nullptr, cap, &out_len, &used, &c)
+                        : zipc_hip_inflate_extent(context(), p, n, has_limit, limit, cap ? &out[0] : nullptr, cap, ZIPC_HIP_CRC_NOP,
+                                                  &out_len, &used, &c);
+    if (st == ZIPC_HIP_ERR_DST_TOO_SMALL && !decompressed_size) {
+      cap = cap < 1024 ? 2048 : cap * 2;
+      continue;
+    }
+    throw_if_library_failure(st);
+    if (st == ZIPC_HIP_ERR_ZLIB_METHOD) {
+      char b[64];
+      snprintf(b, sizeof b, "Unknown compression method (%d)", (int)((unsigned char)p[0] & 0x0F));
+      return R::Error(b);
+    }
+    if (st) return R::Error(message(st));
+    out.resize(out_len);
+    return R::Ok({std::move(out), used});
+  }
+}
+Result<std::pair<std::string, std::size_t>> inflate_extent(const std::string &s, std::optional<std::size_t> decompressed_size,
+                                                           std::size_t start, std::size_t len) {
+  return extent_raw(false, s, decompressed_size, start, len);
+}
+Result<std::pair<std::string, std::size_t>> zlib_decompress_extent(const std::string &s, std::optional<std::size_t> decompressed_size,
+                                                                   std::size_t start, std::size_t len) {
+  return extent_raw(true, s, decompressed_size, start, len);
+}
+
 ZlibResult zlib_decompress(const std::string &s, std::optional<std::size_t> decompressed_size, std::size_t start,
                            std::size_t len) {
   const auto r = range(s, start, len);

@@ -107,6 +107,17 @@ struct ZlibResult {
 ZlibResult zlib_decompress(const std::string &s, std::optional<std::size_t> decompressed_size = std::nullopt,
                            std::size_t start = 0, std::size_t len = npos);
 
+// ADDITIONS the reference's signature does not have: streams whose compressed length is not known.  The range (start, len,
+// checked as ever) is an upper bound of the stream; Ok carries the bytes and the count of source bytes, from start on, that
+// the stream took (zipc_hip_inflate_extent / zipc_hip_zlib_decompress_extent: a zlib stream's count includes its header and
+// its Adler-32, which is compared).  The next stream of a run stored back to back begins at start + used.
+Result<std::pair<std::string, std::size_t>> inflate_extent(const std::string &s,
+                                                           std::optional<std::size_t> decompressed_size = std::nullopt,
+                                                           std::size_t start = 0, std::size_t len = npos);
+Result<std::pair<std::string, std::size_t>> zlib_decompress_extent(const std::string &s,
+                                                                   std::optional<std::size_t> decompressed_size = std::nullopt,
+                                                                   std::size_t start = 0, std::size_t len = npos);
+
 enum class level { None = 0, Fast = 1, Default = 2, Best = 3 };  // zipc_deflate.mli:123-125
 
 // zipc_deflate.mli:128-162

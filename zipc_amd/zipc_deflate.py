@@ -216,6 +216,47 @@ def zlib_decompress(s, decompressed_size=None, start=0, len=None, ctx=None):
         return Error((None, _message(st, data[0] & 0x0F if n else 0)))
 
 
+def _extent(zlib, s, decompressed_size, start, length, crc_op, ctx):
+    data = _range(s, start, length)
+    ctx = ctx or default_context()
+    n = data.__len__()
+    has_limit = decompressed_size is not None
+    cap = decompressed_size if has_limit else max(3 * n, 1024)
+    while True:
+        dst = C.create_string_buffer(max(cap, 1))
+        out_len, used, crc = C.c_size_t(), C.c_size_t(), C.c_uint32()
+        if zlib:
+            st = lib().zipc_hip_zlib_decompress_extent(ctx.handle, data, n, int(has_limit), decompressed_size or 0, dst, cap,
+                                                       C.byref(out_len), C.byref(used), C.byref(crc))
+        else:
+            st = lib().zipc_hip_inflate_extent(ctx.handle, data, n, int(has_limit), decompressed_size or 0, dst, cap, crc_op,
+                                               C.byref(out_len), C.byref(used), C.byref(crc))
+        if st == ERR_DST_TOO_SMALL and not has_limit:
+            cap *= 2
+            continue
+        if st == OK:
+            return Ok((dst.raw[:out_len.value], used.value, crc.value))
+        if st in (_lib.ERR_HIP, _lib.ERR_INVALID_ARG, _lib.ERR_NO_DEVICE, _lib.ERR_NOMEM):
+            ctx.check(st)
+        return Error(_message(st, data[0] & 0x0F if n else 0) if zlib else _message(st))
+
+
+def inflate_extent(s, decompressed_size=None, start=0, len=None, ctx=None):
+    """An addition the reference's signature does not have: `inflate` of a stream whose compressed length is not known.
+    The range (?start ?len, checked as ever) is an upper bound of the stream; Ok (bytes, used) | Error msg, `used` the
+    count of source bytes from `start` that the stream took (zipc_hip_inflate_extent).  The next stream of a run stored
+    back to back begins at start + used."""
+    r = _extent(False, s, decompressed_size, start, len, CRC_NOP, ctx)
+    return Ok(r.value[:2]) if r.is_ok() else r
+
+
+def zlib_decompress_extent(s, decompressed_size=None, start=0, len=None, ctx=None):
+    """The same for a zlib stream (an addition, too): Ok (bytes, used) | Error msg, `used` counting the two header bytes
+    and the Adler-32, which is found behind the deflate stream's own end and compared (zipc_hip_zlib_decompress_extent)."""
+    r = _extent(True, s, decompressed_size, start, len, CRC_NOP, ctx)
+    return Ok(r.value[:2]) if r.is_ok() else r
+
+
 def _level(level):
     if level is None:
         return LEVELS["best"]  # make_encoder ?(level = `Best) zipc_deflate.ml:817
