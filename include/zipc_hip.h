@@ -562,6 +562,89 @@ int zipc_hip_zlib_decompress_extent(zipc_hip_ctx *ctx, const void *src, size_t l
                                     void *dst, size_t dst_cap, size_t *out_len, size_t *src_used,
                                     uint32_t *adler);
 
+/* GZIP MEMBERS (RFC 1952): .gz files, HTTP bodies, and BGZF (bgzip, BAM, tabix) -- a file of back-to-back members of at
+ * most 64 KiB each, every one carrying its own length in an extra field.  The reference has no gzip; the rules are RFC
+ * 1952's as zlib reads them, in csrc/gzip_container.h.  A member's length is not known up front, so the forms below are
+ * the extent forms above between an open and a close of a lane per member.  Nothing of an existing form changes.
+ * The defining properties:
+ *   - for an OK member, zipc_hip_inflate_batch over [src_off + hdr_len, src_off + src_used - 8) with ZIPC_HIP_CRC_CRC32
+ *     gives the same bytes, length and checksum;
+ *   - a member produced by zipc_hip_gzip_compress_batch is ten (BGZF: eighteen) header bytes, then exactly the bytes
+ *     zipc_hip_deflate_batch writes for that source and level, then the trailer.
+ * The header (src_len: any upper bound of the member's length inside the arena; every index is checked against it before
+ * it is read), in this order: src_len < 18 is ZIPC_HIP_ERR_CORRUPTED and nothing is read; ID1, ID2 other than 1f 8b
+ * CORRUPTED; CM other than 8 ZIPC_HIP_ERR_ZLIB_METHOD; a reserved bit of FLG (0xE0) CORRUPTED, FTEXT is ignored; FEXTRA:
+ * XLEN and its bytes inside src_len or CORRUPTED -- the first subfield 'B','C' of length 2 is BGZF's BSIZE, a subfield that
+ * overruns XLEN ends the walk and is no error; FNAME, then FCOMMENT: the zero inside src_len and at most 65 535 bytes in
+ * front of it or CORRUPTED -- a LIMIT OF THIS LIBRARY (zlib scans without bound) that keeps a lane's walk over a hostile
+ * member bounded; FHCRC: the low 16 bits of the CRC-32 of the header bytes in front of it, or CORRUPTED.
+ * The body handed to the codec is [hdr_len, src_len).  With u the body's extent, the trailer -- CRC32, then ISIZE,
+ * little-endian -- is the eight bytes at src_off + hdr_len + u; hdr_len + u + 8 > src_len is CORRUPTED with nothing read.
+ * A CRC-32 that differs is ZIPC_HIP_ERR_CHECKSUM with the value FOUND in checksum; then an ISIZE other than out_len mod
+ * 2^32 is CORRUPTED (the CRC comes first, as in zlib: a member with both wrong is CHECKSUM).  The sizing forms compare no
+ * CRC-32 (there are no bytes to take it of) but compare ISIZE and hold the same bound, so a member they size OK has the
+ * src_used the decode form reports.  On OK src_used = hdr_len + u + 8; what lies behind it is not looked at. */
+typedef struct {            /* 32 bytes, the layout of zipc_hip_extent_result */
+  uint32_t status;
+  uint32_t checksum;  /* CRC-32 of the output (decode), 0 (size); with ZIPC_HIP_ERR_CHECKSUM the value found; else 0 unless OK */
+  uint64_t out_len;   /* 0 unless OK */
+  uint64_t src_used;  /* whole member: header, body, trailer; 0 unless OK */
+  uint32_t hdr_len;   /* 0 unless OK */
+  uint32_t flg;       /* the member's FLG byte; 0 unless OK */
+} zipc_hip_gzip_result;
+enum { ZIPC_HIP_GZIP_PLAIN = 0, ZIPC_HIP_GZIP_BGZF = 1 };
+/* All pointers are DEVICE pointers.  The descriptors are zipc_hip_stream_desc with every field as in the mirrored extent
+ * form (zipc_hip_inflate_extent_batch with ZIPC_HIP_CRC_CRC32, zipc_hip_inflate_size_extent_batch,
+ * zipc_hip_inflate_size_extent_blocks_batch); limit and ZIPC_HIP_STREAM_HAS_LIMIT apply to the member's output.
+ * The decode form is ALWAYS a wave per member, whatever max_dst_cap: the open, one launch and the CRC-32 pass over the
+ * produced bytes, which max_dst_cap sizes as in zipc_hip_inflate_batch (a member whose output is longer is
+ * ZIPC_HIP_ERR_INVALID_ARG), then the close -- enqueued on the context's stream and never synchronised (growing the
+ * context's scratch may synchronise, as everywhere); zipc_hip_last_inflate_blocks is 0 behind it.  The size form never
+ * synchronises; the size-by-blocks form synchronises where zipc_hip_inflate_size_blocks_batch does, picks the members it
+ * picks, and zipc_hip_last_size_blocks says what it says there.  A caller with long members sizes them by blocks and
+ * decodes with zipc_hip_inflate_batch over the body (the first property), as zipc_hip_gzip_decompress does.
+ * Null ctx, d_descs or d_results, or n_streams above 0x7FFFFFFF, fails the call with ZIPC_HIP_ERR_INVALID_ARG;
+ * n_streams == 0 is ZIPC_HIP_OK and nothing is enqueued.  A flag bit other than ZIPC_HIP_STREAM_HAS_LIMIT, or a length
+ * above ZIPC_HIP_MAX_STREAM_LEN, is ZIPC_HIP_ERR_INVALID_ARG in the member's own result. */
+int zipc_hip_gzip_decompress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                   const zipc_hip_stream_desc *d_descs, zipc_hip_gzip_result *d_results,
+                                   size_t n_streams, size_t max_dst_cap);
+int zipc_hip_gzip_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                             zipc_hip_gzip_result *d_results, size_t n_streams);
+int zipc_hip_gzip_size_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                    zipc_hip_gzip_result *d_results, size_t n_streams);
+/* Compress: zipc_hip_deflate_batch with ZIPC_HIP_CRC_CRC32 between the open and the close, arguments and results as
+ * zipc_hip_zlib_compress_batch's (out_len counts the container's bytes, checksum is the CRC-32 of the source).  The header
+ * is 1f 8b 08 00 00000000 XFL ff: MTIME 0 and OS 255, so the output is a function of the input alone; XFL is 2 at
+ * ZIPC_HIP_LEVEL_BEST, 4 at ZIPC_HIP_LEVEL_FAST, 0 otherwise.  The trailer is the CRC-32 of the source and src_len mod
+ * 2^32.  ZIPC_HIP_GZIP_BGZF writes FLG = 4, XLEN = 6 and the subfield 42 43 02 00 BSIZE (the member's length - 1): an
+ * 18-byte header; the room is first clipped to 65 536 bytes, so a member can never exceed what BSIZE can say (a source
+ * that does not deflate into it is ZIPC_HIP_ERR_DST_TOO_SMALL: BGZF callers cut their input at 65 280 bytes).  The
+ * library writes members only: BGZF's 28-byte end-of-file block is the caller's to append.
+ * dst_cap below the overhead (18 bytes, BGZF 26) is ZIPC_HIP_ERR_DST_TOO_SMALL; zipc_hip_gzip_bound(len, flavour) always
+ * suffices for the plain flavour.  A level outside 0..3 or a flavour other than the two fails the call. */
+size_t zipc_hip_gzip_bound(size_t len, int flavour);
+int zipc_hip_gzip_compress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                 const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                                 size_t n_streams, size_t max_src_len, size_t total_src_len, int level, int flavour);
+/* From HOST memory.  zipc_hip_gzip_compress writes ONE member.  zipc_hip_gzip_size and zipc_hip_gzip_decompress take a
+ * whole FILE: every member is read and the outputs are concatenated (RFC 1952 section 2.2); *src_used says where the last
+ * member ended, *n_members how many there were.  The file is staged once.  A run of consecutive members whose headers say
+ * their length (BGZF) goes to the device as ONE batch call with exact lengths and destinations laid out from the ISIZEs --
+ * a BAM file costs one launch sequence, not a round trip per 64 KiB; a member of such a run that is not OK reports its
+ * status, one whose src_used differs from its BSIZE + 1, or whose body does not fit the room its own ISIZE promised, is
+ * ZIPC_HIP_ERR_CORRUPTED.  A member of unknown length is sized by the size-by-blocks form, decoded by
+ * zipc_hip_inflate_batch over its body (so a long .gz goes by blocks) and closed by the same rule.  Bytes behind the
+ * last member that do not begin with 1f 8b end the walk with ZIPC_HIP_OK.  Total output above dst_cap is
+ * ZIPC_HIP_ERR_DST_TOO_SMALL.  Any error returns with *out_len = *src_used = 0; on ZIPC_HIP_ERR_CHECKSUM *crc_found is the
+ * value found.  n_members and crc_found may be null.  There are no many-stream (_many) forms of gzip. */
+int zipc_hip_gzip_compress(zipc_hip_ctx *ctx, const void *src, size_t len, int level, int flavour,
+                           void *dst, size_t dst_cap, size_t *out_len);
+int zipc_hip_gzip_size(zipc_hip_ctx *ctx, const void *src, size_t len, size_t *out_len, size_t *src_used,
+                       size_t *n_members);
+int zipc_hip_gzip_decompress(zipc_hip_ctx *ctx, const void *src, size_t len, void *dst, size_t dst_cap,
+                             size_t *out_len, size_t *src_used, size_t *n_members, uint32_t *crc_found);
+
 /* Decode into ONE arena laid out on the device: size-then-decode (above) as one call, for a batch that is on the device
  * and whose caller has no destinations of their own.  The call sizes every stream, lays the outputs end to end in
  * d_dst_arena, decodes them there and says where each one went; nothing is read back for the layout.  All pointers are

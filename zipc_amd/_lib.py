@@ -31,6 +31,7 @@ CRC_NOP, CRC_CRC32, CRC_ADLER32, CRC_ADLER32_RFC1950 = 0, 1, 2, 3
 LEVEL_NONE, LEVEL_FAST, LEVEL_DEFAULT, LEVEL_BEST = 0, 1, 2, 3
 STREAM_HAS_LIMIT = 1
 STREAM_EXPECT_CRC32 = 2
+GZIP_PLAIN, GZIP_BGZF = 0, 1
 
 
 class StreamDesc(C.Structure):
@@ -57,6 +58,11 @@ class RecodeResult(C.Structure):
 class PackedResult(C.Structure):
     _fields_ = [("status", C.c_uint32), ("checksum", C.c_uint32), ("out_len", C.c_uint64), ("dst_off", C.c_uint64),
                 ("reserved", C.c_uint64)]
+
+
+class GzipResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("checksum", C.c_uint32), ("out_len", C.c_uint64), ("src_used", C.c_uint64),
+                ("hdr_len", C.c_uint32), ("flg", C.c_uint32)]
 
 
 class Range(C.Structure):
@@ -131,6 +137,14 @@ SYMBOLS = [
     ("zipc_hip_zlib_size_extent_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_inflate_extent", C.c_int, [_P, _P, _SZ, C.c_int, _SZ, _P, _SZ, C.c_int, _SZP, _SZP, _U32P]),
     ("zipc_hip_zlib_decompress_extent", C.c_int, [_P, _P, _SZ, C.c_int, _SZ, _P, _SZ, _SZP, _SZP, _U32P]),
+    ("zipc_hip_gzip_decompress_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ]),
+    ("zipc_hip_gzip_size_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
+    ("zipc_hip_gzip_size_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
+    ("zipc_hip_gzip_bound", _SZ, [_SZ, C.c_int]),
+    ("zipc_hip_gzip_compress_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int, C.c_int]),
+    ("zipc_hip_gzip_compress", C.c_int, [_P, _P, _SZ, C.c_int, C.c_int, _P, _SZ, _SZP]),
+    ("zipc_hip_gzip_size", C.c_int, [_P, _P, _SZ, _SZP, _SZP, _SZP]),
+    ("zipc_hip_gzip_decompress", C.c_int, [_P, _P, _SZ, _P, _SZ, _SZP, _SZP, _SZP, _U32P]),
     ("zipc_hip_inflate_size_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_zlib_size_blocks_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_inflate_packed_batch", C.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _SZ, C.c_int, _P]),

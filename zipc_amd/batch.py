@@ -269,6 +269,68 @@ def zlib_size_extent_blocks_batch(ctx: Context, src, descs_dev, results_dev, n_s
     ctx.synchronize()
 
 
+# zipc_hip_gzip_result: EXTENT_RESULT_DTYPE's layout, the last word split into the member's header length and FLG
+GZIP_RESULT_DTYPE = np.dtype([("status", "<u4"), ("checksum", "<u4"), ("out_len", "<u8"), ("src_used", "<u8"),
+                              ("hdr_len", "<u4"), ("flg", "<u4")])
+assert GZIP_RESULT_DTYPE.itemsize == 32
+GZIP_PLAIN, GZIP_BGZF = 0, 1
+
+
+def gzip_results_from_device(t) -> np.ndarray:
+    return t.cpu().numpy().view(GZIP_RESULT_DTYPE).copy()
+
+
+def gzip_decompress_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, max_dst_cap: int, sync: bool = True):
+    """zipc_hip_gzip_decompress_batch: stream i of `src` holds a gzip member (RFC 1952) from src_off on, src_len an upper
+    bound of its length; header checks, inflate, the CRC-32 and ISIZE comparisons all on the device.  results_dev: a uint8
+    cuda tensor of GZIP_RESULT_DTYPE records; src_used counts header, body and trailer.  Always a wave per member."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_gzip_decompress_batch(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(),
+                                              results_dev.data_ptr(), n_streams, max_dst_cap)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def gzip_size_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int, sync: bool = True):
+    """zipc_hip_gzip_size_batch: what every member inflates to and where it ends; no destination, no CRC-32 compared,
+    ISIZE compared."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_gzip_size_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def gzip_size_blocks_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int):
+    """zipc_hip_gzip_size_blocks_batch: gzip_size_batch's results with the long members sized by a wave per block
+    (Context.last_size_blocks).  The call synchronises the context's stream."""
+    _sync_torch(src)
+    st = lib().zipc_hip_gzip_size_blocks_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    ctx.synchronize()
+
+
+def gzip_compress_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, max_src_len: int, total_src_len: int,
+                        level: int, flavour: int = GZIP_PLAIN, sync: bool = True):
+    """zipc_hip_gzip_compress_batch: every stream's destination slot receives one gzip member (out_len counts its 18
+    container bytes, BGZF 26; checksum is the CRC-32 of the source); slots of gzip_bound(src_len) always fit the plain
+    flavour, a BGZF member never exceeds 65 536 bytes."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_gzip_compress_batch(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(),
+                                            results_dev.data_ptr(), n_streams, max_src_len, total_src_len, level, flavour)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def gzip_bound(n: int, flavour: int = GZIP_PLAIN) -> int:
+    return lib().zipc_hip_gzip_bound(n, flavour)
+
+
 def packed_results_from_device(t) -> np.ndarray:
     return t.cpu().numpy().view(PACKED_RESULT_DTYPE).copy()
 
@@ -560,5 +622,7 @@ __all__ = ["DESC_DTYPE", "RESULT_DTYPE", "RECODE_DESC_DTYPE", "RECODE_RESULT_DTY
            "PREFIX_RESULT_DTYPE", "inflate_prefix_batch", "zlib_decompress_prefix_batch", "prefix_results_from_device",
            "EXTENT_RESULT_DTYPE", "extent_results_from_device", "inflate_extent_batch", "zlib_decompress_extent_batch",
            "inflate_size_extent_batch", "zlib_size_extent_batch", "inflate_size_extent_blocks_batch", "zlib_size_extent_blocks_batch",
+           "GZIP_RESULT_DTYPE", "GZIP_PLAIN", "GZIP_BGZF", "gzip_results_from_device", "gzip_decompress_batch", "gzip_size_batch",
+           "gzip_size_blocks_batch", "gzip_compress_batch", "gzip_bound",
            "deflate_bound", "zlib_bound",
            "uniform_layout", "compact_descs", "OK"]

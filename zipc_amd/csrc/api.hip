@@ -1,6 +1,6 @@
 // api.hip -- the C ABI of include/zipc_hip.h, all of it but the many-stream host forms (many.hip): the context and its
 // scratch, tuning(), the CRC-32 pass and the checksum launches, the batch forms as argument checks around the launchers
-// of deflate.hip, inflate.hip, zlib.hip, recode.hip and packed.hip (ctx.h), and the one-stream host forms.
+// of deflate.hip, inflate.hip, zlib.hip, gzip.hip, recode.hip and packed.hip (ctx.h), and the one-stream host forms.
 //
 // Host forms stage one stream through device scratch and run the same kernels as
 // the batch forms (a batch of one).  Nothing here computes on the CPU: with no
@@ -15,6 +15,7 @@
 #include "ctx.h"
 #include "deflate_packed.h"
 #include "deflate_scratch.h"
+#include "gzip_container.h"
 #include "packed_layout.h"
 #include "recode_rules.h"
 #include "tuning.h"
@@ -319,7 +320,7 @@ void zipc_hip_destroy(zipc_hip_ctx *ctx) {
   free_buf(ctx->tok_scratch);
   free_buf(ctx->descs_marked);
   free_buf(ctx->size_descs); free_buf(ctx->size_head); free_buf(ctx->size_rest);
-  free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre); free_buf(ctx->prefix_adlers); free_buf(ctx->extent_inner);
+  free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre); free_buf(ctx->gzip_descs); free_buf(ctx->gzip_pre); free_buf(ctx->prefix_adlers); free_buf(ctx->extent_inner);
   free_buf(ctx->recode_descs); free_buf(ctx->recode_res); free_buf(ctx->recode_verdicts);
   free_buf(ctx->packed_descs); free_buf(ctx->packed_res); free_buf(ctx->packed_verdicts);
   free_buf(ctx->dpacked_staging); free_buf(ctx->dpacked_descs); free_buf(ctx->dpacked_res);
@@ -1040,6 +1041,250 @@ int zipc_hip_zlib_compress(zipc_hip_ctx *ctx, const void *src, size_t len, int l
   *out_len = body + ZLIB_OVERHEAD;
   if (adler) *adler = a;
   return ZIPC_HIP_OK;
+}
+
+// ---- the gzip container (gzip_container.h has the rules; gzip.hip the three kernels and their launches) ---------------
+// Each batch form is the mirrored extent form (or zipc_hip_deflate_batch) between gzip.hip's open and close.
+
+static_assert(sizeof(zipc_hip_gzip_result) == sizeof(GzipResult) && sizeof(GzipResult) == sizeof(zipc_hip_extent_result), "gzip result layout");
+static_assert(ZIPC_HIP_GZIP_PLAIN == GZIP_PLAIN && ZIPC_HIP_GZIP_BGZF == GZIP_BGZF, "gzip flavours");
+
+int zipc_hip_gzip_decompress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                   zipc_hip_gzip_result *d_results, size_t n_streams, size_t max_dst_cap) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  ctx->last_inflate_blocks = 0;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = launch_gzip_open(ctx, d_src_arena, d_descs, n_streams, 0, 0);
+  if (st) return st;
+  st = launch_inflate_extent(ctx, d_src_arena, d_dst_arena, (const zipc_hip_stream_desc *)ctx->gzip_descs.p, (zipc_hip_extent_result *)d_results,
+                             n_streams, max_dst_cap, ZIPC_HIP_CRC_CRC32);
+  if (st) return st;
+  return launch_gzip_close_extent(ctx, d_src_arena, d_descs, d_results, n_streams, 1);
+}
+int zipc_hip_gzip_size_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_gzip_result *d_results,
+                             size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  ctx->last_size_blocks = 0;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = launch_gzip_open(ctx, d_src_arena, d_descs, n_streams, 0, 0);
+  if (st) return st;
+  st = launch_inflate_size_extent(ctx, d_src_arena, (const zipc_hip_stream_desc *)ctx->gzip_descs.p, (zipc_hip_extent_result *)d_results, n_streams);
+  if (st) return st;
+  return launch_gzip_close_extent(ctx, d_src_arena, d_descs, d_results, n_streams, 0);
+}
+int zipc_hip_gzip_size_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                    zipc_hip_gzip_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  ctx->last_size_blocks = 0;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = launch_gzip_open(ctx, d_src_arena, d_descs, n_streams, 0, 0);
+  if (st) return st;
+  st = launch_inflate_size_extent_blocks(ctx, d_src_arena, (const zipc_hip_stream_desc *)ctx->gzip_descs.p, (zipc_hip_extent_result *)d_results,
+                                         n_streams, nullptr);
+  if (st) return st;
+  return launch_gzip_close_extent(ctx, d_src_arena, d_descs, d_results, n_streams, 0);
+}
+
+size_t zipc_hip_gzip_bound(size_t len, int flavour) {
+  return zipc_hip_deflate_bound(len) + (size_t)gzip_overhead(flavour == ZIPC_HIP_GZIP_BGZF ? GZIP_BGZF : GZIP_PLAIN);
+}
+
+int zipc_hip_gzip_compress_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                 zipc_hip_stream_result *d_results, size_t n_streams, size_t max_src_len, size_t total_src_len, int level,
+                                 int flavour) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull || level < 0 || level > 3) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (flavour != ZIPC_HIP_GZIP_PLAIN && flavour != ZIPC_HIP_GZIP_BGZF) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (max_src_len > MAX_STREAM_LEN) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = launch_gzip_open(ctx, d_src_arena, d_descs, n_streams, 1, flavour);
+  if (st) return st;
+  st = zipc_hip_deflate_batch(ctx, d_src_arena, d_dst_arena, (const zipc_hip_stream_desc *)ctx->gzip_descs.p, d_results, n_streams, max_src_len,
+                              total_src_len, level, ZIPC_HIP_CRC_CRC32);
+  if (st) return st;
+  return launch_gzip_close_compress(ctx, d_dst_arena, d_descs, d_results, n_streams, level, flavour);
+}
+
+// One member from host memory: the batch form of one around a copy in and a copy back
+int zipc_hip_gzip_compress(zipc_hip_ctx *ctx, const void *src, size_t len, int level, int flavour, void *dst, size_t dst_cap, size_t *out_len) {
+  if (!ctx || (!src && len) || (!dst && dst_cap) || !out_len) return ZIPC_HIP_ERR_INVALID_ARG;
+  *out_len = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int st = stage_in(ctx, src, len);
+  if (st) return st;
+  HIP_TRY(ctx, ctx->ensure(ctx->io_dst, dst_cap + 64));
+  HIP_TRY(ctx, ctx->ensure(ctx->io_desc, sizeof(StreamDesc)));
+  HIP_TRY(ctx, ctx->ensure(ctx->io_res, sizeof(StreamResult)));
+  StreamDesc d;
+  memset(&d, 0, sizeof d);
+  d.src_len = len; d.dst_cap = dst_cap;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->io_desc.p, &d, sizeof d, hipMemcpyHostToDevice, ctx->stream));
+  st = zipc_hip_gzip_compress_batch(ctx, ctx->io_src.p, ctx->io_dst.p, (zipc_hip_stream_desc *)ctx->io_desc.p, (zipc_hip_stream_result *)ctx->io_res.p,
+                                    1, len, len, level, flavour);
+  if (st) return st;
+  StreamResult r;
+  HIP_TRY(ctx, hipMemcpyAsync(&r, ctx->io_res.p, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (r.status != ST_OK) return (int)r.status;
+  if (r.out_len > dst_cap) return ZIPC_HIP_ERR_DST_TOO_SMALL;
+  HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->io_dst.p, r.out_len, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *out_len = r.out_len;
+  return ZIPC_HIP_OK;
+}
+
+// A whole FILE of members from host memory (zipc_hip_gzip_size, zipc_hip_gzip_decompress): staged once and walked with
+// gzip_next; the outputs lie end to end in the context's staging room and come back in one copy.
+struct GzipWalk {
+  zipc_hip_ctx *ctx;
+  bool decode;
+  const uint8_t *file;
+  uint64_t len, dst_cap;
+  uint64_t off = 0, total = 0, members = 0;  // where the next member begins, the output so far, the members read
+  uint32_t crc_found = 0;                     // of the member that is ZIPC_HIP_ERR_CHECKSUM
+  std::vector<StreamDesc> descs;
+  std::vector<GzipResult> res;
+};
+
+// descs -> the context's descriptor slot; room for n results of 32 bytes
+static int gzip_walk_put(GzipWalk &w, size_t n) {
+  zipc_hip_ctx *ctx = w.ctx;
+  HIP_TRY(ctx, ctx->ensure(ctx->io_desc, n * sizeof(StreamDesc)));
+  HIP_TRY(ctx, ctx->ensure(ctx->io_res, n * sizeof(GzipResult)));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->io_desc.p, w.descs.data(), n * sizeof(StreamDesc), hipMemcpyHostToDevice, ctx->stream));
+  return ZIPC_HIP_OK;
+}
+static int gzip_walk_get(GzipWalk &w, void *into, size_t bytes) {
+  zipc_hip_ctx *ctx = w.ctx;
+  HIP_TRY(ctx, hipMemcpyAsync(into, ctx->io_res.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return ZIPC_HIP_OK;
+}
+
+// The run of members of known length that begins at w.off (consecutive BGZF members): ONE batch call, src_len exact, the
+// destinations laid out from the ISIZEs.  A member that is not OK reports its status; one whose src_used is not its
+// BSIZE + 1, or whose body does not fit the room its own ISIZE promised, is corrupted.
+static int gzip_walk_run(GzipWalk &w) {
+  zipc_hip_ctx *ctx = w.ctx;
+  uint64_t at = w.off, room = w.total, max_cap = 0;
+  w.descs.clear();
+  for (;;) {
+    const GzipStep s = gzip_next(w.file, w.len, at);
+    if (s.end_of_members || s.status != ST_OK || !s.known) break;
+    StreamDesc d;
+    memset(&d, 0, sizeof d);
+    d.src_off = at; d.src_len = s.bsize; d.dst_off = room; d.dst_cap = s.isize;
+    w.descs.push_back(d);
+    at += s.bsize;
+    room += s.isize;
+    if (s.isize > max_cap) max_cap = s.isize;
+  }
+  const size_t n = w.descs.size();
+  if (n > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  // (a run that promises more than the caller's room is only sized: a member that lies about itself says so first)
+  const bool no_room = w.decode && room > w.dst_cap;
+  int st = gzip_walk_put(w, n);
+  if (st) return st;
+  const zipc_hip_stream_desc *dd = (const zipc_hip_stream_desc *)ctx->io_desc.p;
+  zipc_hip_gzip_result *dr = (zipc_hip_gzip_result *)ctx->io_res.p;
+  st = w.decode && !no_room ? zipc_hip_gzip_decompress_batch(ctx, ctx->io_src.p, ctx->io_dst.p, dd, dr, n, (size_t)max_cap)
+                            : zipc_hip_gzip_size_batch(ctx, ctx->io_src.p, dd, dr, n);
+  if (st) return st;
+  w.res.resize(n);
+  st = gzip_walk_get(w, w.res.data(), n * sizeof(GzipResult));
+  if (st) return st;
+  for (size_t i = 0; i < n; i++) {
+    const GzipResult &r = w.res[i];
+    if (r.status == ST_DST_TOO_SMALL) return ZIPC_HIP_ERR_CORRUPTED;
+    if (r.status != ST_OK) { w.crc_found = r.checksum; return (int)r.status; }
+    if (r.src_used != w.descs[i].src_len) return ZIPC_HIP_ERR_CORRUPTED;
+  }
+  if (no_room) return ZIPC_HIP_ERR_DST_TOO_SMALL;
+  w.off = at; w.total = room; w.members += n;  // (every member OK: out_len is the ISIZE its room was laid out from)
+  return ZIPC_HIP_OK;
+}
+
+// A member of unknown length at w.off: sized by the size-by-blocks form of one over the rest of the file, decoded by
+// zipc_hip_inflate_batch's path over its body with src_len := the extent and CRC-32 (a long member goes by blocks), closed
+// here by the same gzip_close.  (The bound is clipped to the longest stream there is: a longer member is not read.)
+static int gzip_walk_member(GzipWalk &w) {
+  zipc_hip_ctx *ctx = w.ctx;
+  StreamDesc d;
+  memset(&d, 0, sizeof d);
+  d.src_off = w.off;
+  d.src_len = w.len - w.off > MAX_STREAM_LEN ? MAX_STREAM_LEN : w.len - w.off;
+  w.descs.assign(1, d);
+  int st = gzip_walk_put(w, 1);
+  if (st) return st;
+  st = zipc_hip_gzip_size_blocks_batch(ctx, ctx->io_src.p, (const zipc_hip_stream_desc *)ctx->io_desc.p, (zipc_hip_gzip_result *)ctx->io_res.p, 1);
+  if (st) return st;
+  GzipResult sized;
+  st = gzip_walk_get(w, &sized, sizeof sized);
+  if (st) return st;
+  if (sized.status != ST_OK) return (int)sized.status;
+  if (w.decode) {
+    if (w.total + sized.out_len > w.dst_cap) return ZIPC_HIP_ERR_DST_TOO_SMALL;
+    const uint64_t u = sized.src_used - sized.hdr_len - 8u;
+    StreamDesc body;
+    memset(&body, 0, sizeof body);
+    body.src_off = gzip_body_off(w.off, sized.hdr_len); body.src_len = u;
+    body.dst_off = w.total; body.dst_cap = sized.out_len;
+    w.descs.assign(1, body);
+    st = gzip_walk_put(w, 1);
+    if (st) return st;
+    st = launch_inflate(ctx, ctx->io_src.p, ctx->io_dst.p, (const zipc_hip_stream_desc *)ctx->io_desc.p, (zipc_hip_stream_result *)ctx->io_res.p, 1,
+                        (size_t)sized.out_len, ZIPC_HIP_CRC_CRC32, &body, true);
+    if (st) return st;
+    StreamResult sr;
+    st = gzip_walk_get(w, &sr, sizeof sr);
+    if (st) return st;
+    ExtentResult inner;
+    inner.status = sr.status; inner.checksum = sr.checksum; inner.out_len = sr.out_len; inner.src_used = u; inner.reserved = 0;
+    const GzipResult closed = gzip_close(ST_OK, d.src_len, w.file + w.off, sized.hdr_len, sized.flg, inner, true);
+    if (closed.status != ST_OK) { w.crc_found = closed.checksum; return (int)closed.status; }
+  }
+  w.off += sized.src_used; w.total += sized.out_len; w.members += 1;
+  return ZIPC_HIP_OK;
+}
+
+static int gzip_file(zipc_hip_ctx *ctx, bool decode, const void *src, size_t len, void *dst, size_t dst_cap, size_t *out_len, size_t *src_used,
+                     size_t *n_members, uint32_t *crc_found) {
+  if (!ctx || (!src && len) || (decode && !dst && dst_cap) || !out_len || !src_used) return ZIPC_HIP_ERR_INVALID_ARG;
+  *out_len = 0;
+  *src_used = 0;
+  if (n_members) *n_members = 0;
+  if (crc_found) *crc_found = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int st = stage_in(ctx, src, len);
+  if (st) return st;
+  if (decode) HIP_TRY(ctx, ctx->ensure(ctx->io_dst, dst_cap + 64));  // (before anything is in flight: growing it would lose what it holds)
+  GzipWalk w;
+  w.ctx = ctx; w.decode = decode; w.file = (const uint8_t *)src; w.len = len; w.dst_cap = dst_cap;
+  for (;;) {
+    const GzipStep step = gzip_next(w.file, w.len, w.off);
+    if (step.end_of_members) break;  // (what lies behind the last member is ignored: *src_used says where it begins)
+    if (step.status != ST_OK) return (int)step.status;
+    st = step.known ? gzip_walk_run(w) : gzip_walk_member(w);
+    if (st) {
+      if (st == ZIPC_HIP_ERR_CHECKSUM && crc_found) *crc_found = w.crc_found;
+      return st;
+    }
+  }
+  if (decode && w.total) {
+    HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->io_dst.p, w.total, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  *out_len = (size_t)w.total;
+  *src_used = (size_t)w.off;
+  if (n_members) *n_members = (size_t)w.members;
+  return ZIPC_HIP_OK;
+}
+
+int zipc_hip_gzip_size(zipc_hip_ctx *ctx, const void *src, size_t len, size_t *out_len, size_t *src_used, size_t *n_members) {
+  return gzip_file(ctx, false, src, len, nullptr, 0, out_len, src_used, n_members, nullptr);
+}
+int zipc_hip_gzip_decompress(zipc_hip_ctx *ctx, const void *src, size_t len, void *dst, size_t dst_cap, size_t *out_len, size_t *src_used,
+                             size_t *n_members, uint32_t *crc_found) {
+  return gzip_file(ctx, true, src, len, dst, dst_cap, out_len, src_used, n_members, crc_found);
 }
 
 }  // extern "C"

@@ -57,6 +57,7 @@ struct zipc_hip_ctx {
   Buf descs_marked;                               // ... a call's descriptors with those streams marked as done, for the one waves of the rest
   Buf size_descs, size_head, size_rest;                      // sizing by blocks: the call's descriptors with no destination (dst_off 0, dst_cap the longest stream's), the heads' results and span slots, the one-wave results of the streams left
   Buf zlib_descs, zlib_pre;                       // the zlib batch forms: the descriptors the codec runs with, the container checks' verdicts (zlib.hip)
+  Buf gzip_descs, gzip_pre;                       // the gzip batch forms: the descriptors the codec runs with, the headers' verdicts, lengths and FLGs (gzip.hip)
   Buf prefix_adlers;                              // the zlib prefix form: the Adler-32 of every stream that ended within its room (inflate.hip inflate_prefix_kernel)
   Buf extent_inner;                               // the extent decode form with CRC-32: a StreamResult per stream for the checksum pass (inflate.hip launch_inflate_extent)
   Buf recode_descs, recode_res, recode_verdicts;  // the recode forms: the descriptors inflate, then deflate run with, their results, what is known of a stream between the steps (recode.hip)
@@ -220,6 +221,14 @@ int launch_zlib_close_prefix(zipc_hip_ctx *ctx, zipc_hip_prefix_result *d_result
 // ... of the extent forms: d_descs the caller's (the trailer is read at 2 + the body's extent); compare 0: the sizing form's
 int launch_zlib_close_extent(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
                              zipc_hip_extent_result *d_results, size_t n, int compare);
+// gzip.hip: the gzip container's kernels around the codec's (a ZIPC_HIP_* status each): open leaves the codec's descriptors in
+// ctx->gzip_descs and the headers' verdicts in ctx->gzip_pre (compress: the room behind the header to be; flavour: ZIPC_HIP_GZIP_*);
+// the extent close reads the trailer behind the body's extent (d_descs the caller's; compare_crc 0: the sizing forms')
+int launch_gzip_open(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, size_t n, int compress, int flavour);
+int launch_gzip_close_extent(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_gzip_result *d_results,
+                             size_t n, int compare_crc);
+int launch_gzip_close_compress(zipc_hip_ctx *ctx, void *d_dst_arena, const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                               size_t n, int level, int flavour);
 // many.hip: the staging threads' pools, shared by the process's contexts (zipc_hip_create / zipc_hip_destroy)
 void many_pools_acquire();
 void many_pools_release();

@@ -350,6 +350,53 @@ Result<std::string> zlib_compress(const std::string &s, std::optional<level> lvl
   return Result<std::string>::Ok(std::move(out));
 }
 
+Result<std::string> gzip_compress(const std::string &s, std::optional<level> lvl, bool bgzf, std::size_t start, std::size_t len) {
+  const auto r = range(s, start, len);
+  const int flavour = bgzf ? ZIPC_HIP_GZIP_BGZF : ZIPC_HIP_GZIP_PLAIN;
+  const std::size_t cap = zipc_hip_gzip_bound(r.second, flavour);
+  std::string out(cap, '\0');
+  std::size_t out_len = 0;
+  const int st = zipc_hip_gzip_compress(context(), s.data() + r.first, r.second, level_of(lvl), flavour, &out[0], cap, &out_len);
+  throw_if_library_failure(st);
+  if (st) return Result<std::string>::Error(message(st));
+  out.resize(out_len);
+  return Result<std::string>::Ok(std::move(out));
+}
+
+// the two whole-file values: gzip_size alone, or gzip_size for the room and zipc_hip_gzip_decompress into it
+static GzipResult gzip_file(bool decode, const std::string &s, std::size_t start, std::size_t len) {
+  const auto r = range(s, start, len);
+  const char *p = s.data() + r.first;
+  GzipResult g;
+  uint32 found = 0;
+  int st = zipc_hip_gzip_size(context(), p, r.second, &g.value.length, &g.value.used, &g.value.members);
+  if (st == ZIPC_HIP_OK && decode) {
+    g.value.value.resize(g.value.length);
+    std::size_t out_len = 0;
+    st = zipc_hip_gzip_decompress(context(), p, r.second, g.value.length ? &g.value.value[0] : nullptr, g.value.length, &out_len,
+                                  &g.value.used, &g.value.members, &found);
+    g.value.value.resize(st == ZIPC_HIP_OK ? out_len : 0);
+  }
+  throw_if_library_failure(st);
+  if (st == ZIPC_HIP_OK) { g.ok = true; return g; }
+  g.value = GzipFile();
+  if (st == ZIPC_HIP_ERR_CHECKSUM) {
+    char b[64];
+    snprintf(b, sizeof b, "Checksum mismatch, found %lx", (unsigned long)found);
+    g.error.found = found;
+    g.error.message = b;
+  } else if (st == ZIPC_HIP_ERR_ZLIB_METHOD) {
+    char b[64];
+    snprintf(b, sizeof b, "Unknown compression method (%d)", r.second > 2 ? (int)(unsigned char)p[2] : 0);
+    g.error.message = b;
+  } else {
+    g.error.message = message(st);
+  }
+  return g;
+}
+GzipResult gzip_size(const std::string &s, std::size_t start, std::size_t len) { return gzip_file(false, s, start, len); }
+GzipResult gzip_decompress(const std::string &s, std::size_t start, std::size_t len) { return gzip_file(true, s, start, len); }
+
 std::vector<std::pair<std::size_t, std::size_t>> partition_items(const std::vector<ManyItem> &items, std::size_t n_devices) {
   // contiguous ranges balanced by bytes: boundary k is the first index where the running byte count reaches
   // k / n_devices of the total (zipc_amd/shard.partition is the same rule for bench.py's ranks)

@@ -132,6 +132,30 @@ Result<std::pair<Adler_32::t, std::string>> adler_32_and_deflate(const std::stri
 Result<std::string> zlib_compress(const std::string &s, std::optional<level> lvl = std::nullopt,
                                   std::size_t start = 0, std::size_t len = npos);
 
+// ADDITIONS: gzip (RFC 1952; include/zipc_hip.h zipc_hip_gzip_*), the reference has none.  gzip_compress writes ONE member
+// (MTIME 0, OS 255), bgzf: a BGZF member of at most 64 KiB in all -- the end-of-file block is the caller's to append.
+// gzip_size and gzip_decompress read a whole FILE, every member of the range, the outputs concatenated; a run of BGZF
+// members is one batch on the device.  A name or a comment of a header may be at most 65 535 bytes long.
+struct GzipFile {
+  std::string value;         // gzip_decompress: the members' outputs end to end
+  std::size_t length = 0;    // ... and their length (gzip_size: that alone)
+  std::size_t used = 0;      // source bytes from start up to the end of the last member
+  std::size_t members = 0;
+};
+struct GzipError {
+  std::optional<Crc_32::t> found;  // a member's CRC-32 differs: the value found
+  std::string message;
+};
+struct GzipResult {
+  bool ok = false;
+  GzipFile value;
+  GzipError error;
+};
+Result<std::string> gzip_compress(const std::string &s, std::optional<level> lvl = std::nullopt, bool bgzf = false,
+                                  std::size_t start = 0, std::size_t len = npos);
+GzipResult gzip_size(const std::string &s, std::size_t start = 0, std::size_t len = npos);
+GzipResult gzip_decompress(const std::string &s, std::size_t start = 0, std::size_t len = npos);
+
 // ---- many streams at once (no counterpart in the reference, which handles one
 // string per call: what an archive-level caller uses, zipc.hpp)
 struct ManyItem {

@@ -309,6 +309,67 @@ def zlib_compress(s, level=None, start=0, len=None, ctx=None):
     return Ok((adler.value, dst.raw[:out_len.value]))
 
 
+# ---- gzip (RFC 1952; include/zipc_hip.h zipc_hip_gzip_*): additions, the reference has no gzip.  A name or a comment of a
+# member's header may be at most 65 535 bytes long (a limit of this library); compress writes MTIME 0 and OS 255.
+
+_FATAL = (_lib.ERR_HIP, _lib.ERR_INVALID_ARG, _lib.ERR_NO_DEVICE, _lib.ERR_NOMEM)
+
+
+def gzip_compress(s, level=None, bgzf=False, start=0, len=None, ctx=None):
+    """One gzip member of the range: Ok bytes | Error msg.  bgzf: a BGZF member (an extra field with the member's length,
+    at most 64 KiB in all: cut the input at 65 280 bytes; BGZF's end-of-file block is the caller's to append)."""
+    data = _range(s, start, len)
+    ctx = ctx or default_context()
+    n = data.__len__()
+    flavour = _lib.GZIP_BGZF if bgzf else _lib.GZIP_PLAIN
+    cap = lib().zipc_hip_gzip_bound(n, flavour)
+    dst = C.create_string_buffer(cap)
+    out_len = C.c_size_t()
+    st = lib().zipc_hip_gzip_compress(ctx.handle, data, n, _level(level), flavour, dst, cap, C.byref(out_len))
+    if st == OK:
+        return Ok(dst.raw[:out_len.value])
+    if st in _FATAL:
+        ctx.check(st)
+    return Error(_message(st))
+
+
+def gzip_size(s, start=0, len=None, ctx=None):
+    """What `gzip_decompress` of the same range would hand back, without the bytes and without the CRC-32s compared:
+    Ok (length, used, members) | Error msg."""
+    data = _range(s, start, len)
+    ctx = ctx or default_context()
+    out_len, used, members = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    st = lib().zipc_hip_gzip_size(ctx.handle, data, data.__len__(), C.byref(out_len), C.byref(used), C.byref(members))
+    if st == OK:
+        return Ok((out_len.value, used.value, members.value))
+    if st in _FATAL:
+        ctx.check(st)
+    return Error(_message(st, data[2] if data.__len__() > 2 else 0))
+
+
+def gzip_decompress(s, start=0, len=None, ctx=None):
+    """A whole gzip FILE -- every member of the range, their outputs concatenated (a .gz, a BGZF file in one batch per run
+    of members): Ok (bytes, used, members) | Error (found | None, msg), `used` the source bytes up to the end of the last
+    member, `found` the CRC-32 found where a member's own differs."""
+    data = _range(s, start, len)
+    ctx = ctx or default_context()
+    n = data.__len__()
+    size, used, members, crc = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_uint32()
+    st = lib().zipc_hip_gzip_size(ctx.handle, data, n, C.byref(size), C.byref(used), C.byref(members))
+    if st == OK:
+        dst = C.create_string_buffer(max(size.value, 1))
+        out_len = C.c_size_t()
+        st = lib().zipc_hip_gzip_decompress(ctx.handle, data, n, dst, size.value, C.byref(out_len), C.byref(used), C.byref(members),
+                                            C.byref(crc))
+        if st == OK:
+            return Ok((dst.raw[:out_len.value], used.value, members.value))
+    if st in _FATAL:
+        ctx.check(st)
+    if st == ERR_CHECKSUM:
+        return Error((crc.value, "Checksum mismatch, found %x" % crc.value))
+    return Error((None, _message(st, data[2] if n > 2 else 0)))
+
+
 # ---- many streams in one call (include/zipc_hip.h zipc_hip_zlib_*_many): what a caller with a pack of git objects, the
 # IDAT chunks of many images or a table's pages uses instead of n calls of the two functions above.  The reference has
 # no such values; every element of the result is what the single-stream function gives for that stream.
