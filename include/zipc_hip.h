@@ -463,6 +463,85 @@ int zipc_hip_zlib_decompress_prefix_batch(zipc_hip_ctx *ctx, const void *d_src_a
                                           const zipc_hip_stream_desc *d_descs, zipc_hip_prefix_result *d_results,
                                           size_t n_streams);
 
+/* Inflate with HISTORY: a stream that does not start at bit 0 of its input with nothing in front of its output -- a raw
+ * deflate piece whose encoder kept its window across a flush (permessage-deflate messages, pigz-style chunks, the records
+ * of a log written with Z_SYNC_FLUSH), a chunk of a long stream read from an access point (the zran / indexed-gzip idea:
+ * an index holds a bit position and the 32 KiB of output in front of it), a zlib stream with a preset dictionary.  Every
+ * other inflate form calls a match that reaches in front of the output ZIPC_HIP_ERR_CORRUPTED. */
+typedef struct {            /* 8 bytes, one per stream */
+  uint32_t hist_len;   /* bytes of history, <= 32768: they lie at [dst_off - hist_len, dst_off) of the DESTINATION arena */
+  uint32_t start_bit;  /* the bit of the byte at src_off at which the first block header starts, 0..7, 0 the lowest */
+} zipc_hip_history;
+/* All pointers are DEVICE pointers.  The descriptors are zipc_hip_inflate_batch's; d_hist: a record per stream, or null:
+ * every record is {0, 0}.  The CALLER has put the history where the record says (the zlib dictionary forms below do it
+ * themselves); it is read, never written: the bytes at [dst_off - hist_len, dst_off) are unchanged after every call,
+ * whatever the status.
+ * The verdict on a record, in this order, each the stream's own result with out_len 0: hist_len > 32768, start_bit > 7,
+ * hist_len > dst_off (the sizing form has no destination and skips this one) are ZIPC_HIP_ERR_INVALID_ARG; then the
+ * descriptor's own tests as ever, on the caller's values.
+ * The defining property: a match is legal iff its distance <= hist_len + (bytes produced so far).  Everything else is
+ * what zipc_hip_inflate_batch says with positions counted from dst_off: the room table, the limit rule (a limit counts
+ * the stream's own bytes, not the history), the statuses, the order of checks, out_len.  With a null d_hist, or a record
+ * of {0, 0}, every history form IS the form it mirrors: same status, out_len, checksum and bytes.
+ * Checksums: ZIPC_HIP_CRC_ADLER32 / _RFC1950 are of the stream's own output (the history is not summed);
+ * ZIPC_HIP_CRC_CRC32 is the pass over [dst_off, dst_off + out_len).  The checksums of pieces are not combined here.
+ * Always a wave per stream: no by-blocks path, no stored-chain path, nothing read back, never synchronised
+ * (zipc_hip_last_inflate_blocks is 0 behind them).  The layout is the caller's duty ("decode from an
+ * access point"): streams of ONE call need rooms of their own with their histories in front, and a stream's history must
+ * not be the room another stream of the same call is written to (a copy may store up to 7 transient bytes past a match);
+ * pieces decoded in successive calls may lie end to end, hist_len = min(32768, bytes so far).
+ * Null ctx, d_descs or d_results, crc_op outside 0..3, or n_streams above 0x7FFFFFFF, fails the call with
+ * ZIPC_HIP_ERR_INVALID_ARG; n_streams == 0 is ZIPC_HIP_OK and nothing is enqueued.
+ * Out of scope: deflating against a dictionary or a kept window; building an index of access points; history in the
+ * extent, packed, gzip and recode forms; a by-blocks path for long streams with history; combining checksums of pieces.
+ *
+ * zipc_hip_inflate_history_batch: from the start point to the end of the final block, all or nothing. */
+int zipc_hip_inflate_history_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                   const zipc_hip_stream_desc *d_descs, const zipc_hip_history *d_hist,
+                                   zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, int crc_op);
+/* The first dst_cap bytes from the start point: zipc_hip_inflate_prefix_batch's one rule, word for word, over the
+ * statuses above.  This is the read from an access point: a chunk of a long stream is cut at its room, and nothing
+ * behind the cut is read or judged. */
+int zipc_hip_inflate_prefix_history_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                          const zipc_hip_stream_desc *d_descs, const zipc_hip_history *d_hist,
+                                          zipc_hip_prefix_result *d_results, size_t n_streams);
+/* Sizing: no arena is written or read, the record serves the distance test alone; status and out_len are what
+ * zipc_hip_inflate_history_batch reports with dst_cap = ZIPC_HIP_MAX_STREAM_LEN, checksum 0. */
+int zipc_hip_inflate_size_history_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                        const zipc_hip_history *d_hist, zipc_hip_stream_result *d_results,
+                                        size_t n_streams);
+/* WHOLE zlib streams against ONE preset dictionary on the device (RFC 1950's FDICT, as deflateSetDictionary makes them):
+ * d_dict, dict_len <= 32768 bytes (more, or a null d_dict with dict_len != 0, fails the call).
+ * zipc_hip_zlib_decompress_batch keeps answering ZIPC_HIP_ERR_ZLIB_DICT for such streams; these forms open them:
+ *   - the container's checks in their order up to the FDICT test (length, FCHECK, method, window);
+ *   - a stream WITHOUT FDICT is opened exactly as there and decoded with no history, as zlib does;
+ *   - a stream with FDICT: shorter than 10 bytes is ZIPC_HIP_ERR_CORRUPTED; dict_len == 0, or a DICTID (bytes 2..5,
+ *     big-endian) that is not RFC 1950's Adler-32 of the dictionary -- whatever the context's flavour -- is
+ *     ZIPC_HIP_ERR_ZLIB_DICT with checksum = the DICTID found, so that a caller can look the right dictionary up, and
+ *     out_len 0; otherwise the body is [6, len - 4) and the dictionary its history.
+ * The dictionary's Adler-32 is made once per call on the device; nothing is read back, the call is never synchronised.
+ * The decompress form then COPIES THE DICTIONARY to [dst_off - dict_len, dst_off) of every stream opened with FDICT:
+ * the one place where a form of this library writes in front of dst_off.  That gap belongs to the call; dst_off <
+ * dict_len is the stream's ZIPC_HIP_ERR_INVALID_ARG.  The gap of a stream without FDICT, or of one that failed its open,
+ * is not written; nothing is written in front of the gap or behind dst_off + dst_cap.  The sizing form writes nothing.
+ * The close: the Adler-32 of the output alone (the context's flavour) against the trailer, as
+ * zipc_hip_zlib_decompress_batch compares it; the sizing form compares nothing, as zipc_hip_zlib_size_batch. */
+int zipc_hip_zlib_decompress_dict_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena,
+                                        const zipc_hip_stream_desc *d_descs, zipc_hip_stream_result *d_results,
+                                        size_t n_streams, size_t max_dst_cap, const void *d_dict, size_t dict_len);
+int zipc_hip_zlib_size_dict_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                  zipc_hip_stream_result *d_results, size_t n_streams, const void *d_dict,
+                                  size_t dict_len);
+/* Host forms, thin: ONE stream from host memory, staged as [history | room] in the context's buffers, through the batch
+ * form of one, and only the room copied back.  They synchronise.  The return value is the stream's status.
+ * zipc_hip_inflate_history: hist_len bytes at `hist` are the history (hist_len > 32768 or start_bit > 7 is
+ * ZIPC_HIP_ERR_INVALID_ARG); checksum may be null.  zipc_hip_zlib_decompress_dict: a whole zlib stream against `dict`. */
+int zipc_hip_inflate_history(zipc_hip_ctx *ctx, const void *src, size_t len, unsigned start_bit, const void *hist,
+                             size_t hist_len, int has_limit, size_t limit, void *dst, size_t dst_cap, int crc_op,
+                             size_t *out_len, uint32_t *checksum);
+int zipc_hip_zlib_decompress_dict(zipc_hip_ctx *ctx, const void *src, size_t len, const void *dict, size_t dict_len,
+                                  void *dst, size_t dst_cap, size_t *out_len);
+
 /* Sizing with the long streams of the call BY BLOCKS: descriptors, results, argument rules and the defining property of
  * zipc_hip_inflate_size_batch / zipc_hip_zlib_size_batch, word for word -- status and out_len are what
  * zipc_hip_inflate_batch (ZIPC_HIP_CRC_NOP) reports with dst_cap = ZIPC_HIP_MAX_STREAM_LEN, checksum is 0, no arena is

@@ -129,6 +129,13 @@ SYMBOLS = [
     ("zipc_hip_zlib_size_batch", C.c_int, [_P, _P, _P, _P, _SZ]),
     ("zipc_hip_inflate_prefix_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ]),
     ("zipc_hip_zlib_decompress_prefix_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ]),
+    ("zipc_hip_inflate_history_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _SZ, _SZ, C.c_int]),
+    ("zipc_hip_inflate_prefix_history_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _SZ]),
+    ("zipc_hip_inflate_size_history_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ]),
+    ("zipc_hip_zlib_decompress_dict_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, _P, _SZ]),
+    ("zipc_hip_zlib_size_dict_batch", C.c_int, [_P, _P, _P, _P, _SZ, _P, _SZ]),
+    ("zipc_hip_inflate_history", C.c_int, [_P, _P, _SZ, C.c_uint, _P, _SZ, C.c_int, _SZ, _P, _SZ, C.c_int, _SZP, _U32P]),
+    ("zipc_hip_zlib_decompress_dict", C.c_int, [_P, _P, _SZ, _P, _SZ, _P, _SZ, _SZP]),
     ("zipc_hip_inflate_extent_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ, C.c_int]),
     ("zipc_hip_zlib_decompress_extent_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ, _SZ]),
     ("zipc_hip_inflate_size_extent_batch", C.c_int, [_P, _P, _P, _P, _SZ]),

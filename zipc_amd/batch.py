@@ -183,6 +183,101 @@ def zlib_decompress_prefix_batch(ctx: Context, src, dst, descs_dev, results_dev,
         ctx.synchronize()
 
 
+# zipc_hip_history: hist_len bytes of history lie in front of dst_off; the first block header starts at bit start_bit of the byte at src_off
+HISTORY_DTYPE = np.dtype([("hist_len", "<u4"), ("start_bit", "<u4")])
+assert HISTORY_DTYPE.itemsize == 8
+
+
+def make_history(hist_len, start_bit=None) -> np.ndarray:
+    h = np.zeros(len(hist_len), dtype=HISTORY_DTYPE)
+    h["hist_len"] = hist_len
+    if start_bit is not None:
+        h["start_bit"] = start_bit
+    return h
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def inflate_history_batch(ctx: Context, src, dst, descs_dev, hist_dev, results_dev, n_streams: int, max_dst_cap: int,
+                          crc_op: int = CRC_NOP, sync: bool = True):
+    """zipc_hip_inflate_history_batch: inflate_batch from a start point -- stream i begins at bit start_bit of its first byte and
+    may copy from the hist_len bytes the caller has put in front of its room.  hist_dev: a uint8 cuda tensor of HISTORY_DTYPE
+    records, or None (no stream has history).  Always a wave per stream."""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_inflate_history_batch(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(), _ptr(hist_dev),
+                                              results_dev.data_ptr(), n_streams, max_dst_cap, crc_op)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def inflate_prefix_history_batch(ctx: Context, src, dst, descs_dev, hist_dev, results_dev, n_streams: int, sync: bool = True):
+    """zipc_hip_inflate_prefix_history_batch: the first dst_cap bytes from the start point (PREFIX_RESULT_DTYPE records): the
+    read of a chunk of a long stream from an access point"""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_inflate_prefix_history_batch(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(), _ptr(hist_dev),
+                                                     results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def inflate_size_history_batch(ctx: Context, src, descs_dev, hist_dev, results_dev, n_streams: int, sync: bool = True):
+    """zipc_hip_inflate_size_history_batch: what inflate_history_batch reports into the largest room, nothing written"""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_inflate_size_history_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), _ptr(hist_dev),
+                                                   results_dev.data_ptr(), n_streams)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def zlib_decompress_dict_batch(ctx: Context, src, dst, descs_dev, results_dev, n_streams: int, max_dst_cap: int, dict_dev, dict_len: int,
+                               sync: bool = True):
+    """zipc_hip_zlib_decompress_dict_batch: whole zlib streams against one preset dictionary (a uint8 cuda tensor, or None with
+    dict_len 0); the call writes the dictionary to [dst_off - dict_len, dst_off) of every stream that was made with it"""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_zlib_decompress_dict_batch(ctx.handle, src.data_ptr(), dst.data_ptr(), descs_dev.data_ptr(),
+                                                   results_dev.data_ptr(), n_streams, max_dst_cap, _ptr(dict_dev), dict_len)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def zlib_size_dict_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int, dict_dev, dict_len: int, sync: bool = True):
+    """zipc_hip_zlib_size_dict_batch: the same streams sized, nothing written"""
+    if sync:
+        _sync_torch(src)
+    st = lib().zipc_hip_zlib_size_dict_batch(ctx.handle, src.data_ptr(), descs_dev.data_ptr(), results_dev.data_ptr(), n_streams,
+                                             _ptr(dict_dev), dict_len)
+    ctx.check(st)
+    if sync:
+        ctx.synchronize()
+
+
+def inflate_history(ctx: Context, raw: bytes, hist: bytes = b"", start_bit: int = 0, dst_cap: int = 0, limit=None, crc_op: int = CRC_NOP):
+    """zipc_hip_inflate_history, one stream from host memory -> (status, bytes, checksum)"""
+    out = (C.c_ubyte * max(dst_cap, 1))()
+    n, ck = C.c_size_t(), C.c_uint32()
+    st = lib().zipc_hip_inflate_history(ctx.handle, raw, len(raw), start_bit, hist, len(hist), int(limit is not None), limit or 0,
+                                        out, dst_cap, crc_op, C.byref(n), C.byref(ck))
+    return st, bytes(out[:n.value]), int(ck.value)
+
+
+def zlib_decompress_dict(ctx: Context, raw: bytes, zdict: bytes, dst_cap: int):
+    """zipc_hip_zlib_decompress_dict, one zlib stream from host memory against `zdict` -> (status, bytes)"""
+    out = (C.c_ubyte * max(dst_cap, 1))()
+    n = C.c_size_t()
+    st = lib().zipc_hip_zlib_decompress_dict(ctx.handle, raw, len(raw), zdict, len(zdict), out, dst_cap, C.byref(n))
+    return st, bytes(out[:n.value])
+
+
 def inflate_size_blocks_batch(ctx: Context, src, descs_dev, results_dev, n_streams: int):
     """zipc_hip_inflate_size_blocks_batch: inflate_size_batch's results, the long streams of the call sized by a wave per
     block (Context.last_size_blocks tells how many blocks went that way).  The call synchronises the context's stream."""

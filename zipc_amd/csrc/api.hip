@@ -19,6 +19,7 @@
 #include "packed_layout.h"
 #include "recode_rules.h"
 #include "tuning.h"
+#include "inflate_history.h"
 #include "zlib_container.h"
 
 using namespace zd;
@@ -320,7 +321,7 @@ void zipc_hip_destroy(zipc_hip_ctx *ctx) {
   free_buf(ctx->tok_scratch);
   free_buf(ctx->descs_marked);
   free_buf(ctx->size_descs); free_buf(ctx->size_head); free_buf(ctx->size_rest);
-  free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre); free_buf(ctx->gzip_descs); free_buf(ctx->gzip_pre); free_buf(ctx->prefix_adlers); free_buf(ctx->extent_inner);
+  free_buf(ctx->zlib_descs); free_buf(ctx->zlib_pre); free_buf(ctx->gzip_descs); free_buf(ctx->gzip_pre); free_buf(ctx->prefix_adlers); free_buf(ctx->zlib_hist); free_buf(ctx->dict_adler); free_buf(ctx->io_dict); free_buf(ctx->extent_inner);
   free_buf(ctx->recode_descs); free_buf(ctx->recode_res); free_buf(ctx->recode_verdicts);
   free_buf(ctx->packed_descs); free_buf(ctx->packed_res); free_buf(ctx->packed_verdicts);
   free_buf(ctx->dpacked_staging); free_buf(ctx->dpacked_descs); free_buf(ctx->dpacked_res);
@@ -434,6 +435,27 @@ int zipc_hip_inflate_prefix_batch(zipc_hip_ctx *ctx, const void *d_src_arena, vo
                                   zipc_hip_prefix_result *d_results, size_t n_streams) {
   if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
   return launch_inflate_prefix(ctx, d_src_arena, d_dst_arena, d_descs, d_results, n_streams, ZIPC_HIP_CRC_NOP, nullptr);
+}
+
+// The history forms (inflate_history.h has the rule): the three forms above started from a record per stream
+int zipc_hip_inflate_history_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                   const zipc_hip_history *d_hist, zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap,
+                                   int crc_op) {
+  if (!ctx || !d_descs || !d_results) return ZIPC_HIP_ERR_INVALID_ARG;
+  if (crc_op < 0 || crc_op > 3 || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  return launch_inflate_history(ctx, d_src_arena, d_dst_arena, d_descs, d_hist, d_results, n_streams, max_dst_cap, crc_op);
+}
+
+int zipc_hip_inflate_prefix_history_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                          const zipc_hip_history *d_hist, zipc_hip_prefix_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  return launch_inflate_prefix_history(ctx, d_src_arena, d_dst_arena, d_descs, d_hist, d_results, n_streams);
+}
+
+int zipc_hip_inflate_size_history_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                        const zipc_hip_history *d_hist, zipc_hip_stream_result *d_results, size_t n_streams) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  return launch_inflate_size_history(ctx, d_src_arena, d_descs, d_hist, d_results, n_streams);
 }
 
 int zipc_hip_inflate_size_blocks_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
@@ -880,6 +902,120 @@ int zipc_hip_zlib_decompress_prefix_batch(zipc_hip_ctx *ctx, const void *d_src_a
                              zlib_crc_op(ctx), (uint32_t *)ctx->prefix_adlers.p);
   if (st) return st;
   return launch_zlib_close_prefix(ctx, d_results, n_streams);
+}
+
+// The zlib dictionary forms (zlib_container.h zlib_open_dict): RFC 1950's Adler-32 of the dictionary by the checksum kernels
+// into the context's scratch, the open that compares every DICTID with it and leaves a history record per stream, (to
+// decompress) the seed and the history kernel over the bodies with the context's Adler-32, or the sizing history kernel,
+// and the close.  Nothing is read back.
+static int zlib_dict_front(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, size_t n_streams, const void *d_dict,
+                           size_t dict_len) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->ensure(ctx->dict_adler, 2 * sizeof(uint32_t)));
+  if (dict_len) {  // (always RFC 1950's: the DICTID is zlib's, whatever flavour this context compares outputs in)
+    const bool flavour = ctx->adler_rfc1950;
+    ctx->adler_rfc1950 = true;
+    const int st = zipc_hip_checksum_device(ctx, d_dict, dict_len, 0, 1, (uint32_t *)ctx->dict_adler.p);
+    ctx->adler_rfc1950 = flavour;
+    if (st) return st;
+  }
+  return launch_zlib_open_dict(ctx, d_src_arena, d_descs, n_streams, dict_len, (const uint32_t *)ctx->dict_adler.p + 1);
+}
+int zipc_hip_zlib_decompress_dict_batch(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                        zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap, const void *d_dict,
+                                        size_t dict_len) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull || dict_len > HISTORY_MAX_LEN || (!d_dict && dict_len)) return ZIPC_HIP_ERR_INVALID_ARG;
+  ctx->last_inflate_blocks = 0;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = zlib_dict_front(ctx, d_src_arena, d_descs, n_streams, d_dict, dict_len);
+  if (st) return st;
+  st = launch_zlib_seed_dict(ctx, d_dst_arena, d_descs, n_streams, d_dict, dict_len);
+  if (st) return st;
+  st = launch_inflate_history(ctx, d_src_arena, d_dst_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p,
+                              (const zipc_hip_history *)ctx->zlib_hist.p, d_results, n_streams, max_dst_cap, zlib_crc_op(ctx));
+  if (st) return st;
+  return launch_zlib_close_dict(ctx, d_results, n_streams, 0);
+}
+int zipc_hip_zlib_size_dict_batch(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
+                                  zipc_hip_stream_result *d_results, size_t n_streams, const void *d_dict, size_t dict_len) {
+  if (!ctx || !d_descs || !d_results || n_streams > 0x7FFFFFFFull || dict_len > HISTORY_MAX_LEN || (!d_dict && dict_len)) return ZIPC_HIP_ERR_INVALID_ARG;
+  ctx->last_size_blocks = 0;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  int st = zlib_dict_front(ctx, d_src_arena, d_descs, n_streams, d_dict, dict_len);
+  if (st) return st;
+  st = launch_inflate_size_history(ctx, d_src_arena, (const zipc_hip_stream_desc *)ctx->zlib_descs.p, (const zipc_hip_history *)ctx->zlib_hist.p,
+                                   d_results, n_streams);
+  if (st) return st;
+  return launch_zlib_close_dict(ctx, d_results, n_streams, 1);
+}
+
+// The host forms of the two: one stream staged as [history | room] in the context's buffers, the batch form of one, the
+// result's 16 bytes and then the room alone copied back
+static int history_room_back(zipc_hip_ctx *ctx, size_t gap, void *dst, size_t dst_cap, size_t *out_len, uint32_t *checksum) {
+  StreamResult r;
+  HIP_TRY(ctx, hipMemcpyAsync(&r, ctx->io_res.p, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (r.status != ST_OK) {
+    if (checksum) *checksum = r.checksum;  // (ZIPC_HIP_ERR_ZLIB_DICT: the DICTID found, ZIPC_HIP_ERR_CHECKSUM: the value found; else 0)
+    return (int)r.status;
+  }
+  if (r.out_len > dst_cap) return ZIPC_HIP_ERR_DST_TOO_SMALL;
+  if (r.out_len) {
+    HIP_TRY(ctx, hipMemcpyAsync(dst, (const uint8_t *)ctx->io_dst.p + gap, r.out_len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  *out_len = r.out_len;
+  if (checksum) *checksum = r.checksum;
+  return ZIPC_HIP_OK;
+}
+int zipc_hip_inflate_history(zipc_hip_ctx *ctx, const void *src, size_t len, unsigned start_bit, const void *hist, size_t hist_len,
+                             int has_limit, size_t limit, void *dst, size_t dst_cap, int crc_op, size_t *out_len, uint32_t *checksum) {
+  if (!ctx || (!src && len) || (!hist && hist_len) || (!dst && dst_cap) || !out_len) return ZIPC_HIP_ERR_INVALID_ARG;
+  *out_len = 0;
+  if (checksum) *checksum = 0;
+  if (history_record_status(hist_len > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)hist_len, start_bit, hist_len, true) != ST_OK)
+    return ZIPC_HIP_ERR_INVALID_ARG;  // (before anything is staged: the gap is hist_len bytes)
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int st = stage_in(ctx, src, len);
+  if (st) return st;
+  HIP_TRY(ctx, ctx->ensure(ctx->io_dst, hist_len + dst_cap + 64));
+  HIP_TRY(ctx, ctx->ensure(ctx->io_desc, sizeof(StreamDesc)));
+  HIP_TRY(ctx, ctx->ensure(ctx->io_res, sizeof(StreamResult)));
+  HIP_TRY(ctx, ctx->ensure(ctx->io_small, 64));
+  if (hist_len) HIP_TRY(ctx, hipMemcpyAsync(ctx->io_dst.p, hist, hist_len, hipMemcpyHostToDevice, ctx->stream));
+  StreamDesc d;
+  memset(&d, 0, sizeof d);
+  d.src_off = 0; d.src_len = len; d.dst_off = hist_len; d.dst_cap = dst_cap;
+  d.limit = limit; d.flags = has_limit ? STREAM_HAS_LIMIT : 0;
+  HistoryRec h;
+  h.hist_len = (uint32_t)hist_len; h.start_bit = start_bit;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->io_desc.p, &d, sizeof d, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->io_small.p, &h, sizeof h, hipMemcpyHostToDevice, ctx->stream));
+  st = zipc_hip_inflate_history_batch(ctx, ctx->io_src.p, ctx->io_dst.p, (const zipc_hip_stream_desc *)ctx->io_desc.p,
+                                      (const zipc_hip_history *)ctx->io_small.p, (zipc_hip_stream_result *)ctx->io_res.p, 1, dst_cap, crc_op);
+  if (st) return st;
+  return history_room_back(ctx, hist_len, dst, dst_cap, out_len, checksum);
+}
+int zipc_hip_zlib_decompress_dict(zipc_hip_ctx *ctx, const void *src, size_t len, const void *dict, size_t dict_len, void *dst, size_t dst_cap,
+                                  size_t *out_len) {
+  if (!ctx || (!src && len) || (!dict && dict_len) || (!dst && dst_cap) || !out_len || dict_len > HISTORY_MAX_LEN) return ZIPC_HIP_ERR_INVALID_ARG;
+  *out_len = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int st = stage_in(ctx, src, len);
+  if (st) return st;
+  HIP_TRY(ctx, ctx->ensure(ctx->io_dst, dict_len + dst_cap + 64));
+  HIP_TRY(ctx, ctx->ensure(ctx->io_dict, dict_len + 64));
+  HIP_TRY(ctx, ctx->ensure(ctx->io_desc, sizeof(StreamDesc)));
+  HIP_TRY(ctx, ctx->ensure(ctx->io_res, sizeof(StreamResult)));
+  if (dict_len) HIP_TRY(ctx, hipMemcpyAsync(ctx->io_dict.p, dict, dict_len, hipMemcpyHostToDevice, ctx->stream));
+  StreamDesc d;
+  memset(&d, 0, sizeof d);
+  d.src_off = 0; d.src_len = len; d.dst_off = dict_len; d.dst_cap = dst_cap;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->io_desc.p, &d, sizeof d, hipMemcpyHostToDevice, ctx->stream));
+  st = zipc_hip_zlib_decompress_dict_batch(ctx, ctx->io_src.p, ctx->io_dst.p, (const zipc_hip_stream_desc *)ctx->io_desc.p,
+                                           (zipc_hip_stream_result *)ctx->io_res.p, 1, dst_cap, ctx->io_dict.p, dict_len);
+  if (st) return st;
+  return history_room_back(ctx, dict_len, dst, dst_cap, out_len, nullptr);
 }
 
 // The zlib extent forms: open as ever (its `expect`, read at src_len - 4, is not used), the extent kernel over the bodies, and

@@ -58,6 +58,7 @@ struct zipc_hip_ctx {
   Buf size_descs, size_head, size_rest;                      // sizing by blocks: the call's descriptors with no destination (dst_off 0, dst_cap the longest stream's), the heads' results and span slots, the one-wave results of the streams left
   Buf zlib_descs, zlib_pre;                       // the zlib batch forms: the descriptors the codec runs with, the container checks' verdicts (zlib.hip)
   Buf gzip_descs, gzip_pre;                       // the gzip batch forms: the descriptors the codec runs with, the headers' verdicts, lengths and FLGs (gzip.hip)
+  Buf zlib_hist, dict_adler, io_dict;             // the zlib dictionary forms: the history record of every stream (zlib.hip zlib_open_dict_kernel), the dictionary's Adler-32 (two words: zipc_hip_checksum_device's), the host form's copy of the dictionary
   Buf prefix_adlers;                              // the zlib prefix form: the Adler-32 of every stream that ended within its room (inflate.hip inflate_prefix_kernel)
   Buf extent_inner;                               // the extent decode form with CRC-32: a StreamResult per stream for the checksum pass (inflate.hip launch_inflate_extent)
   Buf recode_descs, recode_res, recode_verdicts;  // the recode forms: the descriptors inflate, then deflate run with, their results, what is known of a stream between the steps (recode.hip)
@@ -170,6 +171,17 @@ int launch_inflate_size(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_h
 // stream for the Adler-32 of those that ended (the zlib form)
 int launch_inflate_prefix(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
                           zipc_hip_prefix_result *d_results, size_t n_streams, int crc_op, uint32_t *d_adlers);
+// inflate.hip: the history forms behind their argument checks (a ZIPC_HIP_* status each; inflate_history.h has the rule):
+// inflate_history_kernel / inflate_prefix_history_kernel / inflate_size_history_kernel, a wave per stream whatever its room,
+// one launch on ctx->cur, nothing read back; d_hist: null (no stream has history), or a record per stream.
+// launch_inflate_history with ZIPC_HIP_CRC_CRC32: the checksum pass behind it, over d_descs' rooms.
+int launch_inflate_history(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                           const zipc_hip_history *d_hist, zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap,
+                           int crc_op);
+int launch_inflate_prefix_history(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                  const zipc_hip_history *d_hist, zipc_hip_prefix_result *d_results, size_t n_streams);
+int launch_inflate_size_history(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, const zipc_hip_history *d_hist,
+                                zipc_hip_stream_result *d_results, size_t n_streams);
 // inflate.hip: the extent forms behind their argument checks (a ZIPC_HIP_* status each; inflate_extent.h has the rule).
 // launch_inflate_extent: inflate_extent_kernel, a wave per stream whatever max_dst_cap, one launch on ctx->cur, and for
 // ZIPC_HIP_CRC_CRC32 the checksum pass behind it; launch_inflate_size_extent: inflate_size_extent_kernel, one launch;
@@ -218,6 +230,13 @@ int launch_zlib_close(zipc_hip_ctx *ctx, void *d_dst_arena, const zipc_hip_strea
                       size_t n, int compress, int level);
 int launch_zlib_close_size(zipc_hip_ctx *ctx, zipc_hip_stream_result *d_results, size_t n);
 int launch_zlib_close_prefix(zipc_hip_ctx *ctx, zipc_hip_prefix_result *d_results, size_t n);  // (the Adler-32s: ctx->prefix_adlers)
+// ... of the dictionary forms (zlib_container.h zlib_open_dict): the open also leaves a history record per stream in
+// ctx->zlib_hist (d_dict_adler: a device word, RFC 1950's Adler-32 of the dictionary; not read when dict_len is 0); the seed
+// copies the dictionary in front of the room of every stream opened with FDICT; size 1: the sizing form's close
+int launch_zlib_open_dict(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, size_t n, size_t dict_len,
+                          const uint32_t *d_dict_adler);
+int launch_zlib_seed_dict(zipc_hip_ctx *ctx, void *d_dst_arena, const zipc_hip_stream_desc *d_descs, size_t n, const void *d_dict, size_t dict_len);
+int launch_zlib_close_dict(zipc_hip_ctx *ctx, zipc_hip_stream_result *d_results, size_t n, int size);
 // ... of the extent forms: d_descs the caller's (the trailer is read at 2 + the body's extent); compare 0: the sizing form's
 int launch_zlib_close_extent(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs,
                              zipc_hip_extent_result *d_results, size_t n, int compare);

@@ -53,6 +53,7 @@
 #include "inflate_blocks.h"
 #include "inflate_extent.h"
 #include "inflate_find.h"
+#include "inflate_history.h"
 #include "inflate_lane.h"
 #include "inflate_span.h"
 #include "tuning.h"
@@ -652,7 +653,11 @@ __device__ __forceinline__ Explore no_explore() {
 // EXTENT (with IM_REAL or IM_SIZE): the extent forms' wave (inflate_extent_kernel, inflate_size_extent_kernel) -- the plain
 // wave to its last instruction but the result store: an ExtentResult (inflate_extent.h extent_result) from the status, the
 // Adler-32, the length and the position the wave stands at, which is exactly behind the final block (see that header).
-template <int MODE, bool MULTI = false, bool REUSE = false, bool HEAD = false, bool PREFIX = false, bool EXTENT = false>
+// HISTORY (with IM_REAL or IM_SIZE, and with PREFIX): the history forms' wave (inflate_history_kernel, inflate_prefix_history_kernel,
+// inflate_size_history_kernel) -- the plain wave started by inflate_history.h's bias behind lane_init: at.out_pos bytes of history
+// lie in front of the stream's room and count as written, the first header stands at bit at.bit (0..7) of the source's
+// first byte.  The result store takes the bias off again.  Nothing between the two knows of it.
+template <int MODE, bool MULTI = false, bool REUSE = false, bool HEAD = false, bool PREFIX = false, bool EXTENT = false, bool HISTORY = false>
 __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t *__restrict__ src_arena, uint8_t *__restrict__ dst_arena,
                                                  const StreamDesc &sd, const BlockStart at, StreamResult *__restrict__ result,
                                                  uint16_t *__restrict__ span_idx, uint32_t *__restrict__ tok, int crc_op,
@@ -660,6 +665,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
                                                  uint32_t *__restrict__ adler_out = nullptr) {
   static_assert(!PREFIX || (MODE == IM_REAL && !MULTI && !REUSE && !HEAD), "the prefix form is the stream's plain wave");
   static_assert(!EXTENT || ((MODE == IM_REAL || MODE == IM_SIZE) && !MULTI && !REUSE && !HEAD && !PREFIX), "the extent forms are the stream's plain wave");
+  static_assert(!HISTORY || ((MODE == IM_REAL || MODE == IM_SIZE) && !MULTI && !REUSE && !HEAD && !EXTENT), "the history forms are the stream's plain wave");
   const int lane = threadIdx.x;
   const bool crc_adler = MODE == IM_REAL && (crc_op == CRC_ADLER32 || crc_op == CRC_ADLER32_RFC);
   const bool adler_rfc = crc_op == CRC_ADLER32_RFC;
@@ -674,6 +680,9 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
   InflateLane d;
   if (MODE == IM_SIZE) lane_init_size(d, sd);  // (no destination: dst_off and dst_cap are not looked at)
   else lane_init(d, sd);
+  if constexpr (HISTORY) {  // (the descriptor's own tests are made: on the caller's values)
+    if (d.status == ST_OK) history_start(d, at.out_pos, (uint32_t)at.bit, MODE != IM_SIZE);
+  }
   if (MODE != IM_REAL && MODE != IM_SIZE && d.status == ST_OK) {
     d.in_word = (uint32_t)(at.bit >> 5);
     d.boff = (uint32_t)at.bit & 31u;
@@ -975,7 +984,7 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
   if constexpr (HEAD) { e.pad = n_listed; return e; }
   if constexpr (PREFIX) {
     if (writer) {
-      const PrefixResult r = prefix_result(d.status, d.out_pos, d.cap_min);
+      const PrefixResult r = HISTORY ? history_prefix_result(d.status, d.out_pos, d.cap_min, at.out_pos) : prefix_result(d.status, d.out_pos, d.cap_min);
       *(PrefixResult *)result = r;
       if (adler_out != nullptr) *adler_out = crc_adler && r.ended ? d.adler : 0u;
     }
@@ -987,6 +996,10 @@ __device__ __forceinline__ BlockEnd inflate_wave(uint8_t *lds_raw, const uint8_t
     return e;
   }
   if (MODE != IM_REAL && MODE != IM_SIZE) return e;
+  if constexpr (HISTORY) {
+    if (writer || (MODE == IM_SIZE && lane == 0)) *result = history_result(d.status, crc_adler ? d.adler : 0u, d.out_pos, at.out_pos);
+    return e;
+  }
   if (writer || (MODE == IM_SIZE && lane == 0)) {
     StreamResult r;
     r.status = d.status;
@@ -1141,6 +1154,72 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   at.bit = 0; at.out_pos = 0; at.chunk0 = 0;
   inflate_wave<IM_SIZE, false, false, false, false, true>(lds_raw, src_arena, nullptr, descs[stream], at, (StreamResult *)(results + stream),
                                                           span_scratch + (size_t)stream * SPAN_IDX_ENTRIES, nullptr, CRC_NOP);
+}
+// The history forms: the stream's wave started from a record (HISTORY, inflate_wave; inflate_history.h has the rule) -- hist:
+// null (every record {0, 0}: the form without history, result for result), or a HistoryRec per stream.  A record the rule
+// refuses is the stream's own ST_INVALID_ARG, before its flags are looked at.  One kernel each for every call size, always
+// a wave per stream.
+__device__ __forceinline__ bool history_skips_stream(const HistoryRec *__restrict__ hist, uint32_t stream, uint64_t dst_off, bool has_dst,
+                                                     BlockStart &at, StreamResult *result) {
+  HistoryRec h;
+  h.hist_len = 0; h.start_bit = 0;
+  if (hist != nullptr) h = hist[stream];
+  at.bit = h.start_bit; at.out_pos = h.hist_len; at.chunk0 = 0;
+  if (history_record_status(h.hist_len, h.start_bit, dst_off, has_dst) == ST_OK) return false;
+  if ((threadIdx.x & 63u) == 0) {
+    StreamResult r;
+    r.status = ST_INVALID_ARG; r.checksum = 0; r.out_len = 0;
+    *result = r;
+  }
+  return true;
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void inflate_history_kernel(const uint8_t *__restrict__ src_arena,
+                                                           uint8_t *__restrict__ dst_arena,
+                                                           const StreamDesc *__restrict__ descs,
+                                                           const HistoryRec *__restrict__ hist,
+                                                           StreamResult *__restrict__ results,
+                                                           uint32_t n_streams, uint16_t *__restrict__ span_scratch, int crc_op) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LDS_BYTES_PER_LANE];
+  const uint32_t stream = blockIdx.x;
+  if (stream >= n_streams) return;
+  BlockStart at;
+  if (history_skips_stream(hist, stream, descs[stream].dst_off, true, at, results + stream)) return;
+  if (inflate_skips_stream(descs[stream].flags, crc_op, results + stream)) return;
+  inflate_wave<IM_REAL, false, false, false, false, false, true>(lds_raw, src_arena, dst_arena, descs[stream], at, results + stream,
+                                                                 span_scratch + (size_t)stream * SPAN_IDX_ENTRIES, nullptr, crc_op);
+}
+// ... the first dst_cap bytes from the start point (inflate_prefix_kernel's wave and record)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void inflate_prefix_history_kernel(const uint8_t *__restrict__ src_arena,
+                                                           uint8_t *__restrict__ dst_arena,
+                                                           const StreamDesc *__restrict__ descs,
+                                                           const HistoryRec *__restrict__ hist,
+                                                           PrefixResult *__restrict__ results,
+                                                           uint32_t n_streams, uint16_t *__restrict__ span_scratch) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LDS_BYTES_PER_LANE];
+  const uint32_t stream = blockIdx.x;
+  if (stream >= n_streams) return;
+  int crc_op = CRC_NOP;
+  BlockStart at;
+  if (history_skips_stream(hist, stream, descs[stream].dst_off, true, at, (StreamResult *)(results + stream))) return;
+  if (inflate_skips_stream(descs[stream].flags, crc_op, (StreamResult *)(results + stream))) return;
+  inflate_wave<IM_REAL, false, false, false, true, false, true>(lds_raw, src_arena, dst_arena, descs[stream], at, (StreamResult *)(results + stream),
+                                                                span_scratch + (size_t)stream * SPAN_IDX_ENTRIES, nullptr, CRC_NOP);
+}
+// ... and the sizing form: inflate_size_kernel's wave (no arena but the source is touched: the record serves the distance test alone)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void inflate_size_history_kernel(const uint8_t *__restrict__ src_arena,
+                                                                  const StreamDesc *__restrict__ descs,
+                                                                  const HistoryRec *__restrict__ hist,
+                                                                  StreamResult *__restrict__ results, uint32_t n_streams,
+                                                                  uint16_t *__restrict__ span_scratch) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LDS_BYTES_PER_LANE];
+  const uint32_t stream = blockIdx.x;
+  if (stream >= n_streams) return;
+  int crc_op = CRC_NOP;
+  BlockStart at;
+  if (history_skips_stream(hist, stream, 0, false, at, results + stream)) return;
+  if (inflate_skips_stream(descs[stream].flags, crc_op, results + stream)) return;
+  inflate_wave<IM_SIZE, false, false, false, false, false, true>(lds_raw, src_arena, nullptr, descs[stream], at, results + stream,
+                                                                 span_scratch + (size_t)stream * SPAN_IDX_ENTRIES, nullptr, CRC_NOP);
 }
 // what the checksum pass left in inner[i], into the stream's ExtentResult (inflate_extent.h extent_with_crc): the CRC-32 of an
 // OK stream, or the pass's own refusal of one whose output is longer than the call's max_dst_cap
@@ -2365,6 +2444,50 @@ int launch_inflate_prefix(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_ds
   ZD_LAUNCH(ctx, "inflate_prefix", inflate_prefix_kernel, dim3((unsigned)n_streams), dim3(64), 0, (const uint8_t *)d_src_arena,
             (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs, (PrefixResult *)d_results, (uint32_t)n_streams,
             (uint16_t *)ctx->inflate_scratch.p, crc_op, d_adlers);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+
+// The history forms behind their argument checks, and the zlib dictionary forms' middle step (ctx.h): one launch each, a wave
+// per stream whatever its room, on the context's stream -- no by-blocks path, no stored-chain path, nothing read back.
+// ZIPC_HIP_CRC_CRC32: the checksum pass over [dst_off, dst_off + out_len) behind the kernel, with the caller's descriptors.
+int launch_inflate_history(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                           const zipc_hip_history *d_hist, zipc_hip_stream_result *d_results, size_t n_streams, size_t max_dst_cap,
+                           int crc_op) {
+  ctx->last_inflate_blocks = 0;  // (zipc_hip_last_inflate_blocks: no stream of this call goes by blocks)
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_streams * INFLATE_SCRATCH_PER_STREAM));
+  if (crc_op == ZIPC_HIP_CRC_CRC32 && n_streams * crc32_segs(max_dst_cap) > 0x7FFFFFFFull) return ZIPC_HIP_ERR_INVALID_ARG;
+  ZD_LAUNCH(ctx, "inflate_history", inflate_history_kernel, dim3((unsigned)n_streams), dim3(64), 0, (const uint8_t *)d_src_arena,
+            (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs, (const HistoryRec *)d_hist, (StreamResult *)d_results, (uint32_t)n_streams,
+            (uint16_t *)ctx->inflate_scratch.p, crc_op);
+  HIP_TRY(ctx, hipGetLastError());
+  if (crc_op != ZIPC_HIP_CRC_CRC32) return ZIPC_HIP_OK;
+  return crc32_pass(ctx, (const uint8_t *)d_dst_arena, RANGE_INFLATE_OUT, (const StreamDesc *)d_descs, (StreamResult *)d_results, n_streams,
+                    0, 0, max_dst_cap, nullptr);
+}
+int launch_inflate_prefix_history(zipc_hip_ctx *ctx, const void *d_src_arena, void *d_dst_arena, const zipc_hip_stream_desc *d_descs,
+                                  const zipc_hip_history *d_hist, zipc_hip_prefix_result *d_results, size_t n_streams) {
+  ctx->last_inflate_blocks = 0;
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_streams * INFLATE_SCRATCH_PER_STREAM));
+  ZD_LAUNCH(ctx, "inflate_prefix_history", inflate_prefix_history_kernel, dim3((unsigned)n_streams), dim3(64), 0, (const uint8_t *)d_src_arena,
+            (uint8_t *)d_dst_arena, (const StreamDesc *)d_descs, (const HistoryRec *)d_hist, (PrefixResult *)d_results, (uint32_t)n_streams,
+            (uint16_t *)ctx->inflate_scratch.p);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+int launch_inflate_size_history(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, const zipc_hip_history *d_hist,
+                                zipc_hip_stream_result *d_results, size_t n_streams) {
+  ctx->last_size_blocks = 0;  // (zipc_hip_last_size_blocks: every stream by its one wave)
+  if (n_streams == 0) return ZIPC_HIP_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, ctx->ensure(ctx->inflate_scratch, n_streams * INFLATE_SCRATCH_PER_STREAM));
+  ZD_LAUNCH(ctx, "inflate_size_history", inflate_size_history_kernel, dim3((unsigned)n_streams), dim3(64), 0, (const uint8_t *)d_src_arena,
+            (const StreamDesc *)d_descs, (const HistoryRec *)d_hist, (StreamResult *)d_results, (uint32_t)n_streams,
+            (uint16_t *)ctx->inflate_scratch.p);
   HIP_TRY(ctx, hipGetLastError());
   return ZIPC_HIP_OK;
 }

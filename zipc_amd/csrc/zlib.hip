@@ -11,10 +11,16 @@
 //                      Adler-32 compared, a cut one's not.
 //   zlib_close_extent_kernel, zlib_close_size_extent_kernel  the same behind inflate's extent kernels (zipc_hip_zlib_decompress_extent_batch,
 //                      zipc_hip_zlib_size_extent_batch): the trailer found behind the body's extent, not at src_len - 4.
+//   zlib_open_dict_kernel, zlib_seed_dict_kernel, zlib_close_dict_kernel  the dictionary forms (zipc_hip_zlib_decompress_dict_batch,
+//                      zipc_hip_zlib_size_dict_batch): the open that reads a DICTID and leaves a history record per stream, the
+//                      copy of the dictionary in front of the rooms that decode with it, the close that reports a DICTID.
 // The rules themselves are zlib_container.h's (the host forms and the tests compile the same functions).  Nothing is
 // read back: the calls enqueue and return like the raw batch forms.  The launches at the end of this file are the one
 // way to the kernels (ctx.h).
 #include "ctx.h"
+#include "deflate_packed.h"
+#include "inflate_history.h"
+#include "wave_ops.h"
 #include "zlib_container.h"
 
 namespace zd {
@@ -123,6 +129,92 @@ __global__ __launch_bounds__(256) void zlib_close_size_extent_kernel(const uint8
   results[i] = zlib_close_extent(pre[i].status, descs[i].src_len, src_arena + descs[i].src_off, results[i], false);
 }
 
+// The dictionary forms' open, a lane per stream (zlib_container.h zlib_open_dict): zlib_open_kernel's decompress half with
+// the FDICT branch -- the descriptor the history kernel runs with (the body; the room is the caller's), the stream's
+// history record, the verdict.  dict_adler: a device word, not read when dict_len is 0.
+__global__ __launch_bounds__(256) void zlib_open_dict_kernel(const uint8_t *__restrict__ src_arena, const StreamDesc *__restrict__ descs,
+                                                             uint32_t n_streams, uint64_t dict_len, const uint32_t *__restrict__ dict_adler,
+                                                             StreamDesc *__restrict__ inner, HistoryRec *__restrict__ hist,
+                                                             ZlibPre *__restrict__ pre) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_streams) return;
+  const StreamDesc sd = descs[i];
+  ZlibPre p;
+  p.status = ST_OK;
+  p.expect = 0;
+  StreamDesc in = sd;
+  HistoryRec h;
+  h.hist_len = 0; h.start_bit = 0;
+  if ((sd.flags & ~STREAM_HAS_LIMIT) != 0) {
+    p.status = ST_INVALID_ARG;
+  } else {
+    uint32_t cmf = 0, flg = 0, dictid = 0;
+    const uint8_t *s = src_arena + sd.src_off;
+    if (sd.src_len >= ZLIB_MIN_LEN) {  // (the length first: nothing is read of a shorter stream)
+      cmf = s[0];
+      flg = s[1];
+      dictid = zlib_dictid(s + 2);
+    }
+    const ZlibDictOpen o = zlib_open_dict(sd.src_len, cmf, flg, dictid, dict_len, dict_len ? dict_adler[0] : 0u);
+    p.status = o.status;
+    if (o.status == ST_OK) {
+      p.expect = zlib_expect(s + sd.src_len - 4);
+      in.src_off = sd.src_off + o.body_off;
+      in.src_len = o.body_len;
+      h.hist_len = o.hist_len;
+    } else {
+      p.expect = o.dictid;
+    }
+  }
+  if (p.status != ST_OK) in = zlib_no_stream(sd);
+  inner[i] = in;
+  hist[i] = h;
+  pre[i] = p;
+}
+
+// The seed, a workgroup per stream: the dictionary to [dst_off - hist_len, dst_off) of every stream zlib_dict_seeds names,
+// at any byte alignment of either side -- deflate_packed.h's copy rule (dpacked_span: single bytes up to the destination's
+// first 16-byte boundary, whole aligned units loaded unaligned, single bytes behind them).  The one kernel of these forms
+// that writes in front of dst_off; nothing is written in front of the gap.
+static_assert(HISTORY_MAX_LEN <= DPACKED_SEG_BYTES, "a dictionary is one segment of the copy rule");
+__global__ __launch_bounds__(DPACKED_COPY_THREADS) void zlib_seed_dict_kernel(uint8_t *__restrict__ dst_arena, const StreamDesc *__restrict__ descs,
+                                                                              const HistoryRec *__restrict__ hist, const ZlibPre *__restrict__ pre,
+                                                                              uint32_t n_streams, const uint8_t *__restrict__ dict) {
+  const uint32_t i = blockIdx.x;
+  if (i >= n_streams) return;
+  const uint32_t len = hist[i].hist_len;
+  const uint64_t dst_off = descs[i].dst_off;
+  if (!zlib_dict_seeds(pre[i].status, len, dst_off)) return;
+  uint8_t *d = dst_arena + (dst_off - len);
+  const DpackedSpan sp = dpacked_span(len, 0, (uint64_t)(uintptr_t)d);
+  const uint8_t *s = dict;
+  const uint32_t t = threadIdx.x;
+  const uint32_t rounds = dpacked_rounds(sp.units);
+  for (uint32_t r = 0; r < rounds; r++) {
+    u32x4 v[DPACKED_IN_FLIGHT];
+#pragma unroll
+    for (uint32_t j = 0; j < DPACKED_IN_FLIGHT; j++) {
+      const uint32_t u = dpacked_unit_of(r, j, t);
+      if (u < sp.units) v[j] = load16_unaligned(s + dpacked_unit_at(sp, u));
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < DPACKED_IN_FLIGHT; j++) {
+      const uint32_t u = dpacked_unit_of(r, j, t);
+      if (u < sp.units) *reinterpret_cast<u32x4 *>(d + dpacked_unit_at(sp, u)) = v[j];
+    }
+  }
+  if (t < sp.head) d[t] = s[t];
+  if (t < sp.tail) d[dpacked_tail_at(sp) + t] = s[dpacked_tail_at(sp) + t];
+}
+
+// The dictionary forms' closes (zlib_close_dict): size 0 -- the Adler-32 of the output alone against the trailer; 1 -- nothing compared
+__global__ __launch_bounds__(256) void zlib_close_dict_kernel(const ZlibPre *__restrict__ pre, StreamResult *__restrict__ results,
+                                                              uint32_t n_streams, int size) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_streams) return;
+  results[i] = zlib_close_dict(pre[i].status, pre[i].expect, results[i], size != 0);
+}
+
 int zlib_crc_op(const zipc_hip_ctx *ctx) { return ctx->adler_rfc1950 ? ZIPC_HIP_CRC_ADLER32_RFC1950 : ZIPC_HIP_CRC_ADLER32; }
 
 // zlib_open_kernel over the caller's descriptors: the codec's descriptors and the checks' verdicts, in the context's scratch
@@ -152,6 +244,32 @@ int launch_zlib_close_size(zipc_hip_ctx *ctx, zipc_hip_stream_result *d_results,
 int launch_zlib_close_prefix(zipc_hip_ctx *ctx, zipc_hip_prefix_result *d_results, size_t n) {
   ZD_LAUNCH(ctx, "zlib_close_prefix", zlib_close_prefix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
             (const ZlibPre *)ctx->zlib_pre.p, (const uint32_t *)ctx->prefix_adlers.p, (PrefixResult *)d_results, (uint32_t)n);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+
+int launch_zlib_open_dict(zipc_hip_ctx *ctx, const void *d_src_arena, const zipc_hip_stream_desc *d_descs, size_t n, size_t dict_len,
+                          const uint32_t *d_dict_adler) {
+  HIP_TRY(ctx, ctx->ensure(ctx->zlib_descs, n * sizeof(StreamDesc)));
+  HIP_TRY(ctx, ctx->ensure(ctx->zlib_pre, n * sizeof(ZlibPre)));
+  HIP_TRY(ctx, ctx->ensure(ctx->zlib_hist, n * sizeof(HistoryRec)));
+  ZD_LAUNCH(ctx, "zlib_open_dict", zlib_open_dict_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint8_t *)d_src_arena,
+            (const StreamDesc *)d_descs, (uint32_t)n, (uint64_t)dict_len, d_dict_adler, (StreamDesc *)ctx->zlib_descs.p,
+            (HistoryRec *)ctx->zlib_hist.p, (ZlibPre *)ctx->zlib_pre.p);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+int launch_zlib_seed_dict(zipc_hip_ctx *ctx, void *d_dst_arena, const zipc_hip_stream_desc *d_descs, size_t n, const void *d_dict, size_t dict_len) {
+  if (dict_len == 0) return ZIPC_HIP_OK;  // (no stream was opened with FDICT)
+  ZD_LAUNCH(ctx, "zlib_seed_dict", zlib_seed_dict_kernel, dim3((unsigned)n), dim3(DPACKED_COPY_THREADS), 0, (uint8_t *)d_dst_arena,
+            (const StreamDesc *)d_descs, (const HistoryRec *)ctx->zlib_hist.p, (const ZlibPre *)ctx->zlib_pre.p, (uint32_t)n,
+            (const uint8_t *)d_dict);
+  HIP_TRY(ctx, hipGetLastError());
+  return ZIPC_HIP_OK;
+}
+int launch_zlib_close_dict(zipc_hip_ctx *ctx, zipc_hip_stream_result *d_results, size_t n, int size) {
+  ZD_LAUNCH(ctx, "zlib_close_dict", zlib_close_dict_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+            (const ZlibPre *)ctx->zlib_pre.p, (StreamResult *)d_results, (uint32_t)n, size);
   HIP_TRY(ctx, hipGetLastError());
   return ZIPC_HIP_OK;
 }

@@ -109,6 +109,47 @@ ZD_HD ExtentResult zlib_close_extent(uint32_t pre, uint64_t src_len, const uint8
   inner.src_used = u + 6u;
   return inner;
 }
+// ---- zlib streams with a preset dictionary (zipc_hip_zlib_decompress_dict_batch, zipc_hip_zlib_size_dict_batch): RFC 1950's
+// FDICT, as deflateSetDictionary makes them.  One dictionary of dict_len bytes serves the call; dict_adler is RFC 1950's
+// Adler-32 of it, whatever flavour the context compares outputs in (the DICTID is the encoder's, and zlib's is RFC 1950's).
+constexpr uint64_t ZLIB_DICT_MIN_LEN = 10;  // CMF, FLG, the DICTID and the Adler-32
+// what the open says of a stream: the verdict; on ST_ZLIB_DICT the DICTID found (a caller can look the right dictionary
+// up), else 0; on ST_OK the body as [body_off, body_off + body_len) of the stream and the history it decodes with
+struct ZlibDictOpen {
+  uint32_t status, dictid;
+  uint64_t body_off, body_len;
+  uint32_t hist_len;
+};
+// the DICTID: bytes 2..5, big-endian
+ZD_HD uint32_t zlib_dictid(const uint8_t *at2) {
+  return ((uint32_t)at2[0] << 24) | ((uint32_t)at2[1] << 16) | ((uint32_t)at2[2] << 8) | (uint32_t)at2[3];
+}
+// zlib_open_status's checks in their order up to the FDICT test.  A stream without FDICT is opened exactly as
+// zipc_hip_zlib_decompress_batch opens it and decodes with no history (zlib does the same).  One with FDICT: len < 10 is
+// ST_CORRUPTED; no dictionary, or another DICTID than the dictionary's, is ST_ZLIB_DICT; otherwise the body is [6, len - 4)
+// and the whole dictionary is its history.  dictid: the stream's (read only when len >= 10 and FDICT is set: callers
+// that cannot read it pass anything).
+ZD_HD ZlibDictOpen zlib_open_dict(uint64_t len, uint32_t cmf, uint32_t flg, uint32_t dictid, uint64_t dict_len, uint32_t dict_adler) {
+  ZlibDictOpen o;
+  o.status = zlib_open_status(len, cmf, flg); o.dictid = 0; o.body_off = 0; o.body_len = 0; o.hist_len = 0;
+  if (o.status == ST_OK) { o.body_off = zlib_body_off(0); o.body_len = zlib_body_len(len); return o; }
+  if (o.status != ST_ZLIB_DICT) return o;
+  if (len < ZLIB_DICT_MIN_LEN) { o.status = ST_CORRUPTED; return o; }
+  if (dict_len == 0 || dictid != dict_adler) { o.dictid = dictid; return o; }
+  o.status = ST_OK; o.body_off = 6; o.body_len = len - ZLIB_DICT_MIN_LEN; o.hist_len = (uint32_t)dict_len;
+  return o;
+}
+// The seed: the dictionary is copied to [dst_off - hist_len, dst_off) of a stream that was opened with FDICT and has the
+// gap (a stream without it is ST_INVALID_ARG by inflate_history.h's rule).  The gap of a stream without FDICT, or of one
+// that failed its open, is not written.
+ZD_HD bool zlib_dict_seeds(uint32_t pre, uint32_t hist_len, uint64_t dst_off) { return pre == ST_OK && hist_len != 0 && dst_off >= hist_len; }
+// The closes: zlib_close_decompress / zlib_close_size, but a stream whose dictionary is not the call's reports the
+// DICTID it asks for (`expect` holds it then: the trailer was not read)
+ZD_HD StreamResult zlib_close_dict(uint32_t pre, uint32_t expect, StreamResult inner, bool size) {
+  if (pre == ST_ZLIB_DICT) { inner.status = pre; inner.checksum = expect; inner.out_len = 0; return inner; }
+  return size ? zlib_close_size(pre, inner) : zlib_close_decompress(pre, expect, inner);
+}
+
 // zlib_compress: `inner` is deflate's, the result counts the container's bytes too.  *wrap: the caller has to put the
 // header and the trailer (inner.checksum, behind inner.out_len bytes of payload) around what deflate wrote.
 ZD_HD StreamResult zlib_close_compress(uint32_t pre, StreamResult inner, bool *wrap) {
